@@ -47,6 +47,16 @@ Prints ONE JSON line (rank 0).  `value` = samples processed by all ranks / max-o
 from ONE HIP-event pair recorded on the launch stream around the timed region.  `robustness` (c2, N = 1): the same 65,536-channel
 chain on adverse inputs / settings that defeat its data-dependent fast paths, measured the same way after the headline region.
 `cpu_baseline` is the CPU oracle (a port, the reference is unbuildable here) timed on this host on a bounded sample of C2.
+
+`--full`: a plain run sets up, settles the clocks, warms up, times the K steps and prints the line -- only what `value` and
+`ms_per_step` need.  Everything measured or read beside the headline runs with `--full` alone: `roofline.steady_state`,
+`roofline.caller_stream_ordered`, `roofline.kernel_ms_event_pair_per_launch`, `roofline.traffic`, `roofline_issue`,
+`roofline_latency`, `h2d_d2h_inclusive`, `robustness`, `configs` and `cpu_baseline` (the --no-* flags still drop them one by one).
+
+`--dump-outputs DIR`: after the timed steps, the audio the last timed step produced (what a caller of asdr_update_device /
+asdr_capture_update_device receives) is written as DIR/audio.npy in float32, [channels][128] (c5: [channels][646][128]); the
+inputs are seeded, so two builds run with the same arguments can be compared sample for sample.  Beyond DUMP_BYTES the rows are
+a fixed sample of channels (dump_rows: seed 0, ascending).  Several ranks / shards write audio_rank<r>.npy / audio_shard<g>.npy.
 """
 import argparse
 import json
@@ -62,6 +72,7 @@ sys.path.insert(0, ROOT)
 BLOCK = 128
 HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md: 8.0 TB/s spec
 N_INPUT_BLOCKS = 4                    # distinct resident input blocks cycled through by the steps
+DUMP_BYTES = 32 << 20                 # --dump-outputs: float32 bytes per run at most (the whole C2 output, 65,536 x 128, fits)
 PMC_FILE = os.path.join("profiles", "pmc_latest.json")
 ISSUE_FILE = os.path.join("profiles", "issue_latest.json")
 LATENCY_FILE = os.path.join("profiles", "roofline_latency_latest.json")
@@ -228,6 +239,28 @@ def cpu_baseline(seconds_budget=14.0):
                       % (n_ch, n_blk, threads, note)}
 
 
+def dump_rows(n_rows, row_bytes, budget):
+    """Rows of an output that --dump-outputs writes: all of them when they fit `budget` bytes, else a fixed sample (seed 0, ascending)."""
+    import numpy as np
+    k = max(1, budget // row_bytes)
+    if n_rows <= k:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(0).choice(n_rows, k, replace=False))
+
+
+def dump_audio(out_dir, name, rows):
+    """One int16 output of the timed path as <out_dir>/<name>.npy in float32 (exact: every int16 is a float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), np.asarray(rows, dtype=np.float32))
+
+
+def device_rows(torch, t, budget):
+    """dump_rows of a device tensor [rows][...] int16, copied to the host."""
+    idx = dump_rows(t.shape[0], t[0].numel() * 4, budget)
+    return t[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+
+
 def free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
     return p
@@ -315,7 +348,7 @@ def configure_c3(sdr):   # SAM, blanker at 10 dB (else no lock, Q2
 
 
 def other_configs(np, torch, dev, local_rank):
-    """BASELINE configs 3, 4 and 5 (their single-GPU shares) ON THE DRIVER'S RECORD: the default `bench.py --gpus 1` line carries, beside
+    """BASELINE configs 3, 4 and 5 (their single-GPU shares) beside the headline: the `bench.py --gpus 1 --full` line carries, beside
     C2's headline, one short measured region per config -- same method (one HIP-event pair on the launch stream, ASDR_STREAM_BATCH:
     lanes where the schedule has them), SURVEY 8(d)'s bytes, and a one-channel bit-for-bit spot check against the CPU oracle of the
     blocks in front of the region.  C3 and C4 carry TWO regions, like the C2 line (its timed window | `roofline.steady_state`):
@@ -527,6 +560,9 @@ def main_single_process(args, cfg, settle_min, warm_req):
     sync()
     wall = time.perf_counter() - t0
     launched = A.binding.kernels_launched()
+    if args.dump_outputs:
+        for g, (_, _, dOut, _) in enumerate(bufs):
+            dump_audio(args.dump_outputs, "audio_shard%d" % g, device_rows(torch, dOut, DUMP_BYTES // G))
     per_gpu_ms = wall / args.steps * 1e3
     algo = cfg["algo"] * total_ch
     ach = algo / G / (per_gpu_ms * 1e-3) / 1e9      # per GPU: each holds 1/G of the channels
@@ -570,7 +606,13 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (C3 / C4 share / C5 share beside C2's headline)")
     ap.add_argument("--caller-stream", action="store_true",
                     help="launch on torch's current stream (strict stream order) instead of ASDR_STREAM_BATCH")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / read everything beside the headline (module docstring); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's audio as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes no outputs")
     if args.autopin_leg:
         import numpy as np
         print(json.dumps(host_path(np, args.device, args.channels or 65536, only_autopin=True)))
@@ -709,6 +751,15 @@ def main():
     t1 = time.perf_counter()
     wall = t1 - t0
     launched = A.binding.kernels_launched() if batch is not None else {}
+    if args.dump_outputs and batch is not None:   # (before anything below runs more steps on the batch)
+        name = "audio" if world == 1 else "audio_rank%d" % rank
+        if args.config == "c5":   # the last call's T blocks at the end of every channel's capture row
+            pos = batch.capture_position
+            idx = dump_rows(n_ch, T * BLOCK * 4, DUMP_BYTES // world)
+            rows = np.stack([batch.capture_read(int(c), pos - T, T).reshape(T, BLOCK) for c in idx])
+        else:
+            rows = device_rows(torch, dOut, DUMP_BYTES // world)
+        dump_audio(args.dump_outputs, name, rows)
     if not args.dry_run and scratch is not None:
         scratch.close()
     k_ms = region_ms / max(1, region_calls) if batch is not None else 0.0
@@ -716,7 +767,7 @@ def main():
     ordered = None
     steady = None
     lane_calls = batch.lane_calls() if batch is not None else 0
-    if batch is not None and args.config == "c2" and args.steps < 1000:
+    if args.full and batch is not None and args.config == "c2" and args.steps < 1000:
         # A short timed region (the driver's --warmup 5 --steps 20) is the first few blocks of a FRESH receiver bank: the AGC's envelope
         # is still creeping up to the signal's peaks (attacking samples in most eight-sample chunks; profiles/README.md "The first blocks
         # of a fresh batch").  `value` stays what those steps took; the same batch after 500 further steps is reported beside it.
@@ -726,7 +777,7 @@ def main():
                   "what": "the same batch, same launch form, after the timed region: 500 untimed steps, then one HIP-event pair around 1,500 "
                           "steps -- the receiver bank in its steady state (the timed region above is blocks %d..%d of a fresh bank)"
                           % (args.warmup, args.warmup + args.steps - 1)}
-    if batch is not None and args.config == "c2":
+    if args.full and batch is not None and args.config == "c2":
         if not args.caller_stream:   # the same steps in strict stream order, on a caller's stream
             def cs_step(i):
                 b = i % N_INPUT_BLOCKS
@@ -756,7 +807,7 @@ def main():
         try:
             with open(os.path.join(ROOT, PMC_FILE)) as f:
                 pj = json.load(f)
-            if args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
+            if args.full and args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
                 import audiosdr_amd as A
                 from audiosdr_amd import build as _build
                 same_binary = pj.get("library_sha256") == A.library_sha256()
@@ -776,7 +827,7 @@ def main():
         try:
             with open(os.path.join(ROOT, ISSUE_FILE)) as f:
                 ij = json.load(f)
-            if args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
+            if args.full and args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
                 from audiosdr_amd import build as _build
                 if ij.get("source_sha256") == _build.source_sha256():
                     floor = ij.get("valu_floor_ms")
@@ -799,7 +850,7 @@ def main():
         try:
             with open(os.path.join(ROOT, LATENCY_FILE)) as f:
                 lj = json.load(f)
-            if args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
+            if args.full and args.config == "c2" and n_ch == CHANNELS_PER_GPU and not args.dry_run:
                 from audiosdr_amd import build as _build
                 if lj.get("source_sha256") == _build.source_sha256():
                     latency = {k: lj.get(k) for k in ("kernel", "model", "wave_lifetime_cycles", "model_over_measured", "ms_per_step", "shader_clock_ghz_assumed",
@@ -861,7 +912,7 @@ def main():
                 out["config"]["times_real_time"] = round(T * BLOCK / 44100.0 / (k_ms * 1e-3), 1)
         if args.dry_run:
             out["dry_run"] = True
-        if world == 1 and args.config == "c2" and not args.dry_run and not (args.no_robustness and args.no_host_path and args.no_configs):
+        if args.full and world == 1 and args.config == "c2" and not args.dry_run and not (args.no_robustness and args.no_host_path and args.no_configs):
             if batch is not None:
                 batch.close(); batch = None
             del dI, dQ
@@ -871,7 +922,7 @@ def main():
                 out["robustness"] = robustness(np, torch, dev, local_rank, n_ch, stream, 300)
             if not args.no_configs:
                 out["configs"] = other_configs(np, torch, dev, local_rank)
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if batch is not None:

@@ -1,8 +1,8 @@
 #!/bin/bash
 # One GPU-box call that produces everything profiles/ needs for the current build (copy the results from gpurun_out/<tag>/):
-#   bench.json              python bench.py (default flags: the driver's N=1 command; headline + robustness + cpu_baseline)
-#   bench_driver.json       python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's exact command line)
-#   kernel_stats.csv        rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-robustness --no-host-path` (the headline: on
+#   bench.json              python bench.py --full (default steps; headline + robustness + configs + cpu_baseline)
+#   bench_driver.json       python bench.py --gpus 1 --steps 20 --warmup 5 --full (the driver's command line + the steady_state beside it)
+#   kernel_stats.csv        rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline --no-robustness --no-host-path` (the headline: on
 #                           ASDR_STREAM_BATCH every step is TWO half-size launches of asdr_update_kernel, one per lane, in flight together)
 #   kernel_stats_caller_stream.csv   the same with --caller-stream (strict stream order: one launch per step)
 #   pmc.json                rocprofv3 --pmc passes of the C2 command (tools/prof_pmc2.sh; HBM traffic = 2*FETCH_SIZE + WRITE_SIZE)
@@ -16,12 +16,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-robustness --no-host-path --no-configs > "$OUT/stats.log" 2>&1 )
+python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-robustness --no-host-path --no-configs > "$OUT/stats.log" 2>&1 )
 f=$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv"
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_cs" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-robustness --no-host-path --no-configs --caller-stream > "$OUT/stats_cs.log" 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_cs" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-robustness --no-host-path --no-configs --caller-stream > "$OUT/stats_cs.log" 2>&1 )
 f=$(find "$OUT/stats_cs" -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" "$OUT/kernel_stats_caller_stream.csv"
 bash tools/prof_pmc2.sh "gpurun_out/$TAG/pmc" > "$OUT/pmc.log" 2>&1

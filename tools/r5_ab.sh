@@ -10,8 +10,8 @@ for r in $(seq 1 "$rounds"); do
     lib=${v%%@*}; envset=""; if [ "$lib" != "$v" ]; then envset=${v#*@}; fi
     if [ "$lib" = intree ]; then unset ASDR_TOOLS_LIB; else export ASDR_TOOLS_LIB=audiosdr_amd/variants/libasdr_$lib.so; fi
     if [ -n "$envset" ]; then export "$envset"; fi
-    python3 tools/bench_variant.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --no-robustness --no-configs > "$out/${v}_drv_$r.json" 2> "$out/${v}_drv_$r.err"
-    python3 tools/bench_variant.py --no-cpu-baseline --no-host-path --no-configs ${AB_EXTRA} > "$out/${v}_steady_$r.json" 2> "$out/${v}_steady_$r.err"
+    python3 tools/bench_variant.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-host-path --no-robustness --no-configs > "$out/${v}_drv_$r.json" 2> "$out/${v}_drv_$r.err"
+    python3 tools/bench_variant.py --full --no-cpu-baseline --no-host-path --no-configs ${AB_EXTRA} > "$out/${v}_steady_$r.json" 2> "$out/${v}_steady_$r.err"
     if [ -n "$envset" ]; then unset "${envset%%=*}"; fi
   done
 done
