@@ -1,0 +1,86 @@
+/* asdr_tuner.h -- C ABI of the digital tuner bank: per-receiver digital LO + decimating low-pass that turns shared wideband
+ * CS16 I/Q into the 44.1 kHz int16 I and Q rows asdr_update_device / asdr_capture_update_device consume.  It stands in for the
+ * reference's quadrature LO (EXTRAS/SI5351quad, tuned to `frequency - TuningOffset`, BareBonesWSPR.ino:102,116) and its codec.
+ * Not a function of the reference library: the arithmetic is this project's own and is stated below, integer-only, so results
+ * are bit-exact whatever the summation order.  Same library (libasdr_hip.so) and conventions as asdr.h / asdr_front.h: `ch` =
+ * channel index or ASDR_ALL (-1) for setters, ASDR_NO_DEVICE for a control-plane-only bank whose update calls fail, errors
+ * through asdr_last_error() (setters return 0 / -1).
+ *
+ * Arithmetic (all integer; sat16 clamps to [-32768, 32767]; >> is an arithmetic shift = floor):
+ *   bank      n_channels channels, n_sources sources, one decimation D in [1, 64], one filter h[0..L-1] int16, L in [1, 1024],
+ *             gain shift g in [0, 15].  Position P = input samples per source since creation / reset; x_s[m] = sample m of source s.
+ *   NCO       C[k] = round(32767 cos(2 pi k / 4096)), S[k] = round(32767 sin(2 pi k / 4096)) (asdr_tuner_tables.h).
+ *   channel   src, frequency word fw (uint32), anchor (pos_a, ph_a); theta(m) = ph_a + (m - pos_a) * fw mod 2^32 for m >= pos_a.
+ *   mixer     k = theta(m) >> 20, x = x_src[m]:  zr = sat16((xr C[k] + xi S[k] + 16384) >> 15),
+ *                                                zi = sat16((xi C[k] - xr S[k] + 16384) >> 15);   z[m] = 0 for m < pos_a.
+ *   filter    s = 15 - g, r = s ? 1 << (s - 1) : 0:  I[n] = sat16((sum_{k<L} h[k] zr[nD + D - 1 - k] + r) >> s), Q[n] likewise on zi.
+ *   retune    set_source / set_frequency / set_frequency_word / set_phase act at the current P: the channel is re-anchored
+ *             (pos_a = P; ph_a = theta_old(P), or the given phase for set_phase) and its history flushed (z = 0 before P) -- even
+ *             when the value does not change.  A new filter applies to outputs from P on; the sources' history is kept.
+ *   creation  P = 0, every anchor (0, 0), fw 0, src 0, source history zeros.  Default filter: D = 1 -> h = {16384}, g = 1 (exact
+ *             pass-through of z); D >= 2 -> a Kaiser low-pass of 12 D + 1 taps, g = 0 (DESIGN.md 3.8 gives its response).
+ */
+#ifndef ASDR_TUNER_H_
+#define ASDR_TUNER_H_
+
+#include <stdint.h>
+
+#include "asdr.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ASDR_TUNER_MAX_DECIMATION 64
+#define ASDR_TUNER_MAX_TAPS 1024
+#define ASDR_TUNER_MAX_GAIN_SHIFT 15
+#define ASDR_TUNER_HISTORY 1023 /* input samples per source kept across calls (L - 1 at most) */
+
+typedef struct asdr_tuner_bank asdr_tuner_t;
+
+typedef struct {
+  int32_t src;          /* source row */
+  uint32_t fw;          /* frequency word: phase step per input sample, 2^32 = one turn */
+  int64_t pos_a;        /* anchor position (input samples) */
+  uint32_t ph_a;        /* NCO phase at pos_a */
+  uint32_t reserved;
+} asdr_tuner_state_t;
+
+/* lifetime; NULL on failure (asdr_last_error) */
+asdr_tuner_t *asdr_tuner_create(int n_channels, int n_sources, int decimation, int device);
+void asdr_tuner_destroy(asdr_tuner_t *t);
+int asdr_tuner_reset(asdr_tuner_t *t);            /* P = 0, creation state for every channel and source; the filter is kept */
+long long asdr_tuner_position(const asdr_tuner_t *t);  /* P */
+int asdr_tuner_n_channels(const asdr_tuner_t *t);
+int asdr_tuner_n_sources(const asdr_tuner_t *t);
+int asdr_tuner_decimation(const asdr_tuner_t *t);
+
+/* control plane (all take effect at the current P) */
+int asdr_tuner_set_source(asdr_tuner_t *t, int ch, int source);
+/* hz in [-Fs_in/2, Fs_in/2], Fs_in = D * 44100: fw = (uint32)(int64)llround(hz * 2^32 / Fs_in).  To receive RF f of a capture
+ * centred at fc with the chain behind it: hz = f - fc - asdr_getTuningOffset(). */
+int asdr_tuner_set_frequency(asdr_tuner_t *t, int ch, double hz);
+int asdr_tuner_set_frequency_word(asdr_tuner_t *t, int ch, uint32_t fw);
+int asdr_tuner_set_phase(asdr_tuner_t *t, int ch, uint32_t phase);
+/* Rejected (old filter kept): L or g out of range, sum |h[k]| > 65535 (32-bit accumulation is then exact). */
+int asdr_tuner_set_filter(asdr_tuner_t *t, const int16_t *h, int n_taps, int gain_shift);
+/* Copies min(L, cap) taps to h (if not NULL) and g to *gain_shift (if not NULL); returns L. */
+int asdr_tuner_get_filter(const asdr_tuner_t *t, int16_t *h, int cap, int *gain_shift);
+int asdr_tuner_read_state(const asdr_tuner_t *t, asdr_tuner_state_t *dst /* [n_channels] */);
+
+/* The hot path.  dIQ: n_sources rows of interleaved re, im int16 (CS16), in_stride_samples complex samples apart, each holding
+ * n_blocks * 128 * D new samples.  dI, dQ: [n_channels][out_stride_blocks][128] int16 (as asdr_update_device_strided takes them);
+ * blocks 0..n_blocks-1 of every row are written.  Device pointers 16-byte aligned; the output spans must not overlap the input span.
+ *  _update_device : asynchronous on `stream` (a hipStream_t; NULL = the null stream).  A call on another stream than the
+ *                   previous one first waits (event) for that call's work.
+ *  _update        : host pointers, contiguous rows (in_stride = n_blocks * 128 * D, out_stride = n_blocks); synchronous. */
+int asdr_tuner_update_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
+                             long out_stride_blocks, void *stream);
+int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q, int n_blocks);
+int asdr_tuner_synchronize(asdr_tuner_t *t);
+float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its two kernels); -1 if none */
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ASDR_TUNER_H_ */

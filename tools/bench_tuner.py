@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Digital tuner bank (include/asdr_tuner.h) on the MI355X: one JSON line per config.  (GPU box.)
+
+  T1        skimmer: 1 source, D = 1, 512 channels, L = 257, 256 blocks per call
+  T2        one SDR: 1 source, D = 48, 4,096 channels, default filter, 64 blocks per call
+  T3        wide bank: 16 sources, D = 48, 65,536 channels (4,096 per source), default filter, 16 blocks per call
+  T3+chain  T3 followed by asdr_update_device (USB) on the same stream
+
+Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
+multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
+source, int16 I and Q out, the history rows); their share of the VALU issue bound and of HBM, and which of the two bounds the
+call.  The first call of each config is checked against tests/tuner_ref.py on a few channels.  Inputs are seeded.
+
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain]
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: E402  (first: one HIP runtime per process)
+import audiosdr_amd as A  # noqa: E402
+import tuner_ref as R  # noqa: E402
+
+VALU_LANE_OPS = 256 * 4 * 64 / 2 * 2.4e9     # CUs x SIMDs x wave64 lanes per 2-cycle issue x max clock: 7.86e13 lane-ops/s
+HBM_BPS = 6.29e12                             # measured float4 copy (MI355X_MICROARCH), not the 8 TB/s spec
+
+CONFIGS = {
+    "T1": dict(n_src=1, D=1, n_ch=512, L=257, nb=256),
+    "T2": dict(n_src=1, D=48, n_ch=4096, L=None, nb=64),
+    "T3": dict(n_src=16, D=48, n_ch=65536, L=None, nb=16),
+    "T3+chain": dict(n_src=16, D=48, n_ch=65536, L=None, nb=16, chain=True),
+}
+
+
+def run(name, n_src, D, n_ch, L, nb, chain=False):
+    rng = np.random.default_rng(sum(map(ord, name)))
+    bank = A.TunerBank(n_ch, n_src, D)
+    if L is not None:
+        h = np.round(np.hamming(L) * np.sinc((np.arange(L) - (L - 1) / 2) * 0.5) * 16384 / 2).astype(np.int16)
+        bank.set_filter(h, 0)
+    h, g = bank.get_filter()
+    L = h.size
+    srcs = np.arange(n_ch) % n_src
+    fws = rng.integers(0, 2**32, size=n_ch, dtype=np.uint64)
+    for c in range(n_ch):
+        bank.set_source(int(srcs[c]), ch=c); bank.set_frequency_word(int(fws[c]), ch=c)
+    N = nb * 128 * D
+    calls = 4                                              # distinct seeded inputs, cycled
+    iq = rng.integers(-12000, 12000, size=(calls, n_src, N, 2), endpoint=True).astype(np.int16)
+    dIQ = torch.from_numpy(iq).cuda()
+    dI = torch.empty((n_ch, nb, 128), dtype=torch.int16, device="cuda")
+    dQ = torch.empty_like(dI)
+    stream = torch.cuda.current_stream()
+    sp = stream.cuda_stream
+    sdr, dOut = None, None
+    if chain:
+        sdr = A.AudioSDRBatch(n_ch)
+        sdr.setDemodMode(A.USBmode)
+        dOut = torch.empty_like(dI)
+
+    def call(k):
+        bank.update_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, stream=sp)
+        if chain:
+            sdr.update_device(dI.data_ptr(), dQ.data_ptr(), dOut.data_ptr(), nb, stream=sp)
+
+    # parity of the first call on 8 channels
+    check = sorted(set([0, 1, n_ch - 1] + [int(c) for c in rng.integers(0, n_ch, size=5)]))
+    ref = R.TunerRef(len(check), n_src, D, h, g)
+    for i, c in enumerate(check):
+        ref.src[i], ref.fw[i] = int(srcs[c]), int(fws[c])
+    call(0)
+    torch.cuda.synchronize()
+    wI, wQ = ref.update(iq[0])
+    parity = bool(np.array_equal(dI.cpu().numpy()[check], wI) and np.array_equal(dQ.cpu().numpy()[check], wQ))
+    # warm, then size the timed window to >= 1 s
+    for k in range(1, 6):
+        call(k)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(3):
+        call(k)
+    torch.cuda.synchronize()
+    est = max((time.perf_counter() - t0) / 3, 1e-5)
+    reps = max(10, int(1.2 / est) + 1)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for k in range(reps):
+        call(k)
+    e1.record(stream)
+    e1.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    n_out = n_ch * nb * 128
+    macs = n_out * (4 * D + 2 * L)
+    nbytes = n_src * N * 4 + n_out * 4 + 2 * n_src * 1024 * 4
+    t_valu, t_hbm = macs / VALU_LANE_OPS, nbytes / HBM_BPS
+    bound = "valu" if t_valu >= t_hbm else "hbm"
+    out = {"config": name, "sources": n_src, "decimation": D, "channels": n_ch, "taps": int(L), "blocks_per_call": nb,
+           "chain": "USB" if chain else None, "timed_calls": reps, "timed_s": round(ms * reps / 1e3, 3),
+           "ms_per_call": round(ms, 4), "output_samples_per_s": round(n_out / (ms * 1e-3), 1),
+           "realtime_factor": round(nb * 128 / 44100.0 / (ms * 1e-3), 2),
+           "model": {"int_mult_adds": int(macs), "bytes": int(nbytes), "valu_bound_ms": round(t_valu * 1e3, 4),
+                     "hbm_bound_ms": round(t_hbm * 1e3, 4), "bound": bound,
+                     "share_of_bound": round(max(t_valu, t_hbm) / (ms * 1e-3), 4),
+                     "note": "tuner model only" if chain else None},
+           "parity_channels": len(check), "parity": parity}
+    print(json.dumps(out), flush=True)
+    bank.close()
+    if sdr is not None:
+        sdr.close()
+    return parity
+
+
+def main():
+    names = sys.argv[1:] or list(CONFIGS)
+    ok = True
+    for n in names:
+        ok = run(n, **CONFIGS[n]) and ok
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
