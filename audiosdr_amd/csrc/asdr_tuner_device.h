@@ -25,9 +25,33 @@ typedef struct {
   int32_t shift, round;             /* s = 15 - g, r = s ? 1 << (s - 1) : 0 */
 } TunerArgs;
 
+/* Stage 2 of a rate bank (asdr_tuner_resample.hip).  Window coordinates: w = 0 is u sample N_u - ASDR_TUNER_CARRY (N_u before the
+ * call); w < ASDR_TUNER_CARRY comes from the carry row, the rest from the call's intermediate rows. */
+#define ASDR_TUNER_CARRY 576          /* u samples per channel carried across calls: >= K - 1 + ceil(127 M / U) + 1 = 572 */
+#define ASDR_TUNER_RS_LANES 256
+#define ASDR_TUNER_RS_OUT 512         /* outputs per workgroup (4 blocks); its u window is at most 511 * 4 + 1 + 63 + 1 samples */
+#define ASDR_TUNER_RS_WIN 2112
+
+typedef struct {
+  const int16_t *mid_i, *mid_q;     /* [n_channels][n_frames * 128]: stage 1's u for this call */
+  const int32_t *carry_rd;          /* [n_channels][576]: u (I low, Q high) before N_u */
+  int32_t *carry_wr;                /* [n_channels][576]: u before N_u + 128 n_frames */
+  const int16_t *taps;              /* [U][KP]: taps[phi][k] = h2[k U + phi], zero past K */
+  const int32_t *lane_qr;           /* [512]: (o M / U) << 11 | (o M % U) for o < 512 */
+  int16_t *out_i, *out_q;           /* [n_channels][out_stride] */
+  int64_t out_stride;               /* output samples */
+  int32_t n_channels, n_frames, n_out;   /* n_out = output samples this call (128 x blocks) */
+  int32_t up, down, k, kp;          /* U, M, K, KP = K rounded up to 8 */
+  int32_t q0, r0;                   /* b_{j0} - (N_u - 576) and j0 M - b_{j0} U for the call's first output j0 */
+  int32_t tile_q, tile_r;           /* 512 M / U and 512 M % U */
+  int32_t shift, round;             /* s2, r2 */
+} ResampleArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the stage-2 step: every channel x 512-output tile (at least one tile: the carry is written even when no block is) */
+int asdr_launch_tuner_resample(const ResampleArgs *a, void *stream);
 /* the filter step (every channel x 128-output block) followed by the history step, in order on `stream` */
 int asdr_launch_tuner(const TunerArgs *a, void *stream);
 #ifdef __cplusplus

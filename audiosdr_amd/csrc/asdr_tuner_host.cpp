@@ -35,13 +35,11 @@ double bessel_i0(double x) {
   return s;
 }
 
-// The default filter (asdr_tuner.h): D = 1 -> {16384}, g = 1; D >= 2 -> a Kaiser-windowed sinc of 12 D + 1 taps (beta 9, cut-off
-// midway between 11.2 kHz and 32.1 kHz), normalised to unit DC gain and rounded to Q15, g = 0.  Its measured response: DESIGN.md 3.8.
-void default_filter(int D, std::vector<int16_t> &h, int &g) {
-  if (D == 1) { h.assign(1, 16384); g = 1; return; }
-  const int L = 12 * D + 1, M = L - 1;
-  const double fc = 0.5 * (11200.0 + 32100.0) / (44100.0 * D), beta = 9.0, pi = 3.14159265358979323846;
-  std::vector<double> w(L);
+// Kaiser-windowed (beta 9) sinc of L taps with cut-off fc (cycles per sample); returns the sum of the taps.
+double kaiser_sinc(int L, double fc, std::vector<double> &w) {
+  const int M = L - 1;
+  const double beta = 9.0, pi = 3.14159265358979323846;
+  w.assign(L, 0.0);
   double sum = 0.0;
   for (int n = 0; n < L; n++) {
     const double x = n - 0.5 * M, u = 2.0 * n / M - 1.0;
@@ -49,15 +47,82 @@ void default_filter(int D, std::vector<int16_t> &h, int &g) {
     w[n] = s * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / bessel_i0(beta);
     sum += w[n];
   }
+  return sum;
+}
+
+// The default filter (asdr_tuner.h): D = 1 -> {16384}, g = 1; D >= 2 -> a Kaiser-windowed sinc of 12 D + 1 taps (beta 9, cut-off
+// midway between 11.2 kHz and 32.1 kHz), normalised to unit DC gain and rounded to Q15, g = 0.  Its measured response: DESIGN.md 3.8.
+void default_filter(int D, std::vector<int16_t> &h, int &g) {
+  if (D == 1) { h.assign(1, 16384); g = 1; return; }
+  const int L = 12 * D + 1;
+  std::vector<double> w;
+  const double sum = kaiser_sinc(L, 0.5 * (11200.0 + 32100.0) / (44100.0 * D), w);
   h.resize(L);
   for (int n = 0; n < L; n++) h[n] = (int16_t)std::llround(32768.0 * w[n] / sum);
   g = 0;
+}
+
+// A rate bank's stage-1 default (asdr_tuner.h): the plain default at Fs_mid = 44100, else stop band from Fs_mid - 12 kHz, cut-off
+// midway between 11.2 kHz and that edge, L1 = 2 ceil(6 D Fs_mid 20900 / (44100 (Fs_mid - 23200))) + 1 taps.
+void default_rate_filter(int D, long long fs_mid, std::vector<int16_t> &h, int &g) {
+  if (fs_mid == 44100 || D == 1) { default_filter(D, h, g); return; }
+  const long long num = 6LL * D * fs_mid * 20900, den = 44100LL * (fs_mid - 23200);
+  const int L = (int)(2 * ((num + den - 1) / den) + 1);
+  std::vector<double> w;
+  const double sum = kaiser_sinc(L, 0.5 * (11200.0 + (double)(fs_mid - 12000)) / (double)(fs_mid * D), w);
+  h.resize(L);
+  for (int n = 0; n < L; n++) h[n] = (int16_t)std::llround(32768.0 * w[n] / sum);
+  g = 0;
+}
+
+// Stage-2 default: U = M = 1 -> {16384}, g2 = 1; otherwise a prototype of U K taps at U Fs_mid, cut-off 21.65 kHz,
+// K = 2 ceil(6 Fs_mid / 44100); each phase rounded to Q15 on its own, the residual to 32768 put on its largest tap; g2 = 0.
+void default_resampler(int U, int M, long long fs_mid, std::vector<int16_t> &h2, int &g2) {
+  if (U == 1 && M == 1) { h2.assign(1, 16384); g2 = 1; return; }
+  const int K = (int)(2 * ((6 * fs_mid + 44099) / 44100)), L = U * K;
+  std::vector<double> w;
+  const double sum = kaiser_sinc(L, 21650.0 / ((double)U * (double)fs_mid), w);
+  h2.assign(L, 0);
+  for (int ph = 0; ph < U; ph++) {
+    long long tot = 0;
+    int big = ph;
+    for (int k = 0; k < K; k++) {
+      const int i = k * U + ph;
+      h2[i] = (int16_t)std::llround(32768.0 * U * w[i] / sum);
+      tot += h2[i];
+      if (h2[i] > h2[big]) big = i;
+    }
+    h2[big] = (int16_t)(h2[big] + (32768 - tot));
+  }
+  g2 = 0;
+}
+
+long long gcd_ll(long long a, long long b) { while (b) { const long long r = a % b; a = b; b = r; } return a; }
+
+// U K taps and g2 passing the set_resampler rules for a bank with up-factor U
+std::string resampler_error(int U, const int16_t *h2, int n_taps, int g2) {
+  if (!h2) return "null taps";
+  if (n_taps < U || n_taps % U != 0) return "resampler length must be a multiple of U";
+  if (n_taps / U > ASDR_TUNER_MAX_RESAMPLER_TAPS) return "resampler taps per phase (K) must be in 1..64";
+  if (g2 < 0 || g2 > ASDR_TUNER_MAX_GAIN_SHIFT) return "gain shift must be in 0..15";
+  for (int ph = 0; ph < U; ph++) {
+    long sum = 0;
+    for (int i = ph; i < n_taps; i += U) sum += std::labs((long)h2[i]);
+    if (sum > 65535) return "a resampler phase has sum of |h2| over 65535";
+  }
+  return "";
 }
 }  // namespace
 
 struct asdr_tuner_bank {
   int n = 0, n_src = 0, D = 1, device = ASDR_NO_DEVICE;
   long long pos = 0;
+  // rate bank (stage 2): Fs_in, U / M, the prototype [U K] and g2, output samples written
+  long long fs_in = 44100;
+  int up = 1, down = 1, k2 = 1, g2 = 1;
+  std::vector<int16_t> h2;
+  long long out_pos = 0;
+  bool rs_dirty = true, carry_stale = false;
   std::vector<asdr_tuner_state_t> chan;
   std::vector<int32_t> order;
   std::vector<int16_t> h;
@@ -73,6 +138,13 @@ struct asdr_tuner_bank {
   bool ev_valid = false;
   void *d_io = nullptr;               // staging for asdr_tuner_update
   size_t io_cap = 0;
+  // stage 2: taps [U][KP] + the lane table, the carry rows (double-buffered, allocated by the first stage-2 call), the intermediate
+  int16_t *d_rs_taps = nullptr;
+  int32_t *d_lane_qr = nullptr, *d_carry[2] = {nullptr, nullptr};
+  int ccur = 0;                       // d_carry[ccur] holds the u samples before N_u
+  int kp = 8;
+  int16_t *d_mid = nullptr;           // [2][n][n_frames * 128]
+  size_t mid_cap = 0;
 };
 
 namespace {
@@ -127,18 +199,95 @@ int push(asdr_tuner_t *t, hipStream_t stream) {
 }
 
 bool overlap(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return a0 < b0 + bn && b0 < a0 + an; }
-}  // namespace
 
-extern "C" {
+// stage 2 is a pass-through (the output is u): U = M = 1, K = 1, h2 = {1 << s2}
+bool pass_through(const asdr_tuner_t *t) {
+  return t->up == 1 && t->down == 1 && t->h2.size() == 1 && t->g2 >= 1 && t->h2[0] == (1 << (15 - t->g2));
+}
 
-asdr_tuner_t *asdr_tuner_create(int n_channels, int n_sources, int decimation, int device) {
+// b = floor(j M / U) and j M - b U without forming j M (exact for every j >= 0)
+void split(long long j, int U, int M, long long &b, int &r) {
+  const long long jq = j / U, jr = j % U;
+  b = jq * M + (jr * M) / U;
+  r = (int)((jr * M) % U);
+}
+
+// output blocks written by a call of n_frames frames: block J is out once b_{128 J + 127} <= N_u - 1, i.e.
+// (128 J + 127) M <= N_u U - 1
+long long blocks_after(const asdr_tuner_t *t, int n_frames) {
+  const __int128 n_u = (__int128)(t->pos / t->D) + (__int128)128 * n_frames;
+  const __int128 num = n_u * t->up - 1 - (__int128)127 * t->down;
+  const long long j_next = t->out_pos / 128;
+  const long long j_end = num < 0 ? 0 : (long long)(num / ((__int128)128 * t->down)) + 1;   // blocks 0 .. j_end - 1 are out
+  return j_end > j_next ? j_end - j_next : 0;
+}
+
+int push_resampler(asdr_tuner_t *t, hipStream_t stream) {
+  if (!t->rs_dirty) return 0;
+  const int U = t->up, K = t->k2;
+  t->kp = (K + 7) & ~7;
+  std::vector<int16_t> taps((size_t)U * t->kp, 0);
+  for (int ph = 0; ph < U; ph++)
+    for (int k = 0; k < K; k++) taps[(size_t)ph * t->kp + k] = t->h2[(size_t)k * U + ph];
+  std::vector<int32_t> qr(ASDR_TUNER_RS_OUT);
+  for (int o = 0; o < ASDR_TUNER_RS_OUT; o++) qr[o] = ((o * t->down / U) << 11) | (o * t->down % U);
+  HIPCHK(hipMemcpyAsync(t->d_rs_taps, taps.data(), taps.size() * sizeof(int16_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(t->d_lane_qr, qr.data(), qr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  t->rs_dirty = false;
+  return 0;
+}
+
+// The stage-1 launch of a call: n_blocks blocks of every channel into rows out_stride_blocks apart, then P advances.
+int run_stage1(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
+               long out_stride_blocks, hipStream_t stream) {
+  TunerArgs a;
+  a.in = (const int32_t *)dIQ; a.hist_rd = t->d_hist[t->cur]; a.hist_wr = t->d_hist[t->cur ^ 1];
+  a.chan = t->d_chan; a.order = t->d_order; a.taps = t->d_taps; a.out_i = dI; a.out_q = dQ;
+  a.pos = t->pos; a.in_stride = in_stride_samples; a.out_stride = (int64_t)out_stride_blocks * 128;
+  a.n_channels = t->n; a.n_sources = t->n_src; a.n_blocks = n_blocks; a.decimation = t->D;
+  a.n_phase_rows = t->n_rows; a.n_phase_pairs = t->n_pairs;
+  a.shift = 15 - t->g; a.round = a.shift ? 1 << (a.shift - 1) : 0;
+  if (asdr_launch_tuner(&a, stream) != 0) return fail("tuner kernel launch failed");
+  t->pos += (long long)n_blocks * 128 * t->D;
+  t->cur ^= 1;
+  return 0;
+}
+
+// The argument checks shared by the update entry points (n_blocks = stage-1 blocks = frames, out_blocks = output row length).
+int check_io(const asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, const int16_t *dI, const int16_t *dQ, int n_blocks,
+             long out_stride_blocks, long out_blocks) {
+  if (n_blocks > 65535 || (long long)n_blocks * 128 * t->D > (1LL << 30)) return fail("too many blocks in one call");
+  const long long n_in = (long long)n_blocks * 128 * t->D;
+  if (in_stride_samples < n_in) return fail("input row stride shorter than n_blocks * 128 * D samples");
+  if (out_stride_blocks < out_blocks) return fail("output row stride shorter than n_blocks");
+  if (in_stride_samples > (1LL << 40) || out_stride_blocks > (1LL << 30)) return fail("row stride too large");
+  if ((((uintptr_t)dIQ | (uintptr_t)dI | (uintptr_t)dQ) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
+  const size_t in_bytes = ((size_t)(t->n_src - 1) * in_stride_samples + n_in) * 4;
+  const size_t out_bytes = ((size_t)(t->n - 1) * out_stride_blocks + out_blocks) * 128 * 2;
+  if (overlap((uintptr_t)dI, out_bytes, (uintptr_t)dIQ, in_bytes) || overlap((uintptr_t)dQ, out_bytes, (uintptr_t)dIQ, in_bytes))
+    return fail("output span overlaps the input span");
+  if (overlap((uintptr_t)dI, out_bytes, (uintptr_t)dQ, out_bytes)) return fail("I and Q output spans overlap");
+  return 0;
+}
+
+asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int decimation, int device) {
   if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
   if (n_sources <= 0 || n_sources > 65535) { fail("n_sources must be in 1..65535"); return nullptr; }
   if (decimation < 1 || decimation > ASDR_TUNER_MAX_DECIMATION) { fail("decimation must be in 1..64"); return nullptr; }
+  if (fs_in <= 0) { fail("input rate Fs_in must be positive"); return nullptr; }
+  if (fs_in % decimation != 0) { fail("input rate Fs_in is not a multiple of the decimation D"); return nullptr; }
+  const long long fs_mid = fs_in / decimation;
+  if (fs_mid < 44100 || fs_mid > 4 * 44100) { fail("Fs_in / D must lie in [44100, 176400] Hz"); return nullptr; }
+  const long long gd = gcd_ll(44100, fs_mid);
+  if (44100 / gd > ASDR_TUNER_MAX_UP) { fail("44100 / (Fs_in / D) in lowest terms needs U > 2048"); return nullptr; }
   asdr_tuner_bank *t = new asdr_tuner_bank();
   t->n = n_channels; t->n_src = n_sources; t->D = decimation; t->device = device;
+  t->fs_in = fs_in; t->up = (int)(44100 / gd); t->down = (int)(fs_mid / gd);
   t->chan.assign(n_channels, fresh_state());
-  default_filter(decimation, t->h, t->g);
+  default_rate_filter(decimation, fs_mid, t->h, t->g);
+  default_resampler(t->up, t->down, fs_mid, t->h2, t->g2);
+  t->k2 = (int)t->h2.size() / t->up;
   if (device == ASDR_NO_DEVICE) return t;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete t; return nullptr; }
@@ -148,12 +297,26 @@ asdr_tuner_t *asdr_tuner_create(int n_channels, int n_sources, int decimation, i
       hipEventCreate(&t->ev1) != hipSuccess || hipMalloc(&t->d_chan, n_channels * sizeof(asdr_tuner_state_t)) != hipSuccess ||
       hipMalloc(&t->d_order, n_channels * sizeof(int32_t)) != hipSuccess || hipMalloc(&t->d_taps, kTapWords * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&t->d_hist[0], hist) != hipSuccess || hipMalloc(&t->d_hist[1], hist) != hipSuccess ||
+      hipMalloc(&t->d_rs_taps, (size_t)t->up * ASDR_TUNER_MAX_RESAMPLER_TAPS * sizeof(int16_t)) != hipSuccess ||
+      hipMalloc(&t->d_lane_qr, ASDR_TUNER_RS_OUT * sizeof(int32_t)) != hipSuccess ||
       hipMemset(t->d_hist[0], 0, hist) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     fail("tuner bank: device allocation failed");
     asdr_tuner_destroy(t);
     return nullptr;
   }
   return t;
+}
+}  // namespace
+
+extern "C" {
+
+asdr_tuner_t *asdr_tuner_create(int n_channels, int n_sources, int decimation, int device) {
+  if (decimation < 1 || decimation > ASDR_TUNER_MAX_DECIMATION) { fail("decimation must be in 1..64"); return nullptr; }
+  return create_bank(n_channels, n_sources, 44100LL * decimation, decimation, device);
+}
+
+asdr_tuner_t *asdr_tuner_create_rate(int n_channels, int n_sources, long long fs_in_hz, int decimation, int device) {
+  return create_bank(n_channels, n_sources, fs_in_hz, decimation, device);
 }
 
 void asdr_tuner_destroy(asdr_tuner_t *t) {
@@ -162,6 +325,7 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipSetDevice(t->device);
     hipDeviceSynchronize();
     hipFree(t->d_chan); hipFree(t->d_order); hipFree(t->d_taps); hipFree(t->d_hist[0]); hipFree(t->d_hist[1]); hipFree(t->d_io);
+    hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -174,9 +338,12 @@ int asdr_tuner_reset(asdr_tuner_t *t) {
   if (t->device != ASDR_NO_DEVICE) {
     if (asdr_tuner_synchronize(t) != 0) return -1;
     HIPCHK(hipMemset(t->d_hist[t->cur], 0, (size_t)t->n_src * ASDR_TUNER_HIST_SLOTS * sizeof(int32_t)));
+    if (t->d_carry[t->ccur]) HIPCHK(hipMemset(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t)));
     HIPCHK(hipDeviceSynchronize());
   }
   t->pos = 0;
+  t->out_pos = 0;
+  t->carry_stale = false;
   std::fill(t->chan.begin(), t->chan.end(), fresh_state());
   t->chan_dirty = t->order_dirty = true;
   return 0;
@@ -196,7 +363,7 @@ int asdr_tuner_set_source(asdr_tuner_t *t, int ch, int source) {
 
 int asdr_tuner_set_frequency(asdr_tuner_t *t, int ch, double hz) {
   if (!t) return fail("null tuner bank");
-  const double fs = 44100.0 * t->D;
+  const double fs = (double)t->fs_in;
   if (!(hz >= -0.5 * fs && hz <= 0.5 * fs)) return fail("frequency outside [-Fs_in/2, Fs_in/2]");
   const uint32_t fw = (uint32_t)(int64_t)std::llround(hz * 4294967296.0 / fs);
   return retune(t, ch, [fw](asdr_tuner_state_t &s) { s.fw = fw; });
@@ -243,42 +410,27 @@ int asdr_tuner_update_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride
                              long out_stride_blocks, void *stream_) {
   if (!t) return fail("null tuner bank");
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (!pass_through(t)) return fail("stage 2 of this bank resamples: use asdr_tuner_update_rate_device / asdr_tuner_update_rate");
   if (!dIQ || !dI || !dQ) return fail("null device pointer");
   if (n_blocks <= 0) return 0;
-  if (n_blocks > 65535 || (long long)n_blocks * 128 * t->D > (1LL << 30)) return fail("too many blocks in one call");
-  const long long n_in = (long long)n_blocks * 128 * t->D;
-  if (in_stride_samples < n_in) return fail("input row stride shorter than n_blocks * 128 * D samples");
-  if (out_stride_blocks < n_blocks) return fail("output row stride shorter than n_blocks");
-  if (in_stride_samples > (1LL << 40) || out_stride_blocks > (1LL << 30)) return fail("row stride too large");
-  if ((((uintptr_t)dIQ | (uintptr_t)dI | (uintptr_t)dQ) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
-  const size_t in_bytes = ((size_t)(t->n_src - 1) * in_stride_samples + n_in) * 4;
-  const size_t out_bytes = ((size_t)(t->n - 1) * out_stride_blocks + n_blocks) * 128 * 2;
-  if (overlap((uintptr_t)dI, out_bytes, (uintptr_t)dIQ, in_bytes) || overlap((uintptr_t)dQ, out_bytes, (uintptr_t)dIQ, in_bytes))
-    return fail("output span overlaps the input span");
-  if (overlap((uintptr_t)dI, out_bytes, (uintptr_t)dQ, out_bytes)) return fail("I and Q output spans overlap");
+  if (check_io(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, n_blocks) != 0) return -1;
   hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(t->device));
   if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
   if (push(t, stream) != 0) return -1;
-  TunerArgs a;
-  a.in = (const int32_t *)dIQ; a.hist_rd = t->d_hist[t->cur]; a.hist_wr = t->d_hist[t->cur ^ 1];
-  a.chan = t->d_chan; a.order = t->d_order; a.taps = t->d_taps; a.out_i = dI; a.out_q = dQ;
-  a.pos = t->pos; a.in_stride = in_stride_samples; a.out_stride = (int64_t)out_stride_blocks * 128;
-  a.n_channels = t->n; a.n_sources = t->n_src; a.n_blocks = n_blocks; a.decimation = t->D;
-  a.n_phase_rows = t->n_rows; a.n_phase_pairs = t->n_pairs;
-  a.shift = 15 - t->g; a.round = a.shift ? 1 << (a.shift - 1) : 0;
   HIPCHK(hipEventRecord(t->ev0, stream));
-  if (asdr_launch_tuner(&a, stream) != 0) return fail("tuner kernel launch failed");
+  if (run_stage1(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream) != 0) return -1;
   HIPCHK(hipEventRecord(t->ev1, stream));
   t->ev_valid = true; t->last_stream = stream;
-  t->pos += n_in;
-  t->cur ^= 1;
+  t->out_pos += (long long)n_blocks * 128;   // a pass-through stage 2 writes every u sample at once
+  t->carry_stale = true;                      // and keeps no history
   return 0;
 }
 
 int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q, int n_blocks) {
   if (!t) return fail("null tuner bank");
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (!pass_through(t)) return fail("stage 2 of this bank resamples: use asdr_tuner_update_rate_device / asdr_tuner_update_rate");
   if (!IQ || !I || !Q) return fail("null host pointer");
   if (n_blocks <= 0) return 0;
   if (n_blocks > 65535) return fail("too many blocks in one call");
@@ -300,6 +452,139 @@ int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q
   HIPCHK(hipMemcpyAsync(Q, dQ, out_bytes, hipMemcpyDeviceToHost, t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));
   return 0;
+}
+
+long long asdr_tuner_rate(const asdr_tuner_t *t) { return t ? t->fs_in : 0; }
+
+int asdr_tuner_ratio(const asdr_tuner_t *t, int *up, int *down) {
+  if (!t) return fail("null tuner bank");
+  if (up) *up = t->up;
+  if (down) *down = t->down;
+  return 0;
+}
+
+long long asdr_tuner_output_position(const asdr_tuner_t *t) { return t ? t->out_pos : -1; }
+
+int asdr_tuner_set_resampler(asdr_tuner_t *t, const int16_t *h2, int n_taps, int gain_shift) {
+  if (!t) return fail("null tuner bank");
+  const std::string e = resampler_error(t->up, h2, n_taps, gain_shift);
+  if (!e.empty()) return fail(e);
+  t->h2.assign(h2, h2 + n_taps);
+  t->g2 = gain_shift;
+  t->k2 = n_taps / t->up;
+  t->rs_dirty = true;
+  return 0;
+}
+
+int asdr_tuner_get_resampler(const asdr_tuner_t *t, int16_t *h2, int cap, int *gain_shift) {
+  if (!t) return fail("null tuner bank");
+  const int L = (int)t->h2.size();
+  if (h2) for (int k = 0; k < L && k < cap; k++) h2[k] = t->h2[k];
+  if (gain_shift) *gain_shift = t->g2;
+  return L;
+}
+
+int asdr_tuner_out_blocks(const asdr_tuner_t *t, int n_frames) {
+  if (!t) return fail("null tuner bank");
+  if (n_frames < 0 || n_frames > 65535) return fail("n_frames must be in 0..65535");
+  return (int)blocks_after(t, n_frames);
+}
+
+int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int n_frames, int16_t *dI,
+                                  int16_t *dQ, int out_capacity_blocks, long out_stride_blocks, void *stream_) {
+  if (!t) return fail("null tuner bank");
+  if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (!dIQ || !dI || !dQ) return fail("null device pointer");
+  if (n_frames < 0 || n_frames > 65535) return fail("n_frames must be in 0..65535");
+  if (n_frames == 0) return 0;
+  const long long nb = blocks_after(t, n_frames);
+  if (nb > out_capacity_blocks)
+    return fail("output capacity of " + std::to_string(out_capacity_blocks) + " blocks: this call writes " + std::to_string(nb));
+  if (out_stride_blocks < out_capacity_blocks) return fail("output row stride shorter than the output capacity");
+  if (check_io(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, out_capacity_blocks) != 0) return -1;
+  if (pass_through(t))
+    return asdr_tuner_update_device(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, stream_) == 0 ? n_frames : -1;
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(t->device));
+  const size_t row = (size_t)n_frames * 128, mid_bytes = 2 * (size_t)t->n * row * sizeof(int16_t);
+  if (mid_bytes > t->mid_cap || !t->d_carry[0]) {   // grow the intermediate / allocate the carry: nothing of ours may be in flight
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (mid_bytes > t->mid_cap) {
+      if (t->d_mid) HIPCHK(hipFree(t->d_mid));
+      t->d_mid = nullptr; t->mid_cap = 0;
+      HIPCHK(hipMalloc(&t->d_mid, mid_bytes));
+      t->mid_cap = mid_bytes;
+    }
+    if (!t->d_carry[0]) {
+      const size_t cb = (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t);
+      HIPCHK(hipMalloc(&t->d_carry[0], cb));
+      HIPCHK(hipMalloc(&t->d_carry[1], cb));
+      HIPCHK(hipMemset(t->d_carry[t->ccur], 0, cb));
+      HIPCHK(hipDeviceSynchronize());
+      t->carry_stale = false;
+    }
+  }
+  if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
+  if (push(t, stream) != 0 || push_resampler(t, stream) != 0) return -1;
+  HIPCHK(hipEventRecord(t->ev0, stream));
+  if (t->carry_stale) {   // the pass-through calls before this one kept no stage-2 history (asdr_tuner.h)
+    HIPCHK(hipMemsetAsync(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t), stream));
+    t->carry_stale = false;
+  }
+  const long long n_u = t->pos / t->D;
+  int16_t *mid_i = t->d_mid, *mid_q = t->d_mid + (size_t)t->n * row;
+  if (run_stage1(t, dIQ, in_stride_samples, mid_i, mid_q, n_frames, n_frames, stream) != 0) return -1;
+  ResampleArgs r;
+  r.mid_i = mid_i; r.mid_q = mid_q;
+  r.carry_rd = t->d_carry[t->ccur]; r.carry_wr = t->d_carry[t->ccur ^ 1];
+  r.taps = t->d_rs_taps; r.lane_qr = t->d_lane_qr; r.out_i = dI; r.out_q = dQ;
+  r.out_stride = (int64_t)out_stride_blocks * 128;
+  r.n_channels = t->n; r.n_frames = n_frames; r.n_out = (int)(nb * 128);
+  r.up = t->up; r.down = t->down; r.k = t->k2; r.kp = t->kp;
+  long long b0;
+  split(t->out_pos, t->up, t->down, b0, r.r0);
+  r.q0 = (int)(b0 - (n_u - ASDR_TUNER_CARRY));
+  r.tile_q = ASDR_TUNER_RS_OUT * t->down / t->up; r.tile_r = ASDR_TUNER_RS_OUT * t->down % t->up;
+  r.shift = 15 - t->g2; r.round = r.shift ? 1 << (r.shift - 1) : 0;
+  if (r.q0 - (r.k - 1) < 0) return fail("internal: stage-2 window starts before the carry");
+  if (asdr_launch_tuner_resample(&r, stream) != 0) return fail("tuner resampler kernel launch failed");
+  HIPCHK(hipEventRecord(t->ev1, stream));
+  t->ev_valid = true; t->last_stream = stream;
+  t->ccur ^= 1;
+  t->out_pos += nb * 128;
+  return (int)nb;
+}
+
+int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks) {
+  if (!t) return fail("null tuner bank");
+  if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (!IQ || !I || !Q) return fail("null host pointer");
+  if (n_frames < 0 || n_frames > 65535) return fail("n_frames must be in 0..65535");
+  if (n_frames == 0) return 0;
+  const long long nb = blocks_after(t, n_frames);
+  if (nb > out_capacity_blocks)
+    return fail("output capacity of " + std::to_string(out_capacity_blocks) + " blocks: this call writes " + std::to_string(nb));
+  const size_t n_in = (size_t)n_frames * 128 * t->D, in_bytes = (size_t)t->n_src * n_in * 4;
+  const size_t out_bytes = (size_t)t->n * nb * 128 * 2, in_pad = (in_bytes + 255) & ~(size_t)255;
+  HIPCHK(hipSetDevice(t->device));
+  if (in_pad + 2 * out_bytes > t->io_cap) {
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (t->d_io) HIPCHK(hipFree(t->d_io));
+    t->d_io = nullptr; t->io_cap = 0;
+    HIPCHK(hipMalloc(&t->d_io, in_pad + 2 * out_bytes));
+    t->io_cap = in_pad + 2 * out_bytes;
+  }
+  char *base = (char *)t->d_io;
+  int16_t *dI = (int16_t *)(base + in_pad), *dQ = (int16_t *)(base + in_pad + out_bytes);
+  HIPCHK(hipMemcpyAsync(base, IQ, in_bytes, hipMemcpyHostToDevice, t->stream));
+  const int got = asdr_tuner_update_rate_device(t, (const int16_t *)base, (long)n_in, n_frames, dI, dQ, (int)nb, (long)nb, t->stream);
+  if (got < 0) return -1;
+  if (out_bytes) {
+    HIPCHK(hipMemcpyAsync(I, dI, out_bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipMemcpyAsync(Q, dQ, out_bytes, hipMemcpyDeviceToHost, t->stream));
+  }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return got;
 }
 
 int asdr_tuner_synchronize(asdr_tuner_t *t) {

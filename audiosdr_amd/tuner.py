@@ -11,7 +11,12 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_n_sources", "asdr_tuner_decimation", "asdr_tuner_set_source", "asdr_tuner_set_frequency",
                  "asdr_tuner_set_frequency_word", "asdr_tuner_set_phase", "asdr_tuner_set_filter", "asdr_tuner_get_filter",
                  "asdr_tuner_read_state", "asdr_tuner_update_device", "asdr_tuner_update", "asdr_tuner_synchronize",
-                 "asdr_tuner_last_kernel_ms"]
+                 "asdr_tuner_last_kernel_ms", "asdr_tuner_create_rate", "asdr_tuner_rate", "asdr_tuner_ratio",
+                 "asdr_tuner_output_position", "asdr_tuner_set_resampler", "asdr_tuner_get_resampler", "asdr_tuner_out_blocks",
+                 "asdr_tuner_update_rate_device", "asdr_tuner_update_rate"]
+
+MAX_UP = 2048
+MID_RANGE = (44100, 176400)
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
@@ -40,6 +45,16 @@ def _lib():
     L.asdr_tuner_update_device.argtypes = [vp, vp, lg, vp, vp, i, lg, vp]; L.asdr_tuner_update_device.restype = i
     L.asdr_tuner_update.argtypes = [vp, i16p, i16p, i16p, i]; L.asdr_tuner_update.restype = i
     L.asdr_tuner_last_kernel_ms.argtypes = [vp]; L.asdr_tuner_last_kernel_ms.restype = C.c_float
+    ll, ip = C.c_longlong, C.POINTER(C.c_int)
+    L.asdr_tuner_create_rate.argtypes = [i, i, ll, i, i]; L.asdr_tuner_create_rate.restype = vp
+    L.asdr_tuner_rate.argtypes = [vp]; L.asdr_tuner_rate.restype = ll
+    L.asdr_tuner_ratio.argtypes = [vp, ip, ip]; L.asdr_tuner_ratio.restype = i
+    L.asdr_tuner_output_position.argtypes = [vp]; L.asdr_tuner_output_position.restype = ll
+    L.asdr_tuner_set_resampler.argtypes = [vp, i16p, i, i]; L.asdr_tuner_set_resampler.restype = i
+    L.asdr_tuner_get_resampler.argtypes = [vp, i16p, i, ip]; L.asdr_tuner_get_resampler.restype = i
+    L.asdr_tuner_out_blocks.argtypes = [vp, i]; L.asdr_tuner_out_blocks.restype = i
+    L.asdr_tuner_update_rate_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_rate_device.restype = i
+    L.asdr_tuner_update_rate.argtypes = [vp, i16p, i, i16p, i16p, i]; L.asdr_tuner_update_rate.restype = i
     _typed = True
     return L
 
@@ -48,16 +63,42 @@ def _p16(a):
     return a.ctypes.data_as(C.POINTER(C.c_int16))
 
 
-class TunerBank:
-    """n_channels digital tuners over n_sources shared CS16 rows at decimation D (include/asdr_tuner.h).  device = NO_DEVICE (-1)
-    gives the control plane only."""
+def rate_ratio(fs_in, decimation):
+    """(U, M) = 44100 / (fs_in / D) in lowest terms if (fs_in, D) makes a valid rate bank (include/asdr_tuner.h), else None."""
+    import math
+    fs_in, D = int(fs_in), int(decimation)
+    if fs_in <= 0 or not 1 <= D <= 64 or fs_in % D:
+        return None
+    mid = fs_in // D
+    if not MID_RANGE[0] <= mid <= MID_RANGE[1]:
+        return None
+    g = math.gcd(44100, mid)
+    return (44100 // g, mid // g) if 44100 // g <= MAX_UP else None
 
-    def __init__(self, n_channels, n_sources=1, decimation=1, device=0):
+
+def suggest_decimation(fs_in):
+    """The largest D <= 64 that makes a valid rate bank for fs_in (the least stage-2 work), or None."""
+    for D in range(64, 0, -1):
+        if rate_ratio(fs_in, D) is not None:
+            return D
+    return None
+
+
+class TunerBank:
+    """n_channels digital tuners over n_sources shared CS16 rows at decimation D (include/asdr_tuner.h).  fs_in (Hz) makes a rate
+    bank: any integer input rate with fs_in / D in [44100, 176400], resampled to 44.1 kHz after the decimator.  device = NO_DEVICE
+    (-1) gives the control plane only."""
+
+    def __init__(self, n_channels, n_sources=1, decimation=1, fs_in=None, device=0):
         self._L = _lib()
-        self._h = self._L.asdr_tuner_create(int(n_channels), int(n_sources), int(decimation), int(device))
+        if fs_in is None:
+            self._h = self._L.asdr_tuner_create(int(n_channels), int(n_sources), int(decimation), int(device))
+        else:
+            self._h = self._L.asdr_tuner_create_rate(int(n_channels), int(n_sources), int(fs_in), int(decimation), int(device))
         if not self._h:
-            raise AsdrError("asdr_tuner_create failed: %s" % self._L.asdr_last_error().decode())
+            raise AsdrError("asdr_tuner_create%s failed: %s" % ("" if fs_in is None else "_rate", self._L.asdr_last_error().decode()))
         self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(decimation)
+        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -126,6 +167,51 @@ class TunerBank:
         ins = in_stride_samples or n_blocks * BLOCK * self.decimation
         self._chk(self._L.asdr_tuner_update_device(self._h, C.c_void_p(dIQ), int(ins), C.c_void_p(dI), C.c_void_p(dQ), int(n_blocks),
                                                    int(out_stride_blocks or n_blocks), C.c_void_p(stream)))
+
+    def ratio(self):
+        """(U, M): stage 2 resamples Fs_in / D by U / M to 44.1 kHz."""
+        u, m = C.c_int(), C.c_int()
+        self._chk(self._L.asdr_tuner_ratio(self._h, C.byref(u), C.byref(m)))
+        return int(u.value), int(m.value)
+
+    def output_position(self):
+        return int(self._L.asdr_tuner_output_position(self._h))
+
+    def set_resampler(self, h2, gain_shift=0):
+        h2 = np.ascontiguousarray(h2, dtype=np.int16)
+        self._chk(self._L.asdr_tuner_set_resampler(self._h, _p16(h2), int(h2.size), int(gain_shift)))
+
+    def get_resampler(self):
+        """(h2 int16 [U K], gain_shift)."""
+        n = self._chk(self._L.asdr_tuner_get_resampler(self._h, None, 0, None))
+        h, g = np.zeros(n, dtype=np.int16), C.c_int()
+        self._chk(self._L.asdr_tuner_get_resampler(self._h, _p16(h), n, C.byref(g)))
+        return h, int(g.value)
+
+    def out_blocks(self, n_frames):
+        """Output blocks the next call of n_frames frames (128 D input samples per source each) will write."""
+        return self._chk(self._L.asdr_tuner_out_blocks(self._h, int(n_frames)))
+
+    def update_rate(self, iq):
+        """iq: int16 [n_sources][n_frames * 128 * D][2] on the host.  Returns (I, Q), int16 [n_channels][n][128] for the n blocks
+        this call writes (n may be 0)."""
+        iq = np.ascontiguousarray(iq, dtype=np.int16)
+        per = BLOCK * self.decimation
+        assert iq.shape[0] == self.n_sources and iq.shape[-1] == 2 and iq.shape[1] % per == 0, iq.shape
+        nf = iq.shape[1] // per
+        nb = self.out_blocks(nf)
+        I = np.empty((self.n_channels, max(nb, 1), BLOCK), dtype=np.int16)
+        Q = np.empty_like(I)
+        got = self._chk(self._L.asdr_tuner_update_rate(self._h, _p16(iq), nf, _p16(I), _p16(Q), nb))
+        assert got == nb, (got, nb)
+        return I[:, :nb], Q[:, :nb]
+
+    def update_rate_device(self, dIQ, dI, dQ, n_frames, out_capacity_blocks, in_stride_samples=None, out_stride_blocks=None, stream=0):
+        """Device pointers (ints); asynchronous on `stream`.  Returns the number of blocks written to each row."""
+        ins = in_stride_samples or n_frames * BLOCK * self.decimation
+        return self._chk(self._L.asdr_tuner_update_rate_device(
+            self._h, C.c_void_p(dIQ), int(ins), int(n_frames), C.c_void_p(dI), C.c_void_p(dQ), int(out_capacity_blocks),
+            int(out_stride_blocks or out_capacity_blocks), C.c_void_p(stream)))
 
     def synchronize(self):
         self._chk(self._L.asdr_tuner_synchronize(self._h))

@@ -19,6 +19,29 @@
  *             when the value does not change.  A new filter applies to outputs from P on; the sources' history is kept.
  *   creation  P = 0, every anchor (0, 0), fw 0, src 0, source history zeros.  Default filter: D = 1 -> h = {16384}, g = 1 (exact
  *             pass-through of z); D >= 2 -> a Kaiser low-pass of 12 D + 1 taps, g = 0 (DESIGN.md 3.8 gives its response).
+ *
+ * Rate banks (asdr_tuner_create_rate): wideband input at any integer rate Fs_in (Hz) that a decimation D in [1, 64] brings to
+ * Fs_mid = Fs_in / D (Fs_in % D == 0) in [44100, 176400]; U / M = 44100 / Fs_mid in lowest terms, U <= 2048.  A plain bank is the
+ * rate bank with Fs_in = D * 44100 (U = M = 1): the same defaults and the same output.
+ *   stage 1   the arithmetic above, with Fs_in for the frequency word; it gives the channel's intermediate sequence u[i] (I and Q,
+ *             int16) at Fs_mid.  N_u = P / D = u samples produced so far.
+ *   stage 2   a polyphase rational resampler: prototype h2[0 .. U K - 1] int16, K taps per phase in [1, 64], gain shift g2 in
+ *             [0, 15], every phase phi with sum_k |h2[k U + phi]| <= 65535.  Output j: b_j = floor(j M / U), phi_j = j M - b_j U,
+ *             y[j] = sat16((sum_{k<K} h2[k U + phi_j] u[b_j - k] + r2) >> s2), s2 = 15 - g2, r2 = s2 ? 1 << (s2 - 1) : 0,
+ *             u[i] = 0 for i < 0; I and Q separately.
+ *   timing    a call consumes whole frames: 128 D input samples per source (128 new u samples).  Output block J (samples 128 J ..
+ *             128 J + 127) is written by the first call after which b_{128 J + 127} <= N_u - 1, blocks in order: 0 .. n_frames + 1
+ *             blocks per call, a count that depends on the positions only (asdr_tuner_out_blocks).
+ *   state     a retune does not touch stage 2 (stage 1 flushes its own history as above); a new stage-2 filter applies to the
+ *             outputs written from the next call on; reset zeroes P, the output position and the stage-2 history.  A stage 2
+ *             with U = M = 1, K = 1 and h2 = {1 << s2} is a pass-through (the output is u) and keeps no history: the first call
+ *             that runs another stage 2 after pass-through calls sees u[i] = 0 for every i before that call.
+ *   defaults  Kaiser (beta 9) windowed sincs, 0 - 11.2 kHz passband, rejecting what would fold into 0 - 12 kHz at 44.1 kHz.
+ *             Stage 1: Fs_mid = 44100 -> the plain default above; D = 1 -> {16384}, g = 1; otherwise stop band from
+ *             Fs_mid - 12 kHz, cut-off midway between 11.2 kHz and that edge, L1 = 2 ceil(6 D Fs_mid 20900 / (44100 (Fs_mid -
+ *             23200))) + 1 taps, g = 0.  Stage 2: U = M = 1 -> {16384}, g2 = 1; otherwise a prototype at U Fs_mid with cut-off
+ *             21.65 kHz, K = 2 ceil(6 Fs_mid / 44100), each phase rounded to Q15 on its own and its largest tap corrected so the
+ *             phase sums to exactly 32768, g2 = 0 (DESIGN.md 3.8 gives the responses).
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -35,6 +58,8 @@ extern "C" {
 #define ASDR_TUNER_MAX_TAPS 1024
 #define ASDR_TUNER_MAX_GAIN_SHIFT 15
 #define ASDR_TUNER_HISTORY 1023 /* input samples per source kept across calls (L - 1 at most) */
+#define ASDR_TUNER_MAX_UP 2048
+#define ASDR_TUNER_MAX_RESAMPLER_TAPS 64 /* K, taps per phase */
 
 typedef struct asdr_tuner_bank asdr_tuner_t;
 
@@ -57,7 +82,7 @@ int asdr_tuner_decimation(const asdr_tuner_t *t);
 
 /* control plane (all take effect at the current P) */
 int asdr_tuner_set_source(asdr_tuner_t *t, int ch, int source);
-/* hz in [-Fs_in/2, Fs_in/2], Fs_in = D * 44100: fw = (uint32)(int64)llround(hz * 2^32 / Fs_in).  To receive RF f of a capture
+/* hz in [-Fs_in/2, Fs_in/2], Fs_in = the bank's rate (D * 44100 for a plain bank): fw = (uint32)(int64)llround(hz * 2^32 / Fs_in).  To receive RF f of a capture
  * centred at fc with the chain behind it: hz = f - fc - asdr_getTuningOffset(). */
 int asdr_tuner_set_frequency(asdr_tuner_t *t, int ch, double hz);
 int asdr_tuner_set_frequency_word(asdr_tuner_t *t, int ch, uint32_t fw);
@@ -77,8 +102,31 @@ int asdr_tuner_read_state(const asdr_tuner_t *t, asdr_tuner_state_t *dst /* [n_c
 int asdr_tuner_update_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
                              long out_stride_blocks, void *stream);
 int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q, int n_blocks);
+
+/* Rate banks.  NULL (asdr_last_error) for each violated constraint above; ASDR_NO_DEVICE gives a control-plane-only bank. */
+asdr_tuner_t *asdr_tuner_create_rate(int n_channels, int n_sources, long long fs_in_hz, int decimation, int device);
+long long asdr_tuner_rate(const asdr_tuner_t *t);                /* Fs_in (D * 44100 for a plain bank) */
+int asdr_tuner_ratio(const asdr_tuner_t *t, int *up, int *down);  /* U and M (either pointer may be NULL) */
+long long asdr_tuner_output_position(const asdr_tuner_t *t);      /* output samples written since creation / reset */
+/* Rejected (old resampler kept): n_taps % U != 0, K = n_taps / U or g2 out of range, a phase with sum |h2| > 65535. */
+int asdr_tuner_set_resampler(asdr_tuner_t *t, const int16_t *h2, int n_taps, int gain_shift);
+/* Copies min(U K, cap) taps to h2 (if not NULL) and g2 to *gain_shift (if not NULL); returns U K. */
+int asdr_tuner_get_resampler(const asdr_tuner_t *t, int16_t *h2, int cap, int *gain_shift);
+/* Blocks the next call of n_frames frames will write (host arithmetic only; exact for 64-bit positions). */
+int asdr_tuner_out_blocks(const asdr_tuner_t *t, int n_frames);
+/* The rate hot path: n_frames frames of dIQ (as asdr_tuner_update_device, n_frames * 128 * D samples per source) in, the blocks
+ * the call writes out: blocks 0 .. n - 1 of each [n_channels][out_stride_blocks][128] row of dI, dQ; returns n (>= 0) or -1.
+ * Fails, with no work done and the state unchanged, when n > out_capacity_blocks or out_stride_blocks < out_capacity_blocks.
+ *  _update_rate_device : asynchronous on `stream`, with the stream rule of asdr_tuner_update_device (the wait is on the previous
+ *                        call's last kernel).  It also takes plain banks, where it gives asdr_tuner_update_device's output.
+ *  _update_rate        : host pointers, contiguous rows (n blocks apart, in_stride = n_frames * 128 * D); synchronous.
+ * asdr_tuner_update_device / asdr_tuner_update need a pass-through stage 2 and fail otherwise. */
+int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int n_frames, int16_t *dI,
+                                  int16_t *dQ, int out_capacity_blocks, long out_stride_blocks, void *stream);
+int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks);
+
 int asdr_tuner_synchronize(asdr_tuner_t *t);
-float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its two kernels); -1 if none */
+float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */
 
 #ifdef __cplusplus
 }

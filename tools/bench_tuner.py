@@ -5,13 +5,18 @@
   T2        one SDR: 1 source, D = 48, 4,096 channels, default filter, 64 blocks per call
   T3        wide bank: 16 sources, D = 48, 65,536 channels (4,096 per source), default filter, 16 blocks per call
   T3+chain  T3 followed by asdr_update_device (USB) on the same stream
+  T4        rate bank: 16 sources at 2.4 MS/s, D = 50 (stage 2: 147 / 160), 65,536 channels, default filters, 16 frames per call
+  T4+chain  T4 followed by asdr_update_device (USB) on the same stream
+  S48       skimmer on sound-card I/Q: 1 source at 48 kHz, D = 1 (147 / 160), 4,096 channels, default filters, 64 frames per call
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
 source, int16 I and Q out, the history rows); their share of the VALU issue bound and of HBM, and which of the two bounds the
-call.  The first call of each config is checked against tests/tuner_ref.py on a few channels.  Inputs are seeded.
+call.  Rate banks (T4, S48) add stage 2's 2 K multiply-adds per output and the intermediate rows' traffic; x real time is input
+time per call over call time.  The first call of each config is checked against tests/tuner_ref.py / tuner_rate_ref.py on a few
+channels.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48]
 """
 import json
 import os
@@ -25,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import audiosdr_amd as A  # noqa: E402
+import tuner_rate_ref as RR  # noqa: E402
 import tuner_ref as R  # noqa: E402
 
 VALU_LANE_OPS = 256 * 4 * 64 / 2 * 2.4e9     # CUs x SIMDs x wave64 lanes per 2-cycle issue x max clock: 7.86e13 lane-ops/s
@@ -35,12 +41,18 @@ CONFIGS = {
     "T2": dict(n_src=1, D=48, n_ch=4096, L=None, nb=64),
     "T3": dict(n_src=16, D=48, n_ch=65536, L=None, nb=16),
     "T3+chain": dict(n_src=16, D=48, n_ch=65536, L=None, nb=16, chain=True),
+    "T4": dict(n_src=16, D=50, n_ch=65536, L=None, nb=16, fs_in=2400000),
+    "T4+chain": dict(n_src=16, D=50, n_ch=65536, L=None, nb=16, chain=True, fs_in=2400000),
+    "S48": dict(n_src=1, D=1, n_ch=4096, L=None, nb=64, fs_in=48000),
 }
 
 
-def run(name, n_src, D, n_ch, L, nb, chain=False):
+def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None):
+    """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given)."""
     rng = np.random.default_rng(sum(map(ord, name)))
-    bank = A.TunerBank(n_ch, n_src, D)
+    bank = A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
+    rate = fs_in is not None
+    cap = nb + 1 if rate else nb
     if L is not None:
         h = np.round(np.hamming(L) * np.sinc((np.arange(L) - (L - 1) / 2) * 0.5) * 16384 / 2).astype(np.int16)
         bank.set_filter(h, 0)
@@ -54,7 +66,7 @@ def run(name, n_src, D, n_ch, L, nb, chain=False):
     calls = 4                                              # distinct seeded inputs, cycled
     iq = rng.integers(-12000, 12000, size=(calls, n_src, N, 2), endpoint=True).astype(np.int16)
     dIQ = torch.from_numpy(iq).cuda()
-    dI = torch.empty((n_ch, nb, 128), dtype=torch.int16, device="cuda")
+    dI = torch.empty((n_ch, cap, 128), dtype=torch.int16, device="cuda")
     dQ = torch.empty_like(dI)
     stream = torch.cuda.current_stream()
     sp = stream.cuda_stream
@@ -64,20 +76,34 @@ def run(name, n_src, D, n_ch, L, nb, chain=False):
         sdr.setDemodMode(A.USBmode)
         dOut = torch.empty_like(dI)
 
+    out_blocks = []
+
     def call(k):
-        bank.update_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, stream=sp)
-        if chain:
+        if rate:
+            n = bank.update_rate_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, cap, stream=sp)
+        else:
+            bank.update_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, stream=sp)
+            n = nb
+        out_blocks.append(n)
+        if chain and rate and n > 0:
+            sdr.update_device_strided(dI.data_ptr(), dQ.data_ptr(), dOut.data_ptr(), n, cap, cap, stream=sp)
+        elif chain:
             sdr.update_device(dI.data_ptr(), dQ.data_ptr(), dOut.data_ptr(), nb, stream=sp)
 
     # parity of the first call on 8 channels
     check = sorted(set([0, 1, n_ch - 1] + [int(c) for c in rng.integers(0, n_ch, size=5)]))
-    ref = R.TunerRef(len(check), n_src, D, h, g)
+    if rate:
+        h2, g2 = bank.get_resampler()
+        ref = RR.TunerRateRef(len(check), n_src, D, fs_in, h, g, h2, g2)
+    else:
+        ref = R.TunerRef(len(check), n_src, D, h, g)
     for i, c in enumerate(check):
         ref.src[i], ref.fw[i] = int(srcs[c]), int(fws[c])
     call(0)
     torch.cuda.synchronize()
     wI, wQ = ref.update(iq[0])
-    parity = bool(np.array_equal(dI.cpu().numpy()[check], wI) and np.array_equal(dQ.cpu().numpy()[check], wQ))
+    n0 = out_blocks[0]
+    parity = bool(np.array_equal(dI.cpu().numpy()[check, :n0], wI) and np.array_equal(dQ.cpu().numpy()[check, :n0], wQ))
     # warm, then size the timed window to >= 1 s
     for k in range(1, 6):
         call(k)
@@ -89,21 +115,32 @@ def run(name, n_src, D, n_ch, L, nb, chain=False):
     est = max((time.perf_counter() - t0) / 3, 1e-5)
     reps = max(10, int(1.2 / est) + 1)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    del out_blocks[:]
     e0.record(stream)
     for k in range(reps):
         call(k)
     e1.record(stream)
     e1.synchronize()
     ms = e0.elapsed_time(e1) / reps
-    n_out = n_ch * nb * 128
-    macs = n_out * (4 * D + 2 * L)
-    nbytes = n_src * N * 4 + n_out * 4 + 2 * n_src * 1024 * 4
+    n_mid = n_ch * nb * 128                                   # stage-1 outputs per call
+    n_out = n_ch * sum(out_blocks) * 128 / reps               # outputs per call (mean)
+    macs = n_mid * (4 * D + 2 * L)
+    nbytes = n_src * N * 4 + n_mid * 4 + 2 * n_src * 1024 * 4
+    K2 = 0
+    if rate:
+        U2 = bank.ratio()[0]
+        K2 = bank.get_resampler()[0].size // U2
+        if not (U2 == 1 and K2 == 1):
+            macs += n_out * 2 * K2
+            nbytes += n_mid * 4 + n_out * 4 + 2 * n_ch * 576 * 4     # intermediate read back, outputs, carry
     t_valu, t_hbm = macs / VALU_LANE_OPS, nbytes / HBM_BPS
     bound = "valu" if t_valu >= t_hbm else "hbm"
     out = {"config": name, "sources": n_src, "decimation": D, "channels": n_ch, "taps": int(L), "blocks_per_call": nb,
            "chain": "USB" if chain else None, "timed_calls": reps, "timed_s": round(ms * reps / 1e3, 3),
            "ms_per_call": round(ms, 4), "output_samples_per_s": round(n_out / (ms * 1e-3), 1),
-           "realtime_factor": round(nb * 128 / 44100.0 / (ms * 1e-3), 2),
+           "realtime_factor": round(N / float(fs_in or 44100 * D) / (ms * 1e-3), 2),
+           "fs_in": int(fs_in or 44100 * D), "ratio": list(bank.ratio()), "resampler_taps_per_phase": int(K2) if rate else None,
+           "output_blocks_per_call": round(sum(out_blocks) / reps, 3),
            "model": {"int_mult_adds": int(macs), "bytes": int(nbytes), "valu_bound_ms": round(t_valu * 1e3, 4),
                      "hbm_bound_ms": round(t_hbm * 1e3, 4), "bound": bound,
                      "share_of_bound": round(max(t_valu, t_hbm) / (ms * 1e-3), 4),
