@@ -1,4 +1,4 @@
-// STAND-IN for the Teensy core's Arduino.h (tools/ref_shim/README.md): what AudioSDR.h / .cpp use of it.
+// STAND-IN for the Teensy core's Arduino.h (oracle/ref_shim/README.md): what AudioSDR.h / .cpp use of it.
 #pragma once
 #include <math.h>
 #include <stdlib.h>

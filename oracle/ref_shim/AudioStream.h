@@ -1,4 +1,4 @@
-// STAND-IN for the Teensy audio library's AudioStream.h (tools/ref_shim/README.md): a queue-backed AudioStream of exactly the members
+// STAND-IN for the Teensy audio library's AudioStream.h (oracle/ref_shim/README.md): a queue-backed AudioStream of exactly the members
 // AudioSDR uses (AudioSDR.cpp:46-56, 164-167).
 #pragma once
 #include <stdint.h>

@@ -1,0 +1,2 @@
+// STAND-IN (empty): oracle/ref_shim/README.md
+#pragma once

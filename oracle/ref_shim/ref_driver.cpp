@@ -1,4 +1,4 @@
-// Driver of the stand-in build (tools/ref_shim/README.md): ONE AudioSDR instance of the reference's own source (static storage; one instance per
+// Driver of the stand-in build (oracle/ref_shim/README.md): ONE AudioSDR instance of the reference's own source (static storage; one instance per
 // process: the reference's function-statics), configured by a script of setter calls, fed blocks of I/Q, its output blocks and getters
 // written out.   ref_driver <script.txt> <iq.bin int16 [blocks][2][128]> <n_blocks> <out.bin int16 [blocks][128]>  -> getters on stdout
 #include <stdio.h>

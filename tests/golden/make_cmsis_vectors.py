@@ -1,4 +1,4 @@
-"""Makes tests/golden/cmsis_biquad_vectors.npz and cmsis_cfft128_vectors.npz: outputs of the REFERENCE'S OWN BINARIES of CMSIS-DSP V1.4.5
+"""Makes tests/golden/cmsis_biquad_vectors.npz, cmsis_cfft128_vectors.npz and cmsis_mag_squared_vectors.npz: outputs of the REFERENCE'S OWN BINARIES of CMSIS-DSP V1.4.5
 `arm_cfft_f32` (128 points: arm_cfft_f32.o, arm_cfft_radix8_f32.o, arm_bitreversal2.o and their tables, linked by tests/thumb_emu.py) and
 `arm_biquad_cascade_df1_f32` (member arm_biquad_cascade_df1_f32.o of the reference's
 `ARM_MATH UPDATE/TeensyduinoArmMathUpdate/libarm_cortexM4lf_math.a`), executed instruction by instruction by tests/thumb_emu.py
@@ -43,6 +43,20 @@ def main():
     out["names"] = np.array(names)
     np.savez_compressed(C.GOLDEN_CFFT, **out)
     print("wrote %s: %d cases" % (C.GOLDEN_CFFT, len(names)))
+    write_mag_squared()
+
+
+def write_mag_squared():
+    """arm_cmplx_mag_squared_f32 (member arm_cmplx_mag_squared_f32.o): the object executed on the emulator."""
+    code, _ = T.load_function(C.ARCHIVE, "arm_cmplx_mag_squared_f32.o", "arm_cmplx_mag_squared_f32")
+    out, names = {"object_sha256": np.array(hashlib.sha256(code).hexdigest())}, []
+    for i, (name, x) in enumerate(C.mag_squared_cases()):
+        names.append(name)
+        out["x_%d" % i] = np.asarray(x, np.float32)
+        out["y_bits_%d" % i] = C.run_mag_squared(code, x).view(np.uint32)
+    out["names"] = np.array(names)
+    np.savez_compressed(C.GOLDEN_MAG, **out)
+    print("wrote %s: %d cases" % (C.GOLDEN_MAG, len(names)))
 
 
 if __name__ == "__main__":

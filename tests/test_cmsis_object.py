@@ -24,6 +24,7 @@ from tests import thumb_emu as T
 ARCHIVE = "/root/reference/ARM_MATH UPDATE/TeensyduinoArmMathUpdate/libarm_cortexM4lf_math.a"
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "cmsis_biquad_vectors.npz")
 GOLDEN_CFFT = os.path.join(os.path.dirname(__file__), "golden", "cmsis_cfft128_vectors.npz")
+GOLDEN_MAG = os.path.join(os.path.dirname(__file__), "golden", "cmsis_mag_squared_vectors.npz")
 needs_reference = pytest.mark.skipif(not os.path.exists(ARCHIVE), reason="the reference's CMSIS archive is not on this machine")
 
 CODE, INST, COEF, STATE, SRC, DST, SP = 0x100, 0x1000, 0x1100, 0x1400, 0x2000, 0x6000, 0xF000
@@ -175,6 +176,42 @@ def test_committed_vectors_are_what_the_object_computes():
     for i in (0, 7, len(g["names"]) - 3):
         y, st_after, _ = run_object(code, g["coefs_%d" % i], g["state_%d" % i], g["x_%d" % i])
         assert np.array_equal(_bits(y), g["y_bits_%d" % i]) and np.array_equal(_bits(st_after), g["state_after_bits_%d" % i])
+
+
+def mag_squared_cases():
+    """(name, x[2 n]): inputs of the committed arm_cmplx_mag_squared_f32 vectors -- block lengths that take the 4x-unrolled loop, the tail
+    loop and both, magnitudes whose squares overflow, go denormal or vanish, signed zeros, and the detector's own operand: FFT lines of
+    int16 / 32767 blocks."""
+    rng = np.random.default_rng(20261016)
+    out = []
+    for n in (128, 133, 7, 1):
+        out.append(("gauss_n%d" % n, rng.standard_normal(2 * n).astype(np.float32)))
+    for e in (-30, -20, -3, 3, 19, 25):
+        out.append(("scale_1e%d" % e, (rng.standard_normal(256) * 10.0 ** e).astype(np.float32)))
+    out.append(("zeros_signed", np.concatenate([np.zeros(128, np.float32), -np.zeros(128, np.float32)])))
+    for k in range(3):
+        blk = (rng.integers(-32768, 32768, 256).astype(np.float64) / 32767.0).astype(np.float32)
+        out.append(("fft_lines%d" % k, ao.fft128_interleaved(blk)))
+    return out
+
+
+def run_mag_squared(code, x):
+    """arm_cmplx_mag_squared_f32(pSrc, pDst, numSamples) on the emulator -> float32 [numSamples]."""
+    n = len(x) // 2
+    cpu = T.Cpu()
+    cpu.load_code(code, CODE)
+    cpu.write_f32(SRC, x)
+    cpu.call(CODE, [SRC, DST, n], SP)
+    return cpu.read_f32(DST, n)
+
+
+@needs_reference
+def test_committed_mag_squared_vectors_are_what_the_object_computes():
+    code, _ = T.load_function(ARCHIVE, "arm_cmplx_mag_squared_f32.o", "arm_cmplx_mag_squared_f32")
+    g = np.load(GOLDEN_MAG)
+    assert str(g["object_sha256"]) == __import__("hashlib").sha256(code).hexdigest()
+    for i, name in enumerate(str(n) for n in g["names"]):
+        assert np.array_equal(_bits(run_mag_squared(code, g["x_%d" % i])), g["y_bits_%d" % i]), name
 
 
 @needs_reference

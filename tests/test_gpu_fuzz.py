@@ -9,7 +9,6 @@ pytestmark = pytest.mark.gpu
 
 
 def _random_setter(rng):
-    k = rng.integers(0, 24)
     f = float
     table = [
         lambda: S("setDemodMode", int(rng.integers(0, 7))),
@@ -28,8 +27,10 @@ def _random_setter(rng):
         lambda: S("setALSfilterParams", int(rng.choice([8, 32, 55, 100, 128])), f(rng.choice([0.05, 0.5])), f(rng.choice([1.0, 3.0, 9.0]))),
         lambda: S("setInputGain", f(rng.choice([0.5, 1.0, 2.5]))), lambda: S("setIQgainBalance", f(rng.choice([0.95, 1.02]))),
         lambda: S("setOutputGain", f(rng.choice([0.25, 0.5, 1.0]))),
+        lambda: S("setAGCattackTime", f(rng.choice([0.5, 2.0, 10.0]))), lambda: S("setAGCreleaseTime", f(rng.choice([20.0, 100.0, 500.0]))),
+        lambda: S("setMute", int(rng.integers(0, 2))),
     ]
-    return table[k]()
+    return table[int(rng.integers(0, len(table)))]()
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12])
