@@ -47,9 +47,41 @@ typedef struct {
   int32_t shift, round;             /* s2, r2 */
 } ResampleArgs;
 
+/* Stage 1 of a fast-convolution bank (asdr_tuner_fastconv.hip).  Complex values are float pairs (re, im).  X and the four-step
+ * scratch are [n_sources][n_frames][N]; frame f of the call is frame b = P / H + f of the bank. */
+#define ASDR_TUNER_FC_LANES 256       /* forward kernel: one workgroup per transform (or four-step column / row) */
+#define ASDR_TUNER_FC_LDS_MAX 4096    /* largest transform done in one workgroup's LDS (32 KB) */
+#define ASDR_TUNER_FC_CH_LANES 64     /* channel kernel: one wave per (channel, frame), 4 of the 256 points per lane */
+
+typedef struct {
+  const int32_t *in;                /* [n_sources][in_stride] CS16 words (re low, im high) */
+  const int32_t *hist_rd;           /* [n_sources][H]: samples P - H .. P - 1 */
+  int32_t *hist_wr;                 /* [n_sources][H]: samples P + n_frames H - H .. (written by the history step) */
+  const float *tw;                  /* [N]: W_N^j = e^{-j 2 pi j / N}; then [256]: W_256^j */
+  float *scratch, *x;               /* [n_sources][n_frames][N] each */
+  int64_t in_stride;                /* complex samples */
+  int32_t n_sources, n_frames, hop; /* H */
+  int32_t log2n, log2n1, log2n2;    /* N = N1 N2 for the four-step passes (N > 4096) */
+  int32_t pass;                     /* 0: the whole transform; 1: four-step columns (N1 points); 2: four-step rows (N2 points) */
+} FcForwardArgs;
+
+typedef struct {
+  const float *x;                   /* [n_sources][n_frames][N] */
+  const float *g;                   /* [256]: G[m] at m' = m mod 256 */
+  const float *tw256;               /* [256]: W_256^j */
+  const asdr_tuner_state_t *chan;   /* [n_channels] */
+  const int32_t *order;             /* [n_channels]: channels sorted by (source, k0) (grid x follows it) */
+  int16_t *out_i, *out_q;           /* [n_channels][out_stride] */
+  int64_t pos;                      /* P before this call (a frame boundary) */
+  int64_t out_stride;               /* output samples */
+  int32_t n_channels, n_frames, hop, log2n, decimation;   /* H, log2 N, R */
+} FcChannelArgs;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* a fast-convolution stage 1: the forward step(s), the channel step, then the history step, in order on `stream` */
+int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, void *stream);
 /* the stage-2 step: every channel x 512-output tile (at least one tile: the carry is written even when no block is) */
 int asdr_launch_tuner_resample(const ResampleArgs *a, void *stream);
 /* the filter step (every channel x 128-output block) followed by the history step, in order on `stream` */

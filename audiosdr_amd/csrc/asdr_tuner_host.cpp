@@ -1,6 +1,8 @@
 // asdr_tuner_host.cpp -- host side + C ABI (include/asdr_tuner.h) of the digital tuner bank.  The control plane lives in a host
 // mirror (channel anchors, the source-sorted schedule, the polyphase taps) that is pushed before a launch when a setter touched it;
 // the per-source history rows live on the device only, double-buffered so that the launch that reads one writes the other.
+// Fast-convolution banks share all of it; their stage 1 (asdr_tuner_fastconv.hip) adds the channel filter's response G and the
+// twiddle tables, pushed the same way, and keeps H samples per source in the history rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,10 +37,10 @@ double bessel_i0(double x) {
   return s;
 }
 
-// Kaiser-windowed (beta 9) sinc of L taps with cut-off fc (cycles per sample); returns the sum of the taps.
-double kaiser_sinc(int L, double fc, std::vector<double> &w) {
+// Kaiser-windowed (beta 9 unless given) sinc of L taps with cut-off fc (cycles per sample); returns the sum of the taps.
+double kaiser_sinc(int L, double fc, std::vector<double> &w, double beta = 9.0) {
   const int M = L - 1;
-  const double beta = 9.0, pi = 3.14159265358979323846;
+  const double pi = 3.14159265358979323846;
   w.assign(L, 0.0);
   double sum = 0.0;
   for (int n = 0; n < L; n++) {
@@ -77,11 +79,25 @@ void default_rate_filter(int D, long long fs_mid, std::vector<int16_t> &h, int &
 
 // Stage-2 default: U = M = 1 -> {16384}, g2 = 1; otherwise a prototype of U K taps at U Fs_mid, cut-off 21.65 kHz,
 // K = 2 ceil(6 Fs_mid / 44100); each phase rounded to Q15 on its own, the residual to 32768 put on its largest tap; g2 = 0.
+// (K and the cut-off in cycles per sample at U Fs_mid are given: resampler_taps.)
+void resampler_taps(int U, int K, double fc, std::vector<int16_t> &h2, int &g2);
 void default_resampler(int U, int M, long long fs_mid, std::vector<int16_t> &h2, int &g2) {
   if (U == 1 && M == 1) { h2.assign(1, 16384); g2 = 1; return; }
-  const int K = (int)(2 * ((6 * fs_mid + 44099) / 44100)), L = U * K;
+  resampler_taps(U, (int)(2 * ((6 * fs_mid + 44099) / 44100)), 21650.0 / ((double)U * (double)fs_mid), h2, g2);
+}
+
+// The same rule at a fast-convolution bank's Fs_mid = Fs_in / R, which may be fractional: K = 2 ceil(6 Fs_in / (44100 R)),
+// cut-off 21650 R / (U Fs_in).
+void default_fastconv_resampler(int U, int M, long long fs_in, int R, std::vector<int16_t> &h2, int &g2) {
+  if (U == 1 && M == 1) { h2.assign(1, 16384); g2 = 1; return; }
+  const long long d = 44100LL * R;
+  resampler_taps(U, (int)(2 * ((6 * fs_in + d - 1) / d)), 21650.0 * R / ((double)U * (double)fs_in), h2, g2);
+}
+
+void resampler_taps(int U, int K, double fc, std::vector<int16_t> &h2, int &g2) {
+  const int L = U * K;
   std::vector<double> w;
-  const double sum = kaiser_sinc(L, 21650.0 / ((double)U * (double)fs_mid), w);
+  const double sum = kaiser_sinc(L, fc, w);
   h2.assign(L, 0);
   for (int ph = 0; ph < U; ph++) {
     long long tot = 0;
@@ -98,6 +114,15 @@ void default_resampler(int U, int M, long long fs_mid, std::vector<int16_t> &h2,
 }
 
 long long gcd_ll(long long a, long long b) { while (b) { const long long r = a % b; a = b; b = r; } return a; }
+
+// The fast-convolution default channel filter (asdr_tuner.h): Kaiser (beta 7.857) windowed sinc of 129 taps at Fs_mid, cut-off
+// 11.5 kHz + delta / 2 with delta = 0.0392 Fs_mid, normalised to sum 1, rounded to float.
+void default_channel_filter(double fs_mid, std::vector<float> &g) {
+  std::vector<double> w;
+  const double sum = kaiser_sinc(ASDR_TUNER_FC_MAX_TAPS, (11500.0 + 0.5 * 0.0392 * fs_mid) / fs_mid, w, 7.857);
+  g.resize(ASDR_TUNER_FC_MAX_TAPS);
+  for (int n = 0; n < ASDR_TUNER_FC_MAX_TAPS; n++) g[n] = (float)(w[n] / sum);
+}
 
 // U K taps and g2 passing the set_resampler rules for a bank with up-factor U
 std::string resampler_error(int U, const int16_t *h2, int n_taps, int g2) {
@@ -128,6 +153,14 @@ struct asdr_tuner_bank {
   std::vector<int16_t> h;
   int g = 0;
   bool chan_dirty = true, order_dirty = true, taps_dirty = true;
+  // fast-convolution bank: D = R, N = 256 R = 2^log2n, the channel filter g (float) whose response G is pushed, hist_slots = H
+  bool fc = false;
+  int log2n = 0, hist_slots = ASDR_TUNER_HIST_SLOTS;
+  std::vector<float> gch;
+  bool g_dirty = true;
+  float *d_fc_tab = nullptr;          // [N] W_N, [256] W_256, [256] G (float pairs)
+  float *d_fc_x = nullptr;            // X, then the four-step scratch: [2][n_sources][n_frames][N] float pairs
+  size_t fc_x_cap = 0;
   // device
   asdr_tuner_state_t *d_chan = nullptr;
   int32_t *d_order = nullptr, *d_taps = nullptr, *d_hist[2] = {nullptr, nullptr};
@@ -148,12 +181,25 @@ struct asdr_tuner_bank {
 };
 
 namespace {
+asdr_tuner_t *open_device(asdr_tuner_bank *t);
+
 asdr_tuner_state_t fresh_state() {
   asdr_tuner_state_t s;
   memset(&s, 0, sizeof s);
   return s;
 }
 uint32_t theta_at(const asdr_tuner_state_t &s, long long pos) { return s.ph_a + (uint32_t)(uint64_t)(pos - s.pos_a) * s.fw; }
+
+// fast-convolution banks: coarse bin k0 = floor(((int32) fw + q / 2) / q) and residual rw = fw - k0 q, q = 2^32 / N
+int coarse_bin(uint32_t fw, int log2n) {
+  const int lq = 32 - log2n;
+  return (int)(((int64_t)(int32_t)fw + (1LL << (lq - 1))) >> lq);
+}
+uint32_t residual(uint32_t fw, int log2n) { return fw - ((uint32_t)coarse_bin(fw, log2n) << (32 - log2n)); }
+// the fine NCO's phase at pos
+uint32_t fine_theta_at(const asdr_tuner_state_t &s, long long pos, int log2n) {
+  return s.ph_a + (uint32_t)(uint64_t)(pos - s.pos_a) * residual(s.fw, log2n);
+}
 
 // one retune of channel `ch` (or every channel): re-anchor at P with a continuous phase, then apply f
 template <typename F>
@@ -162,24 +208,47 @@ int retune(asdr_tuner_t *t, int ch, F f) {
   if (ch != ASDR_ALL && (ch < 0 || ch >= t->n)) return fail("bad channel");
   for (int i = (ch == ASDR_ALL ? 0 : ch); i < (ch == ASDR_ALL ? t->n : ch + 1); i++) {
     asdr_tuner_state_t &s = t->chan[i];
-    s.ph_a = theta_at(s, t->pos);
+    s.ph_a = t->fc ? fine_theta_at(s, t->pos, t->log2n) : theta_at(s, t->pos);
     s.pos_a = t->pos;
     f(s);
   }
   t->chan_dirty = true;
+  if (t->fc) t->order_dirty = true;   // sorted by (source, k0)
   return 0;
 }
 
 int push(asdr_tuner_t *t, hipStream_t stream) {
-  if (!t->chan_dirty && !t->order_dirty && !t->taps_dirty) return 0;
+  if (!t->chan_dirty && !t->order_dirty && !t->taps_dirty && !(t->fc && t->g_dirty)) return 0;
   if (t->order_dirty) {
     t->order.resize(t->n);
     for (int i = 0; i < t->n; i++) t->order[i] = i;
-    std::stable_sort(t->order.begin(), t->order.end(), [t](int a, int b) { return t->chan[a].src < t->chan[b].src; });
+    if (t->fc) {   // neighbouring waves gather overlapping bins of one source's X
+      std::vector<int64_t> key(t->n);
+      for (int i = 0; i < t->n; i++) key[i] = ((int64_t)t->chan[i].src << 32) + coarse_bin(t->chan[i].fw, t->log2n);
+      std::stable_sort(t->order.begin(), t->order.end(), [&key](int a, int b) { return key[a] < key[b]; });
+    } else {
+      std::stable_sort(t->order.begin(), t->order.end(), [t](int a, int b) { return t->chan[a].src < t->chan[b].src; });
+    }
     HIPCHK(hipMemcpyAsync(t->d_order, t->order.data(), t->n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
+  std::vector<float> G;
+  if (t->fc && t->g_dirty) {   // G[m] = sum_n g[n] e^{-j 2 pi m n / 256} in float64, at m' = m mod 256, rounded to float
+    const double pi = 3.14159265358979323846;
+    G.assign(512, 0.0f);
+    for (int mp = 0; mp < 256; mp++) {
+      const int m = mp < 128 ? mp : mp - 256;
+      double re = 0.0, im = 0.0;
+      for (size_t n = 0; n < t->gch.size(); n++) {
+        const double a = 2.0 * pi * (double)(((m * (int)n) % 256 + 256) % 256) / 256.0;
+        re += (double)t->gch[n] * std::cos(a);
+        im -= (double)t->gch[n] * std::sin(a);
+      }
+      G[2 * mp] = (float)re; G[2 * mp + 1] = (float)im;
+    }
+    HIPCHK(hipMemcpyAsync(t->d_fc_tab + 2 * ((1 << t->log2n) + 256), G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+  }
   std::vector<int32_t> taps;
-  if (t->taps_dirty) {
+  if (t->taps_dirty && !t->fc) {
     const int D = t->D, L = (int)t->h.size();
     t->n_rows = (L + D - 1) / D;
     t->n_pairs = (D + 1) / 2;
@@ -195,6 +264,7 @@ int push(asdr_tuner_t *t, hipStream_t stream) {
   if (t->chan_dirty) HIPCHK(hipMemcpyAsync(t->d_chan, t->chan.data(), t->n * sizeof(asdr_tuner_state_t), hipMemcpyHostToDevice, stream));
   HIPCHK(hipStreamSynchronize(stream));   // the host mirrors may change as soon as this returns
   t->chan_dirty = t->order_dirty = t->taps_dirty = false;
+  if (t->fc) t->g_dirty = false;
   return 0;
 }
 
@@ -238,9 +308,40 @@ int push_resampler(asdr_tuner_t *t, hipStream_t stream) {
   return 0;
 }
 
+// A fast-convolution bank's stage 1 (asdr_tuner_fastconv.hip): n_frames frames of every channel into rows out_stride_blocks apart.
+int run_fastconv(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_frames,
+                 long out_stride_blocks, hipStream_t stream) {
+  const int log2n = t->log2n, N = 1 << log2n, H = N / 2;
+  const size_t x_floats = (size_t)t->n_src * n_frames * N * 2;
+  const size_t x_bytes = (log2n > 12 ? 2 : 1) * x_floats * sizeof(float);
+  if (x_bytes > t->fc_x_cap) {   // grow X (and the scratch): nothing of ours may be in flight
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (t->d_fc_x) HIPCHK(hipFree(t->d_fc_x));
+    t->d_fc_x = nullptr; t->fc_x_cap = 0;
+    HIPCHK(hipMalloc(&t->d_fc_x, x_bytes));
+    t->fc_x_cap = x_bytes;
+  }
+  FcForwardArgs f;
+  f.in = (const int32_t *)dIQ; f.hist_rd = t->d_hist[t->cur]; f.hist_wr = t->d_hist[t->cur ^ 1];
+  f.tw = t->d_fc_tab; f.x = t->d_fc_x; f.scratch = t->d_fc_x + x_floats;
+  f.in_stride = in_stride_samples; f.n_sources = t->n_src; f.n_frames = n_frames; f.hop = H;
+  f.log2n = log2n; f.log2n1 = (log2n + 1) / 2; f.log2n2 = log2n - f.log2n1;
+  f.pass = log2n > 12 ? 1 : 0;
+  FcChannelArgs c;
+  c.x = t->d_fc_x; c.tw256 = t->d_fc_tab + 2 * N; c.g = t->d_fc_tab + 2 * (N + 256);
+  c.chan = t->d_chan; c.order = t->d_order; c.out_i = dI; c.out_q = dQ;
+  c.pos = t->pos; c.out_stride = (int64_t)out_stride_blocks * 128;
+  c.n_channels = t->n; c.n_frames = n_frames; c.hop = H; c.log2n = log2n; c.decimation = t->D;
+  if (asdr_launch_tuner_fastconv(&f, &c, stream) != 0) return fail("fast-convolution kernel launch failed");
+  t->pos += (long long)n_frames * H;
+  t->cur ^= 1;
+  return 0;
+}
+
 // The stage-1 launch of a call: n_blocks blocks of every channel into rows out_stride_blocks apart, then P advances.
 int run_stage1(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
                long out_stride_blocks, hipStream_t stream) {
+  if (t->fc) return run_fastconv(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream);
   TunerArgs a;
   a.in = (const int32_t *)dIQ; a.hist_rd = t->d_hist[t->cur]; a.hist_wr = t->d_hist[t->cur ^ 1];
   a.chan = t->d_chan; a.order = t->d_order; a.taps = t->d_taps; a.out_i = dI; a.out_q = dQ;
@@ -288,11 +389,17 @@ asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int de
   default_rate_filter(decimation, fs_mid, t->h, t->g);
   default_resampler(t->up, t->down, fs_mid, t->h2, t->g2);
   t->k2 = (int)t->h2.size() / t->up;
+  return open_device(t);
+}
+
+// The device side of a new bank (nothing for ASDR_NO_DEVICE); deletes the bank and returns NULL on failure.
+asdr_tuner_t *open_device(asdr_tuner_bank *t) {
+  const int device = t->device, n_sources = t->n_src, n_channels = t->n;
   if (device == ASDR_NO_DEVICE) return t;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete t; return nullptr; }
   if (device < 0 || device >= count) { fail("bad device index"); delete t; return nullptr; }
-  const size_t hist = (size_t)n_sources * ASDR_TUNER_HIST_SLOTS * sizeof(int32_t);
+  const size_t hist = (size_t)n_sources * t->hist_slots * sizeof(int32_t);
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&t->stream) != hipSuccess || hipEventCreate(&t->ev0) != hipSuccess ||
       hipEventCreate(&t->ev1) != hipSuccess || hipMalloc(&t->d_chan, n_channels * sizeof(asdr_tuner_state_t)) != hipSuccess ||
       hipMalloc(&t->d_order, n_channels * sizeof(int32_t)) != hipSuccess || hipMalloc(&t->d_taps, kTapWords * sizeof(int32_t)) != hipSuccess ||
@@ -304,7 +411,43 @@ asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int de
     asdr_tuner_destroy(t);
     return nullptr;
   }
+  if (t->fc) {   // twiddles W_N^j, W_256^j from float64; G follows with the first push
+    const int N = 1 << t->log2n;
+    const double pi = 3.14159265358979323846;
+    std::vector<float> tab(2 * ((size_t)N + 512), 0.0f);
+    for (int j = 0; j < N; j++) { tab[2 * j] = (float)std::cos(2.0 * pi * j / N); tab[2 * j + 1] = (float)-std::sin(2.0 * pi * j / N); }
+    for (int j = 0; j < 256; j++) {
+      tab[2 * (N + j)] = (float)std::cos(2.0 * pi * j / 256); tab[2 * (N + j) + 1] = (float)-std::sin(2.0 * pi * j / 256);
+    }
+    if (hipMalloc(&t->d_fc_tab, tab.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(t->d_fc_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      fail("tuner bank: device allocation failed");
+      asdr_tuner_destroy(t);
+      return nullptr;
+    }
+  }
   return t;
+}
+
+asdr_tuner_t *create_fastconv(int n_channels, int n_sources, long long fs_in, int R, int device) {
+  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (n_sources <= 0 || n_sources > 65535) { fail("n_sources must be in 1..65535"); return nullptr; }
+  if (R < 2 || R > ASDR_TUNER_FC_MAX_R || (R & (R - 1)) != 0) { fail("R must be a power of two in 2..1024"); return nullptr; }
+  if (fs_in <= 0) { fail("input rate Fs_in must be positive"); return nullptr; }
+  if (fs_in < 44100LL * R || fs_in > 176400LL * R) { fail("Fs_in / R must lie in [44100, 176400] Hz"); return nullptr; }
+  const long long gd = gcd_ll(44100LL * R, fs_in);
+  if (44100LL * R / gd > ASDR_TUNER_MAX_UP) { fail("44100 R / Fs_in in lowest terms needs U > 2048"); return nullptr; }
+  asdr_tuner_bank *t = new asdr_tuner_bank();
+  t->n = n_channels; t->n_src = n_sources; t->D = R; t->device = device;
+  t->fs_in = fs_in; t->up = (int)(44100LL * R / gd); t->down = (int)(fs_in / gd);
+  t->fc = true;
+  for (t->log2n = 0; (1 << t->log2n) < 256 * R; t->log2n++) {}
+  t->hist_slots = 128 * R;
+  t->chan.assign(n_channels, fresh_state());
+  default_channel_filter((double)fs_in / R, t->gch);
+  default_fastconv_resampler(t->up, t->down, fs_in, R, t->h2, t->g2);
+  t->k2 = (int)t->h2.size() / t->up;
+  return open_device(t);
 }
 }  // namespace
 
@@ -319,6 +462,32 @@ asdr_tuner_t *asdr_tuner_create_rate(int n_channels, int n_sources, long long fs
   return create_bank(n_channels, n_sources, fs_in_hz, decimation, device);
 }
 
+asdr_tuner_t *asdr_tuner_create_fastconv(int n_channels, int n_sources, long long fs_in_hz, int R, int device) {
+  return create_fastconv(n_channels, n_sources, fs_in_hz, R, device);
+}
+
+int asdr_tuner_fft_size(const asdr_tuner_t *t) { return t && t->fc ? 1 << t->log2n : 0; }
+
+int asdr_tuner_set_channel_filter(asdr_tuner_t *t, const float *g, int n_taps) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail("only a fast-convolution bank has a channel filter: use asdr_tuner_set_filter");
+  if (!g) return fail("null taps");
+  if (n_taps < 1 || n_taps > ASDR_TUNER_FC_MAX_TAPS) return fail("channel filter length must be in 1..129");
+  for (int k = 0; k < n_taps; k++)
+    if (!std::isfinite(g[k])) return fail("channel filter taps must be finite");
+  t->gch.assign(g, g + n_taps);
+  t->g_dirty = true;
+  return 0;
+}
+
+int asdr_tuner_get_channel_filter(const asdr_tuner_t *t, float *g, int cap) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail("only a fast-convolution bank has a channel filter: use asdr_tuner_get_filter");
+  const int L = (int)t->gch.size();
+  if (g) for (int k = 0; k < L && k < cap; k++) g[k] = t->gch[k];
+  return L;
+}
+
 void asdr_tuner_destroy(asdr_tuner_t *t) {
   if (!t) return;
   if (t->device != ASDR_NO_DEVICE) {
@@ -326,6 +495,7 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipDeviceSynchronize();
     hipFree(t->d_chan); hipFree(t->d_order); hipFree(t->d_taps); hipFree(t->d_hist[0]); hipFree(t->d_hist[1]); hipFree(t->d_io);
     hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
+    hipFree(t->d_fc_tab); hipFree(t->d_fc_x);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -337,7 +507,7 @@ int asdr_tuner_reset(asdr_tuner_t *t) {
   if (!t) return fail("null tuner bank");
   if (t->device != ASDR_NO_DEVICE) {
     if (asdr_tuner_synchronize(t) != 0) return -1;
-    HIPCHK(hipMemset(t->d_hist[t->cur], 0, (size_t)t->n_src * ASDR_TUNER_HIST_SLOTS * sizeof(int32_t)));
+    HIPCHK(hipMemset(t->d_hist[t->cur], 0, (size_t)t->n_src * t->hist_slots * sizeof(int32_t)));
     if (t->d_carry[t->ccur]) HIPCHK(hipMemset(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t)));
     HIPCHK(hipDeviceSynchronize());
   }
@@ -379,6 +549,7 @@ int asdr_tuner_set_phase(asdr_tuner_t *t, int ch, uint32_t phase) {
 
 int asdr_tuner_set_filter(asdr_tuner_t *t, const int16_t *h, int n_taps, int gain_shift) {
   if (!t) return fail("null tuner bank");
+  if (t->fc) return fail("a fast-convolution bank has a float channel filter: use asdr_tuner_set_channel_filter");
   if (!h) return fail("null taps");
   if (n_taps < 1 || n_taps > ASDR_TUNER_MAX_TAPS) return fail("filter length must be in 1..1024");
   if (gain_shift < 0 || gain_shift > ASDR_TUNER_MAX_GAIN_SHIFT) return fail("gain shift must be in 0..15");
@@ -393,6 +564,7 @@ int asdr_tuner_set_filter(asdr_tuner_t *t, const int16_t *h, int n_taps, int gai
 
 int asdr_tuner_get_filter(const asdr_tuner_t *t, int16_t *h, int cap, int *gain_shift) {
   if (!t) return fail("null tuner bank");
+  if (t->fc) return fail("a fast-convolution bank has a float channel filter: use asdr_tuner_get_channel_filter");
   const int L = (int)t->h.size();
   if (h) for (int k = 0; k < L && k < cap; k++) h[k] = t->h[k];
   if (gain_shift) *gain_shift = t->g;

@@ -13,10 +13,12 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_read_state", "asdr_tuner_update_device", "asdr_tuner_update", "asdr_tuner_synchronize",
                  "asdr_tuner_last_kernel_ms", "asdr_tuner_create_rate", "asdr_tuner_rate", "asdr_tuner_ratio",
                  "asdr_tuner_output_position", "asdr_tuner_set_resampler", "asdr_tuner_get_resampler", "asdr_tuner_out_blocks",
-                 "asdr_tuner_update_rate_device", "asdr_tuner_update_rate"]
+                 "asdr_tuner_update_rate_device", "asdr_tuner_update_rate", "asdr_tuner_create_fastconv", "asdr_tuner_fft_size",
+                 "asdr_tuner_set_channel_filter", "asdr_tuner_get_channel_filter"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
+MAX_CHANNEL_TAPS = 129
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
@@ -55,6 +57,11 @@ def _lib():
     L.asdr_tuner_out_blocks.argtypes = [vp, i]; L.asdr_tuner_out_blocks.restype = i
     L.asdr_tuner_update_rate_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_rate_device.restype = i
     L.asdr_tuner_update_rate.argtypes = [vp, i16p, i, i16p, i16p, i]; L.asdr_tuner_update_rate.restype = i
+    fp = C.POINTER(C.c_float)
+    L.asdr_tuner_create_fastconv.argtypes = [i, i, ll, i, i]; L.asdr_tuner_create_fastconv.restype = vp
+    L.asdr_tuner_fft_size.argtypes = [vp]; L.asdr_tuner_fft_size.restype = i
+    L.asdr_tuner_set_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_set_channel_filter.restype = i
+    L.asdr_tuner_get_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_get_channel_filter.restype = i
     _typed = True
     return L
 
@@ -84,6 +91,29 @@ def suggest_decimation(fs_in):
     return None
 
 
+def fastconv_ratio(fs_in, R):
+    """(U, M) = 44100 R / fs_in in lowest terms if (fs_in, R) makes a valid fast-convolution bank (include/asdr_tuner.h), else None."""
+    import math
+    fs_in, R = int(fs_in), int(R)
+    if fs_in <= 0 or not 2 <= R <= 1024 or R & (R - 1):
+        return None
+    if not MID_RANGE[0] * R <= fs_in <= MID_RANGE[1] * R:
+        return None
+    g = math.gcd(44100 * R, fs_in)
+    return (44100 * R // g, fs_in // g) if 44100 * R // g <= MAX_UP else None
+
+
+def suggest_fft_decimation(fs_in):
+    """The R that puts fs_in / R in [44100, 176400] with the smallest stage-2 U (ties: the larger R, the least work per channel),
+    or None."""
+    best = None
+    for R in (1 << k for k in range(1, 11)):
+        ud = fastconv_ratio(fs_in, R)
+        if ud is not None and (best is None or ud[0] <= best[0]):
+            best = (ud[0], R)
+    return None if best is None else best[1]
+
+
 class TunerBank:
     """n_channels digital tuners over n_sources shared CS16 rows at decimation D (include/asdr_tuner.h).  fs_in (Hz) makes a rate
     bank: any integer input rate with fs_in / D in [44100, 176400], resampled to 44.1 kHz after the decimator.  device = NO_DEVICE
@@ -99,6 +129,35 @@ class TunerBank:
             raise AsdrError("asdr_tuner_create%s failed: %s" % ("" if fs_in is None else "_rate", self._L.asdr_last_error().decode()))
         self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(decimation)
         self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+
+    @classmethod
+    def fastconv(cls, n_channels, n_sources, fs_in, R, device=0):
+        """A fast-convolution bank (include/asdr_tuner.h, "Fast-convolution banks"): overlap-save stage 1 with one FFT of N = 256 R
+        points per source and frame, fs_in / R in [44100, 176400], then the rate-bank stage 2.  `decimation` is R."""
+        self = cls.__new__(cls)
+        self._L = _lib()
+        self._h = self._L.asdr_tuner_create_fastconv(int(n_channels), int(n_sources), int(fs_in), int(R), int(device))
+        if not self._h:
+            raise AsdrError("asdr_tuner_create_fastconv failed: %s" % self._L.asdr_last_error().decode())
+        self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(R)
+        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+        return self
+
+    def fft_size(self):
+        """N of a fast-convolution bank, 0 for a direct-form bank."""
+        return int(self._L.asdr_tuner_fft_size(self._h))
+
+    def set_channel_filter(self, g):
+        """Real taps (float32, 1..129) at Fs_mid of a fast-convolution bank."""
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        self._chk(self._L.asdr_tuner_set_channel_filter(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), int(g.size)))
+
+    def get_channel_filter(self):
+        """float32 [Lg]."""
+        n = self._chk(self._L.asdr_tuner_get_channel_filter(self._h, None, 0))
+        g = np.zeros(n, dtype=np.float32)
+        self._chk(self._L.asdr_tuner_get_channel_filter(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return g
 
     def close(self):
         if getattr(self, "_h", None):

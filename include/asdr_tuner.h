@@ -42,6 +42,39 @@
  *             23200))) + 1 taps, g = 0.  Stage 2: U = M = 1 -> {16384}, g2 = 1; otherwise a prototype at U Fs_mid with cut-off
  *             21.65 kHz, K = 2 ceil(6 Fs_mid / 44100), each phase rounded to Q15 on its own and its largest tap corrected so the
  *             phase sums to exactly 32768, g2 = 0 (DESIGN.md 3.8 gives the responses).
+ *
+ * Fast-convolution banks (asdr_tuner_create_fastconv): stage 1 by overlap-save, one forward FFT per source and frame shared by all
+ * of its channels, so a channel's cost follows its output rate, not Fs_in.  Floating point, unlike the integer-exact direct form:
+ * the statement below is exact (float64); the kernels compute in float32 and agree with it within +-1 of u.
+ *   bank      R a power of two in [2, 1024]; Fs_mid = Fs_in / R in [44100, 176400] (it may be fractional: Fs_in % R need not be
+ *             0); U / M = 44100 R / Fs_in in lowest terms, U <= 2048 (2.4 MS/s, R = 16 -> 147 / 500; 20 MS/s, R = 128 -> 882 /
+ *             3125; 61.44 MS/s, R = 512 -> 147 / 400).  decimation() returns R, rate() Fs_in.
+ *   sizes     hop H = 128 R input samples, FFT size N = 2 H = 256 R (512 .. 262,144), q = 2^32 / N.
+ *   frame b   counted from creation / reset; consumes input samples [b H, (b + 1) H) of every source.  Its window is
+ *             x_s[(b - 1) H .. (b + 1) H - 1] (zeros before position 0), X = DFT_N(window), unnormalised, e^{-j 2 pi k n / N}.
+ *   channel   src, fw, anchor (pos_a, ph_a) as above (the setters map Hz to fw as for rate banks).  Coarse bin
+ *             k0 = floor(((int32) fw + q / 2) / q); residual rw = (int32)(fw - k0 q) in [-q / 2, q / 2).
+ *   filter    real taps g[0 .. Lg - 1] (float), 1 <= Lg <= 129, at Fs_mid, one for the whole bank; its response
+ *             G[m] = sum_n g[n] e^{-j 2 pi m n / 256}, m in [-128, 128), computed in float64 and rounded to float.
+ *   output    y[n] = (1 / N) sum_{m=-128}^{127} X[(k0 + m) mod N] G[m] e^{+j 2 pi m n / 256} for n = 128 .. 255 (overlap-save: the
+ *             first 128 are discarded); i = 128 b + n - 128 is the Fs_mid sample (input sample i R).  Times (-1)^{k0 (b - 1)}, so
+ *             that the coarse shift is mixing by e^{-j 2 pi k0 m / N} at absolute input sample m; times e^{-j 2 pi theta_i / 2^32}
+ *             with the fine NCO theta_i = ph_a + rw (i R - pos_a) mod 2^32 (evaluated from (int32) theta_i, |error| <= 2^-21);
+ *             u[i] = sat16(rint(Re)), sat16(rint(Im)), round half to even.  The fine shift follows the filter: the filter acts at
+ *             a tone's offset from the coarse bin (k0 Fs_in / N), at most Fs_mid / 512 from the tuned frequency; the one visible
+ *             effect is a constant phase 2 pi (rw Fs_in / 2^32) tau_g on the channel (tau_g: the filter's group delay).
+ *   stage 2   the rate-bank resampler, unchanged, with its timing and out_blocks rule: a call consumes whole frames (H input
+ *             samples per source) and makes 128 new u samples per frame.  Fs_in = 44100 R defaults to a pass-through (output u).
+ *   retune    set_source / set_frequency(_word) / set_phase act at the current P, always a frame boundary: pos_a = P, ph_a =
+ *             theta_P of the fine NCO (continuous) or the given phase.  Unlike the direct form no history is flushed: a
+ *             fast-convolution channel has none of its own.  Reset zeroes P, the output position, the sources' windows (the last
+ *             H samples per source) and the stage-2 carry.
+ *   defaults  channel filter: Kaiser (beta 7.857) windowed sinc, 129 taps, sum g = 1, cut-off 11.5 kHz + delta / 2 with delta =
+ *             0.0392 Fs_mid (Kaiser's 80 dB transition width for 129 taps): flat over |f| <= 11.5 kHz (0 - 11.2 kHz after the
+ *             fine shift), stop band from 11.5 kHz + delta to Fs_mid / 2.  Stage 2: the rate banks' rule at this Fs_mid, i.e.
+ *             K = 2 ceil(6 Fs_in / (44100 R)), cut-off 21.65 kHz at U Fs_mid.
+ *   ABI       every other function works as for rate banks, except set_filter / get_filter, which fail (use
+ *             set_channel_filter / get_channel_filter), and update(_device), which need a pass-through stage 2.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -60,6 +93,8 @@ extern "C" {
 #define ASDR_TUNER_HISTORY 1023 /* input samples per source kept across calls (L - 1 at most) */
 #define ASDR_TUNER_MAX_UP 2048
 #define ASDR_TUNER_MAX_RESAMPLER_TAPS 64 /* K, taps per phase */
+#define ASDR_TUNER_FC_MAX_R 1024
+#define ASDR_TUNER_FC_MAX_TAPS 129       /* Lg, channel filter taps of a fast-convolution bank */
 
 typedef struct asdr_tuner_bank asdr_tuner_t;
 
@@ -124,6 +159,15 @@ int asdr_tuner_out_blocks(const asdr_tuner_t *t, int n_frames);
 int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int n_frames, int16_t *dI,
                                   int16_t *dQ, int out_capacity_blocks, long out_stride_blocks, void *stream);
 int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks);
+
+/* Fast-convolution banks.  NULL (asdr_last_error) for each violated constraint above; ASDR_NO_DEVICE gives a control-plane-only
+ * bank. */
+asdr_tuner_t *asdr_tuner_create_fastconv(int n_channels, int n_sources, long long fs_in_hz, int R, int device);
+int asdr_tuner_fft_size(const asdr_tuner_t *t);   /* N, or 0 for a direct-form bank */
+/* Rejected (old filter kept): Lg outside 1..129, a non-finite tap, a direct-form bank.  Applies from the next call on. */
+int asdr_tuner_set_channel_filter(asdr_tuner_t *t, const float *g, int n_taps);
+/* Copies min(Lg, cap) taps to g (if not NULL); returns Lg (fails on a direct-form bank). */
+int asdr_tuner_get_channel_filter(const asdr_tuner_t *t, float *g, int cap);
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */

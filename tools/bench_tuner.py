@@ -8,15 +8,21 @@
   T4        rate bank: 16 sources at 2.4 MS/s, D = 50 (stage 2: 147 / 160), 65,536 channels, default filters, 16 frames per call
   T4+chain  T4 followed by asdr_update_device (USB) on the same stream
   S48       skimmer on sound-card I/Q: 1 source at 48 kHz, D = 1 (147 / 160), 4,096 channels, default filters, 64 frames per call
+  F4        fast-convolution bank, T4's geometry: 16 sources at 2.4 MS/s, R = 16 (N = 4,096; stage 2: 147 / 500), 65,536 channels,
+            default filters, 16 frames per call
+  F4+chain  F4 followed by asdr_update_device (USB) on the same stream
+  F20       fast-convolution bank: 16 sources at 20 MS/s, R = 128 (N = 32,768; 882 / 3125), 65,536 channels, 16 frames per call
+  F61       fast-convolution bank: 4 sources at 61.44 MS/s, R = 512 (N = 131,072; 147 / 400), 16,384 channels, 16 frames per call
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
 source, int16 I and Q out, the history rows); their share of the VALU issue bound and of HBM, and which of the two bounds the
 call.  Rate banks (T4, S48) add stage 2's 2 K multiply-adds per output and the intermediate rows' traffic; x real time is input
 time per call over call time.  The first call of each config is checked against tests/tuner_ref.py / tuner_rate_ref.py on a few
-channels.  Inputs are seeded.
+channels.  Fast-convolution banks (F*) have no operation model here (DESIGN.md 3.8.2 counts them); their first call is checked
+against tests/tuner_fastconv_ref.py, a float64 statement, so "parity" there means every sample within +-2.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61]
 """
 import json
 import os
@@ -30,6 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import audiosdr_amd as A  # noqa: E402
+import tuner_fastconv_ref as FR  # noqa: E402
 import tuner_rate_ref as RR  # noqa: E402
 import tuner_ref as R  # noqa: E402
 
@@ -44,19 +51,23 @@ CONFIGS = {
     "T4": dict(n_src=16, D=50, n_ch=65536, L=None, nb=16, fs_in=2400000),
     "T4+chain": dict(n_src=16, D=50, n_ch=65536, L=None, nb=16, chain=True, fs_in=2400000),
     "S48": dict(n_src=1, D=1, n_ch=4096, L=None, nb=64, fs_in=48000),
+    "F4": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True),
+    "F4+chain": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, chain=True, fs_in=2400000, fastconv=True),
+    "F20": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True),
+    "F61": dict(n_src=4, D=512, n_ch=16384, L=None, nb=16, fs_in=61440000, fastconv=True),
 }
 
 
-def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None):
-    """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given)."""
+def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
+    """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank."""
     rng = np.random.default_rng(sum(map(ord, name)))
-    bank = A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
+    bank = A.TunerBank.fastconv(n_ch, n_src, fs_in, D) if fastconv else A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
     rate = fs_in is not None
     cap = nb + 1 if rate else nb
     if L is not None:
         h = np.round(np.hamming(L) * np.sinc((np.arange(L) - (L - 1) / 2) * 0.5) * 16384 / 2).astype(np.int16)
         bank.set_filter(h, 0)
-    h, g = bank.get_filter()
+    h, g = (bank.get_channel_filter(), 0) if fastconv else bank.get_filter()
     L = h.size
     srcs = np.arange(n_ch) % n_src
     fws = rng.integers(0, 2**32, size=n_ch, dtype=np.uint64)
@@ -92,7 +103,10 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None):
 
     # parity of the first call on 8 channels
     check = sorted(set([0, 1, n_ch - 1] + [int(c) for c in rng.integers(0, n_ch, size=5)]))
-    if rate:
+    if fastconv:
+        h2, g2 = bank.get_resampler()
+        ref = FR.TunerFastconvRef(len(check), n_src, fs_in, D, h, h2, g2)
+    elif rate:
         h2, g2 = bank.get_resampler()
         ref = RR.TunerRateRef(len(check), n_src, D, fs_in, h, g, h2, g2)
     else:
@@ -103,7 +117,12 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None):
     torch.cuda.synchronize()
     wI, wQ = ref.update(iq[0])
     n0 = out_blocks[0]
-    parity = bool(np.array_equal(dI.cpu().numpy()[check, :n0], wI) and np.array_equal(dQ.cpu().numpy()[check, :n0], wQ))
+    if fastconv:
+        dmax = max(int(np.abs(dI.cpu().numpy()[check, :n0].astype(np.int64) - wI).max(initial=0)),
+                   int(np.abs(dQ.cpu().numpy()[check, :n0].astype(np.int64) - wQ).max(initial=0)))
+        parity = dmax <= 2
+    else:
+        parity = bool(np.array_equal(dI.cpu().numpy()[check, :n0], wI) and np.array_equal(dQ.cpu().numpy()[check, :n0], wQ))
     # warm, then size the timed window to >= 1 s
     for k in range(1, 6):
         call(k)
@@ -135,17 +154,19 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None):
             nbytes += n_mid * 4 + n_out * 4 + 2 * n_ch * 576 * 4     # intermediate read back, outputs, carry
     t_valu, t_hbm = macs / VALU_LANE_OPS, nbytes / HBM_BPS
     bound = "valu" if t_valu >= t_hbm else "hbm"
+    model = {"int_mult_adds": int(macs), "bytes": int(nbytes), "valu_bound_ms": round(t_valu * 1e3, 4),
+             "hbm_bound_ms": round(t_hbm * 1e3, 4), "bound": bound, "share_of_bound": round(max(t_valu, t_hbm) / (ms * 1e-3), 4),
+             "note": "tuner model only" if chain else None}
     out = {"config": name, "sources": n_src, "decimation": D, "channels": n_ch, "taps": int(L), "blocks_per_call": nb,
            "chain": "USB" if chain else None, "timed_calls": reps, "timed_s": round(ms * reps / 1e3, 3),
            "ms_per_call": round(ms, 4), "output_samples_per_s": round(n_out / (ms * 1e-3), 1),
            "realtime_factor": round(N / float(fs_in or 44100 * D) / (ms * 1e-3), 2),
            "fs_in": int(fs_in or 44100 * D), "ratio": list(bank.ratio()), "resampler_taps_per_phase": int(K2) if rate else None,
            "output_blocks_per_call": round(sum(out_blocks) / reps, 3),
-           "model": {"int_mult_adds": int(macs), "bytes": int(nbytes), "valu_bound_ms": round(t_valu * 1e3, 4),
-                     "hbm_bound_ms": round(t_hbm * 1e3, 4), "bound": bound,
-                     "share_of_bound": round(max(t_valu, t_hbm) / (ms * 1e-3), 4),
-                     "note": "tuner model only" if chain else None},
+           "model": None if fastconv else model,
            "parity_channels": len(check), "parity": parity}
+    if fastconv:
+        out.update({"kind": "fastconv", "fft_size": bank.fft_size(), "parity_max_abs_diff": dmax})
     print(json.dumps(out), flush=True)
     bank.close()
     if sdr is not None:
