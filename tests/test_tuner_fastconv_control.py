@@ -100,6 +100,21 @@ def test_channel_filter_setter(A, T):
     assert t.get_channel_filter().size == 129 and np.array_equal(t.get_channel_filter(), g)   # reset keeps the filter
 
 
+def test_channel_filter_setter_takes_every_finite_tap(A, T):
+    """Lg = 1 and Lg = 129 at the ends of the range, and taps that are finite but extreme: denormals, +-3e38, -0.0."""
+    t = T(44100 * 4, 4)
+    tiny = np.array([1e-45, -1e-40, 1.17549421e-38], dtype=np.float32)            # two denormals and one just below FLT_MIN
+    assert tiny[0] != 0 and tiny[1] != 0
+    for g in (np.array([3e38], np.float32), np.array([-3e38], np.float32), tiny, np.array([-0.0, 1.0], np.float32),
+              np.concatenate([np.full(128, 1e-45, np.float32), np.array([3e38], np.float32)])):
+        t.set_channel_filter(g)
+        got = t.get_channel_filter()
+        assert got.size == g.size and got.tobytes() == g.tobytes()
+    with pytest.raises(A.AsdrError, match="1..129"):
+        t.set_channel_filter(np.full(130, 1e-45, np.float32))
+    assert t.get_channel_filter().size == 129
+
+
 def test_filter_calls_refuse_the_wrong_kind_of_bank(A, T):
     t = T(2400000, 16)
     with pytest.raises(A.AsdrError, match="set_channel_filter"):

@@ -1,10 +1,13 @@
 """The fast-convolution restatement (tests/tuner_fastconv_ref.py) against the statement itself and against known answers: an
 explicit-sum evaluation of the definition at a small N, multitone inputs through the coarse bin, the filter and the fine NCO
 (across frames, both ends of the spectrum and retunes), the default channel filter's response, and an off-channel tone through
-the default stage 2.  CPU only; the last test reads the default stage 2 from an ASDR_NO_DEVICE bank."""
+the default stage 2; the float32 model stage1_f32 against stage1, the GPU suite's EPS table recomputed from it at R <= 16, and
+a reference placed at a position against one stepped there.  CPU only; one test reads the default stage 2 from an
+ASDR_NO_DEVICE bank."""
 import numpy as np
 import pytest
 
+import test_gpu_tuner_fastconv as T
 import tuner_fastconv_ref as F
 
 
@@ -137,3 +140,62 @@ def test_off_channel_tone_through_the_default_stage_2(A):
         else:
             on = np.abs(z).mean()
     assert on > 15000.0 and 20 * np.log10(max(off, 0.5) / on) <= -75.0, (on, off)
+
+
+@pytest.mark.parametrize("R", [2, 8, 64])
+def test_float32_model_against_the_float64_statement(R):
+    """stage1_f32 is stage1 in float32: the same values to about sqrt(log2 N) 2^-24 of the peak, and not closer than float32 can
+    be (it would then be float64 under another name).  State advances alike."""
+    fs = 44100 * R
+    rng = np.random.default_rng(R)
+    a, b = (F.TunerFastconvRef(4, 2, fs, R, g=T.G_ASYM * 4) for _ in range(2))
+    for o in (a, b):
+        T.setup(o, [0, 1, 0, 1], T.edge_words(R)[6:10])
+    iq = T.cs16(rng, 2, 3 * 128 * R)
+    z, w = a.stage1(iq), b.stage1_f32(iq)
+    assert z.dtype == w.dtype == np.complex128 and a.P == b.P == 3 * 128 * R and np.array_equal(a.hist, b.hist)
+    err, peak = np.abs(w - z).max(), np.abs(z).max()
+    assert 2.0 ** -27 * peak <= err <= 16 * 2.0 ** -24 * peak, (err, peak)
+    assert np.array_equal(b.update(iq, keep_float=True, f32=True)[2], b.__class__.stage1_f32(a, iq))   # update(f32=True) is it
+
+
+def test_eps_table_is_eight_times_the_float32_model():
+    """The committed EPS of the GPU suite: an entry for every (recipe, R) it runs, none above 0.1, and 8 x the model's largest
+    error on the recipe's own inputs (recomputed here for R <= 16) within 10 %."""
+    assert set(T.EPS) == {(r, R) for r, Rs in T.CASE_R.items() for R in Rs}
+    assert max(T.EPS.values()) <= 0.1
+    done = 0
+    for (recipe, R), eps in sorted(T.EPS.items()):
+        if R <= 16:
+            worst, _ = T.measure(recipe, R)
+            assert abs(eps - 8 * worst) <= 0.1 * 8 * worst, (recipe, R, eps, 8 * worst)
+            done += 1
+    assert done == 12
+
+
+def test_a_placed_reference_equals_a_stepped_one():
+    """place_at(P, hist) against 300 frames of stepping at R = 2 (the GPU suite places a reference at 2^32 - 2 H, where stepping
+    is out of reach): positions, and the next frames' u before rounding bit for bit, across a retune."""
+    R, n_fed, reps = 2, 20, 15
+    fs = 44100 * R
+    H = 128 * R
+    rng = np.random.default_rng(300)
+    fws = T.edge_words(R) + [0x6789ABCD]
+    a, b = (F.TunerFastconvRef(len(fws), 1, fs, R, g=T.G_ASYM) for _ in range(2))
+    for o in (a, b):
+        T.setup(o, [0] * len(fws), fws)
+        o.set_phase(0xCAFEF00D, ch=3)
+    fed = T.cs16(rng, 1, n_fed * H)
+    for _ in range(reps):
+        a.update(fed)
+    b.place_at(reps * n_fed * H, fed[:, -H:])
+    assert a.P == b.P == 300 * H and a.out_pos == b.out_pos == 300 * 128
+    for k in range(3):
+        if k == 1:
+            for o in (a, b):
+                o.set_frequency_word(0x2468ACE1, ch=4); o.set_phase(0x13579BDF, ch=10)
+        iq = T.cs16(rng, 1, (k + 1) * H)
+        ra, rb = a.update(iq, keep_float=True), b.update(iq, keep_float=True)
+        assert all(np.array_equal(x, y) for x, y in zip(ra, rb))
+        assert a.P == b.P and a.out_pos == b.out_pos
+    assert list(a.pos_a) == list(b.pos_a) and list(a.ph_a) == list(b.ph_a)

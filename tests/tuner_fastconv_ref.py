@@ -100,6 +100,9 @@ class TunerFastconvRef:
         self.g = np.asarray(g, dtype=np.float32).astype(np.float64)
         self.G, self.m = response_table(self.g)
 
+    def get_channel_filter(self):
+        return self.g.astype(np.float32)
+
     def set_resampler(self, h2, g2):
         self.h2, self.g2 = np.asarray(h2, dtype=np.int64), int(g2)
         assert self.h2.size % self.U == 0
@@ -134,27 +137,55 @@ class TunerFastconvRef:
     # stage 1
     def stage1(self, iq):
         """iq: [n_sources][n_frames * H][2].  Returns u before rounding, complex128 [n_channels][n_frames * 128]; advances P."""
+        return self._stage1(iq, np.fft, np.complex128)
+
+    def stage1_f32(self, iq):
+        """stage1() with the arithmetic of the statement held in float32: the window, X, G, the gathered product, the inverse
+        transform, the 1 / N scale and the NCO product are complex64 (scipy.fft keeps complex64; numpy's would promote).  The phase
+        theta stays an exact integer and its phasor is the float64 one rounded to complex64.  A model of what float32 costs the
+        statement -- of no kernel's pass order -- used to size the tests' tolerance."""
+        import scipy.fft
+        return self._stage1(iq, scipy.fft, np.complex64).astype(np.complex128)
+
+    def _stage1(self, iq, fft, ctype):
         iq = np.asarray(iq)                                   # CS16 pairs, or complex samples for known-answer checks
         x = iq.astype(np.complex128) if np.iscomplexobj(iq) else iq[..., 0].astype(np.float64) + 1j * iq[..., 1].astype(np.float64)
         nf = x.shape[1] // self.H
         assert x.shape == (self.n_src, nf * self.H)
         k0, rw = coarse(self.fw, self.R)
-        out = np.zeros((self.n, nf * BLOCK), dtype=np.complex128)
+        out = np.zeros((self.n, nf * BLOCK), dtype=ctype)
         n_keep = np.arange(BLOCK)
+        G = self.G.astype(ctype)
+        scale = (np.float32 if ctype is np.complex64 else np.float64)(256.0 / self.N)
         for f in range(nf):
             b = self.P // self.H
             win = np.concatenate([self.hist, x[:, f * self.H:(f + 1) * self.H]], axis=1)
-            X = np.fft.fft(win, axis=1)
-            Z = X[self.src[:, None], (k0[:, None] + self.m[None, :]) % self.N] * self.G[None, :]
-            y = np.fft.ifft(Z, axis=1)[:, 128:] * (256.0 / self.N)
-            y = y * np.where((k0 * (b - 1)) % 2 == 0, 1.0, -1.0)[:, None]
+            X = fft.fft(win.astype(ctype), axis=1)
+            Z = X[self.src[:, None], (k0[:, None] + self.m[None, :]) % self.N] * G[None, :]
+            y = fft.ifft(Z, axis=1)[:, 128:] * scale
+            y = y * np.where((k0 * (b - 1)) % 2 == 0, 1.0, -1.0)[:, None].astype(ctype)
             i = 128 * b + n_keep
             th = (self.ph_a[:, None] + rw[:, None] * ((i[None, :] * self.R - self.pos_a[:, None]) % (1 << 32))) % (1 << 32)
             th = np.where(th >= 1 << 31, th - (1 << 32), th)
-            out[:, f * BLOCK:(f + 1) * BLOCK] = y * np.exp(-2j * np.pi * th / 4294967296.0)
+            out[:, f * BLOCK:(f + 1) * BLOCK] = y * np.exp(-2j * np.pi * th / 4294967296.0).astype(ctype)
+            assert out.dtype == X.dtype == y.dtype == ctype
             self.hist = win[:, self.H:]
             self.P += self.H
         return out
+
+    def place_at(self, P, hist):
+        """Put a pass-through bank where a run of P input samples per source would have left it, without running it: P (a multiple
+        of H), the output position 128 P / H, the sources' windows hist [n_sources][H] (CS16 pairs or complex: the last H samples
+        fed).  Channels (src, fw, anchors) stay as they are -- an anchor set at position 0 stays (0, ph_a), as it would have.  Stage
+        1 keeps nothing else between frames; a resampling stage 2 would (its u history), hence pass-through only."""
+        assert self.pass_through() and P % self.H == 0 and P >= 0
+        hist = np.asarray(hist)
+        h = hist.astype(np.complex128) if np.iscomplexobj(hist) else hist[..., 0].astype(np.float64) + 1j * hist[..., 1].astype(np.float64)
+        assert h.shape == (self.n_src, self.H)
+        self.P, self.hist = int(P), h
+        self.out_pos = BLOCK * (self.P // self.H)
+        self.u = np.zeros((self.n, 2, 0), dtype=np.int64)
+        self.stale = True
 
     @staticmethod
     def round16(z):
@@ -169,12 +200,13 @@ class TunerFastconvRef:
             return n_frames
         return max(0, RR.blocks_out(self.u.shape[-1] + BLOCK * n_frames, self.U, self.M) - self.out_pos // BLOCK)
 
-    def update(self, iq, keep_float=False):
-        """iq: [n_sources][n_frames * H][2].  Returns (I, Q) int16 [n_channels][blocks written][128] (and u before rounding)."""
+    def update(self, iq, keep_float=False, f32=False):
+        """iq: [n_sources][n_frames * H][2].  Returns (I, Q) int16 [n_channels][blocks written][128] (and u before rounding).
+        f32: stage 1 by stage1_f32()."""
         assert self.h2 is not None, "give the stage-2 taps of a resampling bank"
         nf = np.asarray(iq).shape[1] // self.H
         nb = self.out_blocks(nf)
-        z = self.stage1(iq)
+        z = self.stage1_f32(iq) if f32 else self.stage1(iq)
         I1, Q1 = self.round16(z)
         n_u0 = self.u.shape[-1]
         self.u = np.concatenate([self.u, np.stack([I1, Q1], axis=1)], axis=-1)
