@@ -9,9 +9,12 @@
 
 #define ASDR_TUNER_HIST_SLOTS 1024   /* per-source history row: slot j holds sample P - 1024 + j (slot 0 is never read) */
 
+/* Bytes of one stored sample of an input format (include/asdr_tuner.h, "Input formats"). */
+#define ASDR_TUNER_FMT_BYTES(f) ((f) == ASDR_TUNER_IN_CS16 ? 4 : (f) == ASDR_TUNER_IN_CF32 ? 8 : 2)
+
 typedef struct {
-  const int32_t *in;                /* [n_sources][in_stride] CS16 words (re low, im high) */
-  const int32_t *hist_rd;           /* [n_sources][1024]: the samples before P (read by the mixer) */
+  const int32_t *in;                /* [n_sources][in_stride] samples of format fmt (CS16: words, re low, im high) */
+  const int32_t *hist_rd;           /* [n_sources][1024]: the samples before P (read by the mixer), converted: CS16 words */
   int32_t *hist_wr;                 /* [n_sources][1024]: the samples before P + N (written by the history step) */
   const asdr_tuner_state_t *chan;   /* [n_channels] */
   const int32_t *order;             /* [n_channels]: channels sorted by source (grid x follows it) */
@@ -23,6 +26,7 @@ typedef struct {
   int32_t n_phase_rows;             /* A = ceil(L / D) */
   int32_t n_phase_pairs;            /* DP2 = ceil(D / 2) */
   int32_t shift, round;             /* s = 15 - g, r = s ? 1 << (s - 1) : 0 */
+  int32_t fmt;                      /* ASDR_TUNER_IN_*: picks the kernels' instantiation (the CS16 kernels do not read it) */
 } TunerArgs;
 
 /* Stage 2 of a rate bank (asdr_tuner_resample.hip).  Window coordinates: w = 0 is u sample N_u - ASDR_TUNER_CARRY (N_u before the
@@ -54,8 +58,8 @@ typedef struct {
 #define ASDR_TUNER_FC_CH_LANES 64     /* channel kernel: one wave per (channel, frame), 4 of the 256 points per lane */
 
 typedef struct {
-  const int32_t *in;                /* [n_sources][in_stride] CS16 words (re low, im high) */
-  const int32_t *hist_rd;           /* [n_sources][H]: samples P - H .. P - 1 */
+  const int32_t *in;                /* [n_sources][in_stride] samples of format fmt (CS16: words, re low, im high) */
+  const int32_t *hist_rd;           /* [n_sources][H]: samples P - H .. P - 1, converted: CS16 words */
   int32_t *hist_wr;                 /* [n_sources][H]: samples P + n_frames H - H .. (written by the history step) */
   const float *tw;                  /* [N]: W_N^j = e^{-j 2 pi j / N}; then [256]: W_256^j */
   float *scratch, *x;               /* [n_sources][n_frames][N] each */
@@ -63,6 +67,8 @@ typedef struct {
   int32_t n_sources, n_frames, hop; /* H */
   int32_t log2n, log2n1, log2n2;    /* N = N1 N2 for the four-step passes (N > 4096) */
   int32_t pass;                     /* 0: the whole transform; 1: four-step columns (N1 points); 2: four-step rows (N2 points) */
+  int32_t fmt;                      /* ASDR_TUNER_IN_*.  RS16: the transform has N / 2 points (log2n1 + log2n2 = log2n - 1) and the
+                                       last pass untangles it into the N bins of X */
 } FcForwardArgs;
 
 typedef struct {
@@ -76,6 +82,48 @@ typedef struct {
   int64_t out_stride;               /* output samples */
   int32_t n_channels, n_frames, hop, log2n, decimation;   /* H, log2 N, R */
 } FcChannelArgs;
+
+#ifdef __HIP__
+/* The formats' loads (include/asdr_tuner.h, "Input formats"): sample m >= 0 of a row as the CS16 word of x (xr low, xi high).
+ * Rows start 16-byte aligned, so the 2-byte formats are read as aligned dwords (two samples) and never as bytes or shorts. */
+__device__ inline int32_t asdr_cvt_cs8(uint32_t h) { return (int32_t)(((h & 0xffu) << 8) | ((h & 0xff00u) << 16)); }     /* 256 a */
+__device__ inline int32_t asdr_cvt_cu8(uint32_t h) { return asdr_cvt_cs8(h ^ 0x8080u) | 0x00800080; }   /* 256 (a - 128) + 128 */
+__device__ inline int32_t asdr_cvt_f32(float a) {                       /* sat16(rint(32768 a)), NaN -> 0 */
+  const float v = fminf(fmaxf(a * 32768.0f, -32768.0f), 32767.0f);
+  return a != a ? 0 : (int32_t)rintf(v);
+}
+template <int F>
+__device__ inline int32_t asdr_half_to_word(uint32_t h) {               /* h: the 16 stored bits of a 2-byte sample */
+  return F == ASDR_TUNER_IN_CU8 ? asdr_cvt_cu8(h) : F == ASDR_TUNER_IN_CS8 ? asdr_cvt_cs8(h) : (int32_t)h;   /* RS16: xi = 0 */
+}
+template <int F>
+__device__ inline int32_t asdr_fetch(const void *row, int64_t m) {
+  if constexpr (F == ASDR_TUNER_IN_CS16) {
+    return ((const int32_t *)row)[m];
+  } else if constexpr (F == ASDR_TUNER_IN_CF32) {
+    const float2 v = ((const float2 *)row)[m];
+    return (asdr_cvt_f32(v.x) & 0xffff) | (int32_t)((uint32_t)asdr_cvt_f32(v.y) << 16);
+  } else {
+    const uint32_t d = ((const uint32_t *)row)[m >> 1];
+    return asdr_half_to_word<F>((m & 1) ? d >> 16 : d & 0xffffu);
+  }
+}
+/* samples m (even) and m + 1 in one load: a dword for the 2-byte formats, 8 bytes for CS16, 16 for CF32 */
+template <int F>
+__device__ inline void asdr_fetch2(const void *row, int64_t m, int32_t &w0, int32_t &w1) {
+  if constexpr (ASDR_TUNER_FMT_BYTES(F) == 2) {
+    const uint32_t d = ((const uint32_t *)row)[m >> 1];
+    w0 = asdr_half_to_word<F>(d & 0xffffu); w1 = asdr_half_to_word<F>(d >> 16);
+  } else if constexpr (F == ASDR_TUNER_IN_CF32) {
+    const float4 v = ((const float4 *)row)[m >> 1];
+    w0 = (asdr_cvt_f32(v.x) & 0xffff) | (int32_t)((uint32_t)asdr_cvt_f32(v.y) << 16);
+    w1 = (asdr_cvt_f32(v.z) & 0xffff) | (int32_t)((uint32_t)asdr_cvt_f32(v.w) << 16);
+  } else {
+    const int2 v = ((const int2 *)row)[m >> 1];
+    w0 = v.x; w1 = v.y;
+  }
+}
+#endif
 
 #ifdef __cplusplus
 extern "C" {

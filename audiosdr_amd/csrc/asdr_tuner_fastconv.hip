@@ -13,6 +13,13 @@
 //    q = 2, 3 (n = 128 .. 255, the samples overlap-save keeps) are formed.  Coarse sign, fine NCO (sincospif of (int32) theta
 //    / 2^31), round-half-even and sat16 follow, and the int16 samples go to the caller's rows or the stage-2 intermediate.
 //  * history: the call's last H samples per source into the other history buffer.
+//  * input formats (include/asdr_tuner.h): asdr_tuner_fc_forward_kernel / _history_kernel are the CS16 bank's, as
+//    they were.  asdr_tuner_fc_fmt_forward_kernel<F> / asdr_tuner_fc_fmt_history_kernel<F> convert in the window load (asdr_fetch);
+//    a converted value is an integer of at most 16 bits, exact as a float, and everything after the load is the same code.
+//    RS16: asdr_tuner_fc_real_forward_kernel transforms z[n] = w[2n] + j w[2n + 1] (N / 2 points; a dword of the row IS z[n]) and
+//    untangles, X[k] = (Z[k] + conj Z[N/2 - k]) / 2 - (j / 2) W_N^k (Z[k] - conj Z[N/2 - k]), X[N - k] = conj X[k], into all N
+//    bins in natural order: in LDS before the store for N / 2 <= 2048; above, fused into the four-step row pass, whose workgroup
+//    takes the rows k1 and M1 - k1 (Z[k] and Z[N/2 - k] lie in them) and stores the four mirror images of each pair.
 #include <hip/hip_runtime.h>
 
 #include "asdr_tuner_device.h"
@@ -109,6 +116,121 @@ __global__ __launch_bounds__(ASDR_TUNER_FC_LANES) void asdr_tuner_fc_forward_ker
   }
 }
 
+// asdr_tuner_fc_forward_kernel for a complex format F != CS16, passes 0 and 1 (pass 2 reads no input: the CS16 kernel runs it)
+template <int F>
+__global__ __launch_bounds__(ASDR_TUNER_FC_LANES) void asdr_tuner_fc_fmt_forward_kernel(FcForwardArgs a) {
+  __shared__ float2 buf[ASDR_TUNER_FC_LDS_MAX];
+  const int t = threadIdx.x, unit = blockIdx.x, f = blockIdx.y, s = blockIdx.z;
+  const int H = a.hop, n1 = 1 << a.log2n1;
+  const float2 *tw = (const float2 *)a.tw;
+  const size_t xoff = ((size_t)s * a.n_frames + f) << a.log2n;
+  const int log2m = a.pass == 0 ? a.log2n : a.log2n1;
+  const int m = 1 << log2m;
+  const char *row = (const char *)a.in + (size_t)s * a.in_stride * ASDR_TUNER_FMT_BYTES(F);
+  const int32_t *hrow = a.hist_rd + (size_t)s * H;
+  if (a.pass == 0) {   // window samples 2e, 2e + 1 (input (f - 1) H + 2e of the call: even, so both lie on one side of 0)
+    for (int e = t; e < m / 2; e += ASDR_TUNER_FC_LANES) {
+      const int64_t mm = (int64_t)(f - 1) * H + 2 * e;
+      int2 w;
+      if (mm >= 0) asdr_fetch2<F>(row, mm, w.x, w.y);
+      else w = *(const int2 *)(hrow + H + mm);
+      buf[2 * e] = make_float2((float)(int16_t)(w.x & 0xffff), (float)(w.x >> 16));
+      buf[2 * e + 1] = make_float2((float)(int16_t)(w.y & 0xffff), (float)(w.y >> 16));
+    }
+  } else {             // column n2 = unit: window sample e N2 + n2, one per lane and load (an aligned dword for the 2-byte formats)
+    for (int e = t; e < m; e += ASDR_TUNER_FC_LANES) {
+      const int64_t mm = (int64_t)(f - 1) * H + ((int64_t)e << a.log2n2) + unit;
+      const int32_t word = mm >= 0 ? asdr_fetch<F>(row, mm) : hrow[H + mm];
+      buf[e] = make_float2((float)(int16_t)(word & 0xffff), (float)(word >> 16));
+    }
+  }
+  __syncthreads();
+  lds_fft(buf, log2m, tw, a.log2n);
+  if (a.pass == 0) {
+    float2 *x = (float2 *)a.x + xoff;
+    for (int e = t; e < m; e += ASDR_TUNER_FC_LANES) x[e] = buf[e];
+  } else {
+    float2 *dst = (float2 *)a.scratch + xoff + (size_t)unit * n1;
+    for (int e = t; e < m; e += ASDR_TUNER_FC_LANES) dst[e] = cmul(buf[e], tw[unit * e]);
+  }
+}
+
+namespace {
+// X[k] from Z[k], Z[N/2 - k] and W_N^k
+__device__ inline float2 untangle(float2 zk, float2 zm, float2 w) {
+  const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));   // (Z[k] + conj Z[M - k]) / 2
+  const float2 o = make_float2(0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y));   // (Z[k] - conj Z[M - k]) / 2
+  const float2 p = cmul(w, o);
+  return make_float2(e.x + p.y, e.y - p.x);                                   // e - j p
+}
+// X[k] and its mirror image X[N - k] (k = 0: X[N/2] = Re Z[0] - Im Z[0] instead, the one bin no k < N/2 mirrors to)
+__device__ inline void store_bins(float2 *x, int k, int n, float2 zk, float2 zm, float2 w) {
+  const float2 v = untangle(zk, zm, w);
+  x[k] = v;
+  if (k) x[n - k] = make_float2(v.x, -v.y);
+  else x[n >> 1] = make_float2(zk.x - zk.y, 0.0f);
+}
+}  // namespace
+
+// The forward step of an RS16 bank: M = N / 2 = 2^(log2n - 1) complex points z[n] = w[2n] + j w[2n + 1], M = M1 M2 (log2n1, log2n2)
+// for the four-step passes.  pass 0: the whole transform and the untangle in LDS (M <= 2048).  pass 1: column n2 = unit (M1 points),
+// times W_M^{n2 k1} = W_N^{2 n2 k1}, into the scratch.  pass 2: rows k1 = unit and M1 - unit (unit = 0 .. M1 / 2) and the untangle.
+__global__ __launch_bounds__(ASDR_TUNER_FC_LANES) void asdr_tuner_fc_real_forward_kernel(FcForwardArgs a) {
+  __shared__ float2 buf[ASDR_TUNER_FC_LDS_MAX];
+  const int t = threadIdx.x, unit = blockIdx.x, f = blockIdx.y, s = blockIdx.z;
+  const int H = a.hop, N = 1 << a.log2n, m1 = 1 << a.log2n1, m2 = 1 << a.log2n2;
+  const float2 *tw = (const float2 *)a.tw;
+  const size_t xoff = ((size_t)s * a.n_frames + f) << a.log2n;
+  float2 *x = (float2 *)a.x + xoff;
+  if (a.pass != 2) {   // z[n], n = e (whole) or e M2 + n2: real samples (f - 1) H + 2n, + 1 of the call -- one dword of the row
+    const int m = a.pass == 0 ? N >> 1 : m1;
+    const int stride = a.pass == 0 ? 1 : m2, off = a.pass == 0 ? 0 : unit;
+    const int32_t *row = (const int32_t *)((const char *)a.in + (size_t)s * a.in_stride * 2);
+    const int32_t *hrow = a.hist_rd + (size_t)s * H;
+    for (int e = t; e < m; e += ASDR_TUNER_FC_LANES) {
+      const int64_t mm = (int64_t)(f - 1) * H + 2 * ((int64_t)e * stride + off);
+      if (mm >= 0) {
+        const int32_t word = row[mm >> 1];
+        buf[e] = make_float2((float)(int16_t)(word & 0xffff), (float)(word >> 16));
+      } else {         // converted words (xr, 0)
+        const int2 w = *(const int2 *)(hrow + H + mm);
+        buf[e] = make_float2((float)(int16_t)(w.x & 0xffff), (float)(int16_t)(w.y & 0xffff));
+      }
+    }
+    __syncthreads();
+    lds_fft(buf, a.pass == 0 ? a.log2n - 1 : a.log2n1, tw, a.log2n);
+    if (a.pass == 0) {
+      for (int k = t; k < m; k += ASDR_TUNER_FC_LANES) store_bins(x, k, N, buf[k], buf[(m - k) & (m - 1)], tw[k]);
+    } else {
+      float2 *dst = (float2 *)a.scratch + xoff + (size_t)unit * m1;
+      for (int e = t; e < m; e += ASDR_TUNER_FC_LANES) dst[e] = cmul(buf[e], tw[2 * unit * e]);
+    }
+    return;
+  }
+  // pass 2: A = row k1 = unit (Z[k1 + M1 k2] at buf[k2]), B = row M1 - k1 (at buf[M2 + k2]); rows 0 and M1 / 2 pair with themselves
+  const float2 *src = (const float2 *)a.scratch + xoff;
+  const int kb = (m1 - unit) & (m1 - 1);
+  const bool self = kb == unit;
+  for (int e = t; e < m2; e += ASDR_TUNER_FC_LANES) {
+    buf[e] = src[((size_t)e << a.log2n1) + unit];
+    if (!self) buf[m2 + e] = src[((size_t)e << a.log2n1) + kb];
+  }
+  __syncthreads();
+  lds_fft(buf, a.log2n2, tw, a.log2n);
+  if (!self) lds_fft(buf + m2, a.log2n2, tw, a.log2n);
+  // partner of k = k1 + M1 k2 is M - k = (M1 - k1) + M1 (M2 - 1 - k2) for k1 >= 1, and M1 ((M2 - k2) mod M2) for k1 = 0
+  const float2 *zb = self ? buf : buf + m2;
+  for (int e = t; e < m2; e += ASDR_TUNER_FC_LANES) {
+    const int pe = unit == 0 ? (m2 - e) & (m2 - 1) : m2 - 1 - e;
+    const int k = unit + (e << a.log2n1);
+    store_bins(x, k, N, buf[e], zb[pe], tw[k]);
+    if (!self) {
+      const int k2 = kb + (e << a.log2n1);
+      store_bins(x, k2, N, zb[e], buf[pe], tw[k2]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(ASDR_TUNER_FC_CH_LANES) void asdr_tuner_fc_channel_kernel(FcChannelArgs a) {
   __shared__ float2 buf[256];
   const int t = threadIdx.x;
@@ -177,8 +299,74 @@ __global__ __launch_bounds__(256) void asdr_tuner_fc_history_kernel(FcForwardArg
   a.hist_wr[(size_t)s * a.hop + j] = a.in[(size_t)s * a.in_stride + (int64_t)(a.n_frames - 1) * a.hop + j];
 }
 
+// history for a bank of format F != CS16: lane = slots 2j, 2j + 1, converted and written as one 8-byte store
+template <int F>
+__global__ __launch_bounds__(256) void asdr_tuner_fc_fmt_history_kernel(FcForwardArgs a) {
+  const int s = blockIdx.y, j = 2 * (blockIdx.x * 256 + threadIdx.x);
+  if (j >= a.hop) return;
+  const char *row = (const char *)a.in + (size_t)s * a.in_stride * ASDR_TUNER_FMT_BYTES(F);
+  int2 w;
+  asdr_fetch2<F>(row, (int64_t)(a.n_frames - 1) * a.hop + j, w.x, w.y);
+  *(int2 *)(a.hist_wr + (size_t)s * a.hop + j) = w;
+}
+
+namespace {
+// the forward and history steps of a complex format F != CS16 (the channel step between them is the caller's)
+template <int F>
+int launch_fmt_forward(const FcForwardArgs *f, hipStream_t stream) {
+  if (f->pass == 0) {
+    hipLaunchKernelGGL(asdr_tuner_fc_fmt_forward_kernel<F>, dim3(1, f->n_frames, f->n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, *f);
+  } else {
+    FcForwardArgs p = *f;
+    p.pass = 1;
+    hipLaunchKernelGGL(asdr_tuner_fc_fmt_forward_kernel<F>, dim3(1 << p.log2n2, p.n_frames, p.n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, p);
+    if (hipGetLastError() != hipSuccess) return -1;
+    p.pass = 2;
+    hipLaunchKernelGGL(asdr_tuner_fc_forward_kernel, dim3(1 << p.log2n1, p.n_frames, p.n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, p);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+template <int F>
+int launch_fmt_history(const FcForwardArgs *f, hipStream_t stream) {
+  hipLaunchKernelGGL(asdr_tuner_fc_fmt_history_kernel<F>, dim3((f->hop / 2 + 255) / 256, f->n_sources), dim3(256), 0, stream, *f);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int launch_real_forward(const FcForwardArgs *f, hipStream_t stream) {
+  if (f->pass == 0) {
+    hipLaunchKernelGGL(asdr_tuner_fc_real_forward_kernel, dim3(1, f->n_frames, f->n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, *f);
+  } else {
+    FcForwardArgs p = *f;
+    p.pass = 1;
+    hipLaunchKernelGGL(asdr_tuner_fc_real_forward_kernel, dim3(1 << p.log2n2, p.n_frames, p.n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, p);
+    if (hipGetLastError() != hipSuccess) return -1;
+    p.pass = 2;
+    hipLaunchKernelGGL(asdr_tuner_fc_real_forward_kernel, dim3((1 << p.log2n1) / 2 + 1, p.n_frames, p.n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, p);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+}  // namespace
+
 extern "C" int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  if (f->fmt != ASDR_TUNER_IN_CS16) {
+    int rc;
+    switch (f->fmt) {
+      case ASDR_TUNER_IN_CU8: rc = launch_fmt_forward<ASDR_TUNER_IN_CU8>(f, stream); break;
+      case ASDR_TUNER_IN_CS8: rc = launch_fmt_forward<ASDR_TUNER_IN_CS8>(f, stream); break;
+      case ASDR_TUNER_IN_CF32: rc = launch_fmt_forward<ASDR_TUNER_IN_CF32>(f, stream); break;
+      case ASDR_TUNER_IN_RS16: rc = launch_real_forward(f, stream); break;
+      default: rc = -1;
+    }
+    if (rc != 0) return -1;
+    hipLaunchKernelGGL(asdr_tuner_fc_channel_kernel, dim3(c->n_channels, c->n_frames), dim3(ASDR_TUNER_FC_CH_LANES), 0, stream, *c);
+    if (hipGetLastError() != hipSuccess) return -1;
+    switch (f->fmt) {
+      case ASDR_TUNER_IN_CU8: return launch_fmt_history<ASDR_TUNER_IN_CU8>(f, stream);
+      case ASDR_TUNER_IN_CS8: return launch_fmt_history<ASDR_TUNER_IN_CS8>(f, stream);
+      case ASDR_TUNER_IN_CF32: return launch_fmt_history<ASDR_TUNER_IN_CF32>(f, stream);
+      default: return launch_fmt_history<ASDR_TUNER_IN_RS16>(f, stream);
+    }
+  }
   if (f->pass == 0) {
     hipLaunchKernelGGL(asdr_tuner_fc_forward_kernel, dim3(1, f->n_frames, f->n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, *f);
   } else {

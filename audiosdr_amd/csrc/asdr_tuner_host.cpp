@@ -23,6 +23,7 @@ int fail(const std::string &m) { return asdr_internal_fail(m); }
     if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
   } while (0)
 
+const char *kFormatNames[] = {"CS16", "CU8", "CS8", "CF32", "RS16"};
 const char *kNoDevice = "control-plane-only tuner bank (ASDR_NO_DEVICE): the signal path needs a HIP device";
 constexpr int kTapWords = 1088;   // >= ceil(L / D) * ceil(D / 2) for every D <= 64, L <= 1024 (the largest is 1024, D = 1)
 
@@ -141,6 +142,7 @@ std::string resampler_error(int U, const int16_t *h2, int n_taps, int g2) {
 
 struct asdr_tuner_bank {
   int n = 0, n_src = 0, D = 1, device = ASDR_NO_DEVICE;
+  int fmt = ASDR_TUNER_IN_CS16;       // input format of the next call's rows
   long long pos = 0;
   // rate bank (stage 2): Fs_in, U / M, the prototype [U K] and g2, output samples written
   long long fs_in = 44100;
@@ -309,7 +311,7 @@ int push_resampler(asdr_tuner_t *t, hipStream_t stream) {
 }
 
 // A fast-convolution bank's stage 1 (asdr_tuner_fastconv.hip): n_frames frames of every channel into rows out_stride_blocks apart.
-int run_fastconv(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_frames,
+int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_frames,
                  long out_stride_blocks, hipStream_t stream) {
   const int log2n = t->log2n, N = 1 << log2n, H = N / 2;
   const size_t x_floats = (size_t)t->n_src * n_frames * N * 2;
@@ -325,8 +327,10 @@ int run_fastconv(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, in
   f.in = (const int32_t *)dIQ; f.hist_rd = t->d_hist[t->cur]; f.hist_wr = t->d_hist[t->cur ^ 1];
   f.tw = t->d_fc_tab; f.x = t->d_fc_x; f.scratch = t->d_fc_x + x_floats;
   f.in_stride = in_stride_samples; f.n_sources = t->n_src; f.n_frames = n_frames; f.hop = H;
-  f.log2n = log2n; f.log2n1 = (log2n + 1) / 2; f.log2n2 = log2n - f.log2n1;
+  const int log2t = t->fmt == ASDR_TUNER_IN_RS16 ? log2n - 1 : log2n;   // RS16: a transform of N / 2 points, then the untangle
+  f.log2n = log2n; f.log2n1 = (log2t + 1) / 2; f.log2n2 = log2t - f.log2n1;
   f.pass = log2n > 12 ? 1 : 0;
+  f.fmt = t->fmt;
   FcChannelArgs c;
   c.x = t->d_fc_x; c.tw256 = t->d_fc_tab + 2 * N; c.g = t->d_fc_tab + 2 * (N + 256);
   c.chan = t->d_chan; c.order = t->d_order; c.out_i = dI; c.out_q = dQ;
@@ -339,7 +343,7 @@ int run_fastconv(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, in
 }
 
 // The stage-1 launch of a call: n_blocks blocks of every channel into rows out_stride_blocks apart, then P advances.
-int run_stage1(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
+int run_stage1(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
                long out_stride_blocks, hipStream_t stream) {
   if (t->fc) return run_fastconv(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream);
   TunerArgs a;
@@ -349,6 +353,7 @@ int run_stage1(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int1
   a.n_channels = t->n; a.n_sources = t->n_src; a.n_blocks = n_blocks; a.decimation = t->D;
   a.n_phase_rows = t->n_rows; a.n_phase_pairs = t->n_pairs;
   a.shift = 15 - t->g; a.round = a.shift ? 1 << (a.shift - 1) : 0;
+  a.fmt = t->fmt;
   if (asdr_launch_tuner(&a, stream) != 0) return fail("tuner kernel launch failed");
   t->pos += (long long)n_blocks * 128 * t->D;
   t->cur ^= 1;
@@ -356,7 +361,7 @@ int run_stage1(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int1
 }
 
 // The argument checks shared by the update entry points (n_blocks = stage-1 blocks = frames, out_blocks = output row length).
-int check_io(const asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, const int16_t *dI, const int16_t *dQ, int n_blocks,
+int check_io(const asdr_tuner_t *t, const void *dIQ, long in_stride_samples, const int16_t *dI, const int16_t *dQ, int n_blocks,
              long out_stride_blocks, long out_blocks) {
   if (n_blocks > 65535 || (long long)n_blocks * 128 * t->D > (1LL << 30)) return fail("too many blocks in one call");
   const long long n_in = (long long)n_blocks * 128 * t->D;
@@ -364,7 +369,7 @@ int check_io(const asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, 
   if (out_stride_blocks < out_blocks) return fail("output row stride shorter than n_blocks");
   if (in_stride_samples > (1LL << 40) || out_stride_blocks > (1LL << 30)) return fail("row stride too large");
   if ((((uintptr_t)dIQ | (uintptr_t)dI | (uintptr_t)dQ) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
-  const size_t in_bytes = ((size_t)(t->n_src - 1) * in_stride_samples + n_in) * 4;
+  const size_t in_bytes = ((size_t)(t->n_src - 1) * in_stride_samples + n_in) * ASDR_TUNER_FMT_BYTES(t->fmt);
   const size_t out_bytes = ((size_t)(t->n - 1) * out_stride_blocks + out_blocks) * 128 * 2;
   if (overlap((uintptr_t)dI, out_bytes, (uintptr_t)dIQ, in_bytes) || overlap((uintptr_t)dQ, out_bytes, (uintptr_t)dIQ, in_bytes))
     return fail("output span overlaps the input span");
@@ -449,6 +454,20 @@ asdr_tuner_t *create_fastconv(int n_channels, int n_sources, long long fs_in, in
   t->k2 = (int)t->h2.size() / t->up;
   return open_device(t);
 }
+
+// the int16 entry points on a bank of another format: fail before anything is read
+bool wrong_format(const asdr_tuner_t *t, const char *entry) {
+  if (t->fmt == ASDR_TUNER_IN_CS16) return false;
+  fail(std::string(entry) + " takes CS16 rows and this bank's input format is " + kFormatNames[t->fmt] +
+       ": use asdr_tuner_update_samples_device / asdr_tuner_update_samples");
+  return true;
+}
+
+int pass_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
+                long out_stride_blocks, void *stream_);
+int rate_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int n_frames, int16_t *dI, int16_t *dQ,
+                int out_capacity_blocks, long out_stride_blocks, void *stream_);
+int rate_host(asdr_tuner_t *t, const void *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks);
 }  // namespace
 
 extern "C" {
@@ -581,6 +600,16 @@ int asdr_tuner_read_state(const asdr_tuner_t *t, asdr_tuner_state_t *dst) {
 int asdr_tuner_update_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
                              long out_stride_blocks, void *stream_) {
   if (!t) return fail("null tuner bank");
+  if (wrong_format(t, "asdr_tuner_update_device")) return -1;
+  return pass_device(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream_);
+}
+
+}  // extern "C"
+
+namespace {
+// asdr_tuner_update_device on rows of the bank's format
+int pass_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
+                long out_stride_blocks, void *stream_) {
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
   if (!pass_through(t)) return fail("stage 2 of this bank resamples: use asdr_tuner_update_rate_device / asdr_tuner_update_rate");
   if (!dIQ || !dI || !dQ) return fail("null device pointer");
@@ -598,9 +627,13 @@ int asdr_tuner_update_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride
   t->carry_stale = true;                      // and keeps no history
   return 0;
 }
+}  // namespace
+
+extern "C" {
 
 int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q, int n_blocks) {
   if (!t) return fail("null tuner bank");
+  if (wrong_format(t, "asdr_tuner_update")) return -1;
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
   if (!pass_through(t)) return fail("stage 2 of this bank resamples: use asdr_tuner_update_rate_device / asdr_tuner_update_rate");
   if (!IQ || !I || !Q) return fail("null host pointer");
@@ -665,6 +698,48 @@ int asdr_tuner_out_blocks(const asdr_tuner_t *t, int n_frames) {
 int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_stride_samples, int n_frames, int16_t *dI,
                                   int16_t *dQ, int out_capacity_blocks, long out_stride_blocks, void *stream_) {
   if (!t) return fail("null tuner bank");
+  if (wrong_format(t, "asdr_tuner_update_rate_device")) return -1;
+  return rate_device(t, dIQ, in_stride_samples, n_frames, dI, dQ, out_capacity_blocks, out_stride_blocks, stream_);
+}
+
+int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks) {
+  if (!t) return fail("null tuner bank");
+  if (wrong_format(t, "asdr_tuner_update_rate")) return -1;
+  return rate_host(t, IQ, n_frames, I, Q, out_capacity_blocks);
+}
+
+int asdr_tuner_set_input_format(asdr_tuner_t *t, int format) {
+  if (!t) return fail("null tuner bank");
+  if (format < ASDR_TUNER_IN_CS16 || format > ASDR_TUNER_IN_RS16) return fail("unknown input format (ASDR_TUNER_IN_CS16 .. ASDR_TUNER_IN_RS16)");
+  t->fmt = format;
+  return 0;
+}
+
+int asdr_tuner_input_format(const asdr_tuner_t *t) { return t ? t->fmt : -1; }
+
+int asdr_tuner_update_samples_device(asdr_tuner_t *t, const void *dIn, long in_stride_samples, int n_frames, int16_t *dI, int16_t *dQ,
+                                     int out_capacity_blocks, long out_stride_blocks, void *stream_) {
+  if (!t) return fail("null tuner bank");
+  const long long bps = ASDR_TUNER_FMT_BYTES(t->fmt);
+  if (!dIn || !dI || !dQ) return fail("null device pointer");
+  if (in_stride_samples < 0) return fail("input row stride is negative");
+  if (((uintptr_t)dIn & 15u) != 0 || ((unsigned long long)in_stride_samples * bps) % 16 != 0)
+    return fail(std::string("input rows must start 16-byte aligned: the base pointer, and the row stride a multiple of ") +
+                std::to_string(16 / bps) + " " + kFormatNames[t->fmt] + " samples");
+  return rate_device(t, dIn, in_stride_samples, n_frames, dI, dQ, out_capacity_blocks, out_stride_blocks, stream_);
+}
+
+int asdr_tuner_update_samples(asdr_tuner_t *t, const void *In, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks) {
+  if (!t) return fail("null tuner bank");
+  return rate_host(t, In, n_frames, I, Q, out_capacity_blocks);
+}
+
+}  // extern "C"
+
+namespace {
+// asdr_tuner_update_rate_device on rows of the bank's format
+int rate_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int n_frames, int16_t *dI, int16_t *dQ,
+                int out_capacity_blocks, long out_stride_blocks, void *stream_) {
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
   if (!dIQ || !dI || !dQ) return fail("null device pointer");
   if (n_frames < 0 || n_frames > 65535) return fail("n_frames must be in 0..65535");
@@ -675,7 +750,7 @@ int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_s
   if (out_stride_blocks < out_capacity_blocks) return fail("output row stride shorter than the output capacity");
   if (check_io(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, out_capacity_blocks) != 0) return -1;
   if (pass_through(t))
-    return asdr_tuner_update_device(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, stream_) == 0 ? n_frames : -1;
+    return pass_device(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, stream_) == 0 ? n_frames : -1;
   hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(t->device));
   const size_t row = (size_t)n_frames * 128, mid_bytes = 2 * (size_t)t->n * row * sizeof(int16_t);
@@ -727,8 +802,8 @@ int asdr_tuner_update_rate_device(asdr_tuner_t *t, const int16_t *dIQ, long in_s
   return (int)nb;
 }
 
-int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks) {
-  if (!t) return fail("null tuner bank");
+// asdr_tuner_update_rate on rows of the bank's format
+int rate_host(asdr_tuner_t *t, const void *IQ, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks) {
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
   if (!IQ || !I || !Q) return fail("null host pointer");
   if (n_frames < 0 || n_frames > 65535) return fail("n_frames must be in 0..65535");
@@ -736,7 +811,7 @@ int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int
   const long long nb = blocks_after(t, n_frames);
   if (nb > out_capacity_blocks)
     return fail("output capacity of " + std::to_string(out_capacity_blocks) + " blocks: this call writes " + std::to_string(nb));
-  const size_t n_in = (size_t)n_frames * 128 * t->D, in_bytes = (size_t)t->n_src * n_in * 4;
+  const size_t n_in = (size_t)n_frames * 128 * t->D, in_bytes = (size_t)t->n_src * n_in * ASDR_TUNER_FMT_BYTES(t->fmt);
   const size_t out_bytes = (size_t)t->n * nb * 128 * 2, in_pad = (in_bytes + 255) & ~(size_t)255;
   HIPCHK(hipSetDevice(t->device));
   if (in_pad + 2 * out_bytes > t->io_cap) {
@@ -749,7 +824,7 @@ int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int
   char *base = (char *)t->d_io;
   int16_t *dI = (int16_t *)(base + in_pad), *dQ = (int16_t *)(base + in_pad + out_bytes);
   HIPCHK(hipMemcpyAsync(base, IQ, in_bytes, hipMemcpyHostToDevice, t->stream));
-  const int got = asdr_tuner_update_rate_device(t, (const int16_t *)base, (long)n_in, n_frames, dI, dQ, (int)nb, (long)nb, t->stream);
+  const int got = rate_device(t, base, (long)n_in, n_frames, dI, dQ, (int)nb, (long)nb, t->stream);
   if (got < 0) return -1;
   if (out_bytes) {
     HIPCHK(hipMemcpyAsync(I, dI, out_bytes, hipMemcpyDeviceToHost, t->stream));
@@ -758,6 +833,9 @@ int asdr_tuner_update_rate(asdr_tuner_t *t, const int16_t *IQ, int n_frames, int
   HIPCHK(hipStreamSynchronize(t->stream));
   return got;
 }
+}  // namespace
+
+extern "C" {
 
 int asdr_tuner_synchronize(asdr_tuner_t *t) {
   if (!t) return fail("null tuner bank");

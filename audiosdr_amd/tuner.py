@@ -1,5 +1,5 @@
 """ctypes mirror of include/asdr_tuner.h: the digital tuner bank (per-receiver digital LO + decimating low-pass) that feeds
-the chain's I/Q rows from shared wideband CS16 sources.  Same rules as binding.py: the work happens in libasdr_hip.so on the GPU;
+the chain's I/Q rows from shared wideband sources (CS16 by default; CU8, CS8, CF32 and real int16 by set_input_format).  Same rules as binding.py: the work happens in libasdr_hip.so on the GPU;
 there is no CPU fallback (tests/tuner_ref.py is the independent numpy statement the tests compare with)."""
 import ctypes as C
 
@@ -14,11 +14,15 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_last_kernel_ms", "asdr_tuner_create_rate", "asdr_tuner_rate", "asdr_tuner_ratio",
                  "asdr_tuner_output_position", "asdr_tuner_set_resampler", "asdr_tuner_get_resampler", "asdr_tuner_out_blocks",
                  "asdr_tuner_update_rate_device", "asdr_tuner_update_rate", "asdr_tuner_create_fastconv", "asdr_tuner_fft_size",
-                 "asdr_tuner_set_channel_filter", "asdr_tuner_get_channel_filter"]
+                 "asdr_tuner_set_channel_filter", "asdr_tuner_get_channel_filter", "asdr_tuner_set_input_format",
+                 "asdr_tuner_input_format", "asdr_tuner_update_samples_device", "asdr_tuner_update_samples"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
 MAX_CHANNEL_TAPS = 129
+# input formats (include/asdr_tuner.h, "Input formats"): name -> (ASDR_TUNER_IN_*, numpy dtype, values per stored sample)
+INPUT_FORMATS = {"cs16": (0, np.int16, 2), "cu8": (1, np.uint8, 2), "cs8": (2, np.int8, 2), "cf32": (3, np.float32, 2),
+                 "rs16": (4, np.int16, 1)}
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
@@ -62,6 +66,10 @@ def _lib():
     L.asdr_tuner_fft_size.argtypes = [vp]; L.asdr_tuner_fft_size.restype = i
     L.asdr_tuner_set_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_set_channel_filter.restype = i
     L.asdr_tuner_get_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_get_channel_filter.restype = i
+    L.asdr_tuner_set_input_format.argtypes = [vp, i]; L.asdr_tuner_set_input_format.restype = i
+    L.asdr_tuner_input_format.argtypes = [vp]; L.asdr_tuner_input_format.restype = i
+    L.asdr_tuner_update_samples_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_samples_device.restype = i
+    L.asdr_tuner_update_samples.argtypes = [vp, vp, i, i16p, i16p, i]; L.asdr_tuner_update_samples.restype = i
     _typed = True
     return L
 
@@ -270,6 +278,53 @@ class TunerBank:
         ins = in_stride_samples or n_frames * BLOCK * self.decimation
         return self._chk(self._L.asdr_tuner_update_rate_device(
             self._h, C.c_void_p(dIQ), int(ins), int(n_frames), C.c_void_p(dI), C.c_void_p(dQ), int(out_capacity_blocks),
+            int(out_stride_blocks or out_capacity_blocks), C.c_void_p(stream)))
+
+    def set_input_format(self, fmt):
+        """fmt: "cs16" (the default), "cu8", "cs8", "cf32" or "rs16" (include/asdr_tuner.h, "Input formats"), or an ASDR_TUNER_IN_*
+        value.  Applies to the rows of the next call."""
+        if isinstance(fmt, str):
+            if fmt.lower() not in INPUT_FORMATS:
+                raise AsdrError("unknown input format %r (one of %s)" % (fmt, " ".join(INPUT_FORMATS)))
+            fmt = INPUT_FORMATS[fmt.lower()][0]
+        self._chk(self._L.asdr_tuner_set_input_format(self._h, int(fmt)))
+
+    def input_format(self):
+        """The bank's format by name."""
+        v = int(self._L.asdr_tuner_input_format(self._h))
+        for k, f in INPUT_FORMATS.items():
+            if f[0] == v:
+                return k
+        raise AsdrError("asdr_tuner_input_format returned %d (a closed bank?)" % v)
+
+    def update_samples(self, x):
+        """x: rows in the bank's format on the host, [n_sources][n_frames * 128 * D][2] of dtype int16 (cs16), uint8 (cu8), int8
+        (cs8) or float32 (cf32), or [n_sources][n_frames * 128 * D] int16 (rs16).  dtype and shape must be the format's: nothing is
+        converted here.  Returns what update_rate returns."""
+        name = self.input_format()
+        _, dtype, parts = INPUT_FORMATS[name]
+        if not isinstance(x, np.ndarray) or x.dtype != np.dtype(dtype):
+            raise AsdrError("update_samples: a %s bank takes a numpy array of dtype %s, not %s" % (
+                name, np.dtype(dtype).name, getattr(x, "dtype", type(x).__name__)))
+        per = BLOCK * self.decimation
+        want = (self.n_sources, "n_frames * %d" % per) + ((2,) if parts == 2 else ())
+        if x.ndim != len(want) or x.shape[0] != self.n_sources or x.shape[1] % per != 0 or (parts == 2 and x.shape[2] != 2):
+            raise AsdrError("update_samples: a %s bank takes rows of shape %s, not %s" % (name, list(want), list(x.shape)))
+        x = np.ascontiguousarray(x)
+        nf = x.shape[1] // per
+        nb = self.out_blocks(nf)
+        I = np.empty((self.n_channels, max(nb, 1), BLOCK), dtype=np.int16)
+        Q = np.empty_like(I)
+        got = self._chk(self._L.asdr_tuner_update_samples(self._h, x.ctypes.data_as(C.c_void_p), nf, _p16(I), _p16(Q), nb))
+        assert got == nb, (got, nb)
+        return I[:, :nb], Q[:, :nb]
+
+    def update_samples_device(self, dIn, dI, dQ, n_frames, out_capacity_blocks, in_stride_samples=None, out_stride_blocks=None, stream=0):
+        """update_rate_device with rows of the bank's format at dIn: row starts 16-byte aligned (the pointer, and in_stride_samples
+        times the format's bytes per sample a multiple of 16).  Returns the number of blocks written to each row."""
+        ins = in_stride_samples or n_frames * BLOCK * self.decimation
+        return self._chk(self._L.asdr_tuner_update_samples_device(
+            self._h, C.c_void_p(dIn), int(ins), int(n_frames), C.c_void_p(dI), C.c_void_p(dQ), int(out_capacity_blocks),
             int(out_stride_blocks or out_capacity_blocks), C.c_void_p(stream)))
 
     def synchronize(self):

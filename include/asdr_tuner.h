@@ -75,6 +75,24 @@
  *             K = 2 ceil(6 Fs_in / (44100 R)), cut-off 21.65 kHz at U Fs_mid.
  *   ABI       every other function works as for rate banks, except set_filter / get_filter, which fail (use
  *             set_channel_filter / get_channel_filter), and update(_device), which need a pass-through stage 2.
+ *
+ * Input formats (asdr_tuner_set_input_format): a format says how one input sample is stored and how it becomes the x = (xr, xi)
+ * (two int16) that every statement above starts from.  Everything after x is unchanged.
+ *   format                            stored as       bytes / sample   x
+ *   ASDR_TUNER_IN_CS16 = 0 (default)  int16 re, im    4                as stored
+ *   ASDR_TUNER_IN_CU8                 uint8 re, im    2                256 a - 32640 per part ( = 128 (2 a - 255), the usual a - 127.5
+ *                                                                      convention; range +-32640)
+ *   ASDR_TUNER_IN_CS8                 int8 re, im     2                256 a per part
+ *   ASDR_TUNER_IN_CF32                float re, im    8                sat16(rint(32768 a)) per part, round half to even, NaN -> 0,
+ *                                                                      +-inf saturate (the product is exact, so this is one rounding)
+ *   ASDR_TUNER_IN_RS16                int16, real     2                xr = a, xi = 0
+ * A "sample" in in_stride_samples, in frame sizes (128 D, H = 128 R) and in P is one stored sample of the format (one pair, or one
+ * real value).  The format applies to the rows of the next call; the history rows / windows kept across calls hold converted
+ * samples (x), so a change of format between two calls is well defined by the above and needs no flush.  reset keeps the format.
+ * The conversion happens in the loads of the kernels that read the caller's rows.  A fast-convolution bank
+ * computes X of an RS16 window by a transform of N / 2 complex points on z[n] = w[2n] + j w[2n + 1] and the untangling step
+ * X[k] = (Z[k] + conj Z[N/2 - k]) / 2 - (j / 2) W_N^k (Z[k] - conj Z[N/2 - k]), X[N - k] = conj X[k]: the same X in exact
+ * arithmetic, so the statement of X above holds as it stands.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -95,6 +113,11 @@ extern "C" {
 #define ASDR_TUNER_MAX_RESAMPLER_TAPS 64 /* K, taps per phase */
 #define ASDR_TUNER_FC_MAX_R 1024
 #define ASDR_TUNER_FC_MAX_TAPS 129       /* Lg, channel filter taps of a fast-convolution bank */
+#define ASDR_TUNER_IN_CS16 0             /* input formats (the table above) */
+#define ASDR_TUNER_IN_CU8 1
+#define ASDR_TUNER_IN_CS8 2
+#define ASDR_TUNER_IN_CF32 3
+#define ASDR_TUNER_IN_RS16 4
 
 typedef struct asdr_tuner_bank asdr_tuner_t;
 
@@ -168,6 +191,20 @@ int asdr_tuner_fft_size(const asdr_tuner_t *t);   /* N, or 0 for a direct-form b
 int asdr_tuner_set_channel_filter(asdr_tuner_t *t, const float *g, int n_taps);
 /* Copies min(Lg, cap) taps to g (if not NULL); returns Lg (fails on a direct-form bank). */
 int asdr_tuner_get_channel_filter(const asdr_tuner_t *t, float *g, int cap);
+
+/* Input formats (every bank kind, ASDR_NO_DEVICE banks included).  set: 0 / -1; an unknown value is rejected and the old format
+ * kept.  It may be called between any two update calls and applies to the rows of the next one. */
+int asdr_tuner_set_input_format(asdr_tuner_t *t, int format);
+int asdr_tuner_input_format(const asdr_tuner_t *t);   /* ASDR_TUNER_IN_*, -1 for a NULL bank */
+/* The hot path in the bank's format: the contract of asdr_tuner_update_rate_device / asdr_tuner_update_rate (all three bank kinds,
+ * returns the blocks written, the same stream rule and the same cases that fail with no work done), with rows of n_frames * 128 * D
+ * stored samples of the bank's format.  Row starts must be 16-byte aligned: the base pointer, and in_stride_samples times the
+ * format's bytes per sample a multiple of 16; otherwise the call fails with no work done.
+ * The four int16 update entry points above keep working on CS16 banks and fail, with the state unchanged, on a bank of another
+ * format (asdr_last_error names it): an int16 pointer is never read as bytes or floats. */
+int asdr_tuner_update_samples_device(asdr_tuner_t *t, const void *dIn, long in_stride_samples, int n_frames, int16_t *dI, int16_t *dQ,
+                                     int out_capacity_blocks, long out_stride_blocks, void *stream);
+int asdr_tuner_update_samples(asdr_tuner_t *t, const void *In, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks);
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */

@@ -13,6 +13,11 @@
   F4+chain  F4 followed by asdr_update_device (USB) on the same stream
   F20       fast-convolution bank: 16 sources at 20 MS/s, R = 128 (N = 32,768; 882 / 3125), 65,536 channels, 16 frames per call
   F61       fast-convolution bank: 4 sources at 61.44 MS/s, R = 512 (N = 131,072; 147 / 400), 16,384 channels, 16 frames per call
+  F4u8      F4 with CU8 rows (RTL-SDR bytes; include/asdr_tuner.h, "Input formats")
+  F20s8     F20 with CS8 rows (HackRF bytes)
+  R64       skimmer on a direct-sampling receiver: 1 source of real int16 (RS16) at 64.8 MS/s, R = 512 (N = 131,072; Fs_mid =
+            126.5625 kHz, 392 / 1125), 512 channels, 16 frames per call
+  R64z      R64's signal as CS16 with zero Q (what such a source had to be blown up to before), for comparison
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
@@ -22,7 +27,7 @@ time per call over call time.  The first call of each config is checked against 
 channels.  Fast-convolution banks (F*) have no operation model here (DESIGN.md 3.8.2 counts them); their first call is checked
 against tests/tuner_fastconv_ref.py, a float64 statement, so "parity" there means every sample within +-2.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z]
 """
 import json
 import os
@@ -37,6 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import audiosdr_amd as A  # noqa: E402
 import tuner_fastconv_ref as FR  # noqa: E402
+import tuner_formats_ref as FM  # noqa: E402
 import tuner_rate_ref as RR  # noqa: E402
 import tuner_ref as R  # noqa: E402
 
@@ -55,13 +61,19 @@ CONFIGS = {
     "F4+chain": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, chain=True, fs_in=2400000, fastconv=True),
     "F20": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True),
     "F61": dict(n_src=4, D=512, n_ch=16384, L=None, nb=16, fs_in=61440000, fastconv=True),
+    "F4u8": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, fmt="cu8"),
+    "F20s8": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, fmt="cs8"),
+    "R64": dict(n_src=1, D=512, n_ch=512, L=None, nb=16, fs_in=64800000, fastconv=True, fmt="rs16", seed=648),
+    "R64z": dict(n_src=1, D=512, n_ch=512, L=None, nb=16, fs_in=64800000, fastconv=True, real=True, seed=648),
 }
 
 
-def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
-    """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank."""
-    rng = np.random.default_rng(sum(map(ord, name)))
+def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None):
+    """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank.
+    fmt: the bank's input format (rows go through update_samples_device); real: CS16 rows with zero Q."""
+    rng = np.random.default_rng(sum(map(ord, name)) if seed is None else seed)
     bank = A.TunerBank.fastconv(n_ch, n_src, fs_in, D) if fastconv else A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
+    bank.set_input_format(fmt)
     rate = fs_in is not None
     cap = nb + 1 if rate else nb
     if L is not None:
@@ -75,8 +87,18 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
         bank.set_source(int(srcs[c]), ch=c); bank.set_frequency_word(int(fws[c]), ch=c)
     N = nb * 128 * D
     calls = 4                                              # distinct seeded inputs, cycled
-    iq = rng.integers(-12000, 12000, size=(calls, n_src, N, 2), endpoint=True).astype(np.int16)
-    dIQ = torch.from_numpy(iq).cuda()
+    if fmt == "rs16" or real:
+        raw = rng.integers(-12000, 12000, size=(calls, n_src, N), endpoint=True).astype(np.int16)
+        if real:
+            raw = np.stack([raw, np.zeros_like(raw)], axis=-1)
+    elif fmt == "cu8":
+        raw = rng.integers(0, 255, size=(calls, n_src, N, 2), endpoint=True).astype(np.uint8)
+    elif fmt == "cs8":
+        raw = rng.integers(-128, 127, size=(calls, n_src, N, 2), endpoint=True).astype(np.int8)
+    else:
+        raw = rng.integers(-12000, 12000, size=(calls, n_src, N, 2), endpoint=True).astype(np.int16)
+    iq = [FM.to_cs16(raw[0], fmt)]                            # the first call's rows as the restatements take them
+    dIQ = torch.from_numpy(raw).cuda()
     dI = torch.empty((n_ch, cap, 128), dtype=torch.int16, device="cuda")
     dQ = torch.empty_like(dI)
     stream = torch.cuda.current_stream()
@@ -90,7 +112,9 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
     out_blocks = []
 
     def call(k):
-        if rate:
+        if fmt != "cs16":
+            n = bank.update_samples_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, cap, stream=sp)
+        elif rate:
             n = bank.update_rate_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, cap, stream=sp)
         else:
             bank.update_device(dIQ[k % calls].data_ptr(), dI.data_ptr(), dQ.data_ptr(), nb, stream=sp)
@@ -144,7 +168,7 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
     n_mid = n_ch * nb * 128                                   # stage-1 outputs per call
     n_out = n_ch * sum(out_blocks) * 128 / reps               # outputs per call (mean)
     macs = n_mid * (4 * D + 2 * L)
-    nbytes = n_src * N * 4 + n_mid * 4 + 2 * n_src * 1024 * 4
+    nbytes = n_src * N * FM.BYTES[fmt] + n_mid * 4 + 2 * n_src * 1024 * 4
     K2 = 0
     if rate:
         U2 = bank.ratio()[0]
@@ -161,7 +185,7 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False):
            "chain": "USB" if chain else None, "timed_calls": reps, "timed_s": round(ms * reps / 1e3, 3),
            "ms_per_call": round(ms, 4), "output_samples_per_s": round(n_out / (ms * 1e-3), 1),
            "realtime_factor": round(N / float(fs_in or 44100 * D) / (ms * 1e-3), 2),
-           "fs_in": int(fs_in or 44100 * D), "ratio": list(bank.ratio()), "resampler_taps_per_phase": int(K2) if rate else None,
+           "fs_in": int(fs_in or 44100 * D), "input_format": fmt, "ratio": list(bank.ratio()), "resampler_taps_per_phase": int(K2) if rate else None,
            "output_blocks_per_call": round(sum(out_blocks) / reps, 3),
            "model": None if fastconv else model,
            "parity_channels": len(check), "parity": parity}
