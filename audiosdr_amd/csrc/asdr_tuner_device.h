@@ -83,6 +83,21 @@ typedef struct {
   int32_t n_channels, n_frames, hop, log2n, decimation;   /* H, log2 N, R */
 } FcChannelArgs;
 
+/* The monitors of a fast-convolution bank (asdr_tuner_monitor.hip; include/asdr_tuner.h, "Monitors"). */
+#define ASDR_TUNER_MON_LANES 256      /* spectrum kernel: four independent waves, each owning max(128, g) consecutive bins of X */
+
+typedef struct {
+  const float *x;                   /* [n_sources][n_frames][N]: the call's X */
+  double *acc;                      /* [n_sources][B] */
+  int32_t n_sources, n_frames, log2n, log2b;   /* log2 N, log2 B */
+  int32_t window, mode;             /* ASDR_TUNER_WIN_*, ASDR_TUNER_MON_* */
+} FcSpectrumArgs;
+
+typedef struct {
+  float *part;                      /* [n_frames][n_channels]: e_b[c] of the call's frames (float; channel order) */
+  double *acc;                      /* [n_channels] */
+} FcLevelArgs;
+
 #ifdef __HIP__
 /* The formats' loads (include/asdr_tuner.h, "Input formats"): sample m >= 0 of a row as the CS16 word of x (xr low, xi high).
  * Rows start 16-byte aligned, so the 2-byte formats are read as aligned dwords (two samples) and never as bytes or shorts. */
@@ -128,8 +143,15 @@ __device__ inline void asdr_fetch2(const void *row, int64_t m, int32_t &w0, int3
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* a fast-convolution stage 1: the forward step(s), the channel step, then the history step, in order on `stream` */
-int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, void *stream);
+/* a fast-convolution stage 1: the forward step(s), the channel step, then the history step, in order on `stream`.  sp / lv: the
+ * monitors' arguments, NULL when off: with lv the channel step is asdr_launch_tuner_channel_levels instead of the plain channel
+ * kernel, with sp asdr_launch_tuner_spectrum runs between the channel step and the history step. */
+int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLevelArgs *lv,
+                               void *stream);
+/* asdr_tuner_monitor.hip: every source x span of bins of X into the spectrum accumulators; the channel step with the level
+ * epilogue, then the fold of the call's partials into the level accumulators */
+int asdr_launch_tuner_spectrum(const FcSpectrumArgs *sp, void *stream);
+int asdr_launch_tuner_channel_levels(const FcChannelArgs *c, const FcLevelArgs *lv, void *stream);
 /* the stage-2 step: every channel x 512-output tile (at least one tile: the carry is written even when no block is) */
 int asdr_launch_tuner_resample(const ResampleArgs *a, void *stream);
 /* the filter step (every channel x 128-output block) followed by the history step, in order on `stream` */

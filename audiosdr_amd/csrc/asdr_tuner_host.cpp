@@ -163,6 +163,16 @@ struct asdr_tuner_bank {
   float *d_fc_tab = nullptr;          // [N] W_N, [256] W_256, [256] G (float pairs)
   float *d_fc_x = nullptr;            // X, then the four-step scratch: [2][n_sources][n_frames][N] float pairs
   size_t fc_x_cap = 0;
+  // monitors (fast-convolution banks; include/asdr_tuner.h, "Monitors"): spectrum [n_sources][B] and its frame count; levels
+  // [n_channels], their count and the call's partials [n_frames][n_channels]
+  int spec_bins = 0, spec_win = ASDR_TUNER_WIN_HANN, spec_mode = ASDR_TUNER_MON_SUM;
+  long long spec_frames = 0;
+  double *d_spec = nullptr;
+  bool lev_on = false;
+  long long lev_frames = 0;
+  double *d_lev = nullptr;
+  float *d_lev_part = nullptr;
+  size_t lev_part_cap = 0;
   // device
   asdr_tuner_state_t *d_chan = nullptr;
   int32_t *d_order = nullptr, *d_taps = nullptr, *d_hist[2] = {nullptr, nullptr};
@@ -323,6 +333,14 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16
     HIPCHK(hipMalloc(&t->d_fc_x, x_bytes));
     t->fc_x_cap = x_bytes;
   }
+  const size_t part_bytes = t->lev_on ? (size_t)t->n * n_frames * sizeof(float) : 0;
+  if (part_bytes > t->lev_part_cap) {   // grow the levels' partials, likewise
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (t->d_lev_part) HIPCHK(hipFree(t->d_lev_part));
+    t->d_lev_part = nullptr; t->lev_part_cap = 0;
+    HIPCHK(hipMalloc(&t->d_lev_part, part_bytes));
+    t->lev_part_cap = part_bytes;
+  }
   FcForwardArgs f;
   f.in = (const int32_t *)dIQ; f.hist_rd = t->d_hist[t->cur]; f.hist_wr = t->d_hist[t->cur ^ 1];
   f.tw = t->d_fc_tab; f.x = t->d_fc_x; f.scratch = t->d_fc_x + x_floats;
@@ -336,7 +354,16 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16
   c.chan = t->d_chan; c.order = t->d_order; c.out_i = dI; c.out_q = dQ;
   c.pos = t->pos; c.out_stride = (int64_t)out_stride_blocks * 128;
   c.n_channels = t->n; c.n_frames = n_frames; c.hop = H; c.log2n = log2n; c.decimation = t->D;
-  if (asdr_launch_tuner_fastconv(&f, &c, stream) != 0) return fail("fast-convolution kernel launch failed");
+  FcSpectrumArgs sp;
+  sp.x = t->d_fc_x; sp.acc = t->d_spec; sp.n_sources = t->n_src; sp.n_frames = n_frames; sp.log2n = log2n;
+  for (sp.log2b = 0; (1 << sp.log2b) < t->spec_bins; sp.log2b++) {}
+  sp.window = t->spec_win; sp.mode = t->spec_mode;
+  FcLevelArgs lv;
+  lv.part = t->d_lev_part; lv.acc = t->d_lev;
+  if (asdr_launch_tuner_fastconv(&f, &c, t->spec_bins ? &sp : nullptr, t->lev_on ? &lv : nullptr, stream) != 0)
+    return fail("fast-convolution kernel launch failed");
+  if (t->spec_bins) t->spec_frames += n_frames;
+  if (t->lev_on) t->lev_frames += n_frames;
   t->pos += (long long)n_frames * H;
   t->cur ^= 1;
   return 0;
@@ -514,7 +541,7 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipDeviceSynchronize();
     hipFree(t->d_chan); hipFree(t->d_order); hipFree(t->d_taps); hipFree(t->d_hist[0]); hipFree(t->d_hist[1]); hipFree(t->d_io);
     hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
-    hipFree(t->d_fc_tab); hipFree(t->d_fc_x);
+    hipFree(t->d_fc_tab); hipFree(t->d_fc_x); hipFree(t->d_spec); hipFree(t->d_lev); hipFree(t->d_lev_part);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -528,8 +555,11 @@ int asdr_tuner_reset(asdr_tuner_t *t) {
     if (asdr_tuner_synchronize(t) != 0) return -1;
     HIPCHK(hipMemset(t->d_hist[t->cur], 0, (size_t)t->n_src * t->hist_slots * sizeof(int32_t)));
     if (t->d_carry[t->ccur]) HIPCHK(hipMemset(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t)));
+    if (t->d_spec) HIPCHK(hipMemset(t->d_spec, 0, (size_t)t->n_src * t->spec_bins * sizeof(double)));
+    if (t->d_lev) HIPCHK(hipMemset(t->d_lev, 0, (size_t)t->n * sizeof(double)));
     HIPCHK(hipDeviceSynchronize());
   }
+  t->spec_frames = t->lev_frames = 0;
   t->pos = 0;
   t->out_pos = 0;
   t->carry_stale = false;
@@ -853,5 +883,112 @@ float asdr_tuner_last_kernel_ms(asdr_tuner_t *t) {
   if (hipEventElapsedTime(&ms, t->ev0, t->ev1) != hipSuccess) return -1.0f;
   return ms;
 }
+
+}  // extern "C"
+
+// ---- monitors (include/asdr_tuner.h, "Monitors")
+namespace {
+const char *kNoMonitor = "only a fast-convolution bank has monitors: a direct-form or rate bank computes no spectrum X";
+
+// (re)allocate a monitor's accumulator of n doubles (n = 0: free it) and zero it; nothing of ours is in flight afterwards
+int monitor_alloc(asdr_tuner_t *t, double **acc, size_t n) {
+  if (t->device == ASDR_NO_DEVICE) return 0;
+  if (asdr_tuner_synchronize(t) != 0) return -1;
+  double *fresh = nullptr;
+  if (n) {
+    HIPCHK(hipMalloc(&fresh, n * sizeof(double)));
+    if (hipMemset(fresh, 0, n * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+      hipFree(fresh);
+      return fail("tuner monitor: clearing the accumulators failed");
+    }
+  }
+  if (*acc) hipFree(*acc);
+  *acc = fresh;
+  return 0;
+}
+
+// the shared read: wait, copy n doubles and the count out, clear on request
+int monitor_read(asdr_tuner_t *t, double *acc, size_t n, long long *count, double *dst, long long *frames, int clear) {
+  if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (asdr_tuner_synchronize(t) != 0) return -1;
+  if (dst) HIPCHK(hipMemcpy(dst, acc, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (frames) *frames = *count;
+  if (clear) {
+    HIPCHK(hipMemset(acc, 0, n * sizeof(double)));
+    HIPCHK(hipDeviceSynchronize());
+    *count = 0;
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int asdr_tuner_spectrum_enable(asdr_tuner_t *t, int n_bins, int window, int mode) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoMonitor);
+  if (n_bins != 0) {
+    if (n_bins < 256 || n_bins > (1 << t->log2n) || (n_bins & (n_bins - 1)) != 0)
+      return fail("spectrum bins must be 0 (off) or a power of two in 256.." + std::to_string(1 << t->log2n) + " (the FFT size)");
+    if (window != ASDR_TUNER_WIN_RECT && window != ASDR_TUNER_WIN_HANN) return fail("unknown spectrum window (ASDR_TUNER_WIN_RECT, ASDR_TUNER_WIN_HANN)");
+    if (mode != ASDR_TUNER_MON_SUM && mode != ASDR_TUNER_MON_PEAK) return fail("unknown spectrum mode (ASDR_TUNER_MON_SUM, ASDR_TUNER_MON_PEAK)");
+  }
+  if (monitor_alloc(t, &t->d_spec, (size_t)t->n_src * n_bins) != 0) return -1;
+  t->spec_bins = n_bins;
+  if (n_bins) { t->spec_win = window; t->spec_mode = mode; }
+  t->spec_frames = 0;
+  return 0;
+}
+
+int asdr_tuner_spectrum_bins(const asdr_tuner_t *t) { return t && t->fc ? t->spec_bins : 0; }
+int asdr_tuner_spectrum_window(const asdr_tuner_t *t) { return t && t->fc && t->spec_bins ? t->spec_win : -1; }
+int asdr_tuner_spectrum_mode(const asdr_tuner_t *t) { return t && t->fc && t->spec_bins ? t->spec_mode : -1; }
+long long asdr_tuner_spectrum_frames(const asdr_tuner_t *t) { return t && t->fc && t->spec_bins ? t->spec_frames : -1; }
+
+int asdr_tuner_spectrum_read(asdr_tuner_t *t, double *dst, long long *frames, int clear) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoMonitor);
+  if (!t->spec_bins) return fail("the spectrum monitor is off: asdr_tuner_spectrum_enable");
+  return monitor_read(t, t->d_spec, (size_t)t->n_src * t->spec_bins, &t->spec_frames, dst, frames, clear);
+}
+
+const double *asdr_tuner_spectrum_device(asdr_tuner_t *t) {
+  if (!t) { fail("null tuner bank"); return nullptr; }
+  if (!t->fc) { fail(kNoMonitor); return nullptr; }
+  if (!t->spec_bins) { fail("the spectrum monitor is off: asdr_tuner_spectrum_enable"); return nullptr; }
+  if (t->device == ASDR_NO_DEVICE) { fail(kNoDevice); return nullptr; }
+  return t->d_spec;
+}
+
+int asdr_tuner_spectrum_clear(asdr_tuner_t *t) { return asdr_tuner_spectrum_read(t, nullptr, nullptr, 1); }
+
+int asdr_tuner_levels_enable(asdr_tuner_t *t, int on) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoMonitor);
+  if (monitor_alloc(t, &t->d_lev, on ? (size_t)t->n : 0) != 0) return -1;
+  t->lev_on = on != 0;
+  t->lev_frames = 0;
+  return 0;
+}
+
+int asdr_tuner_levels_enabled(const asdr_tuner_t *t) { return t && t->fc && t->lev_on ? 1 : 0; }
+long long asdr_tuner_levels_frames(const asdr_tuner_t *t) { return t && t->fc && t->lev_on ? t->lev_frames : -1; }
+
+int asdr_tuner_levels_read(asdr_tuner_t *t, double *dst, long long *frames, int clear) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoMonitor);
+  if (!t->lev_on) return fail("the level monitor is off: asdr_tuner_levels_enable");
+  return monitor_read(t, t->d_lev, (size_t)t->n, &t->lev_frames, dst, frames, clear);
+}
+
+const double *asdr_tuner_levels_device(asdr_tuner_t *t) {
+  if (!t) { fail("null tuner bank"); return nullptr; }
+  if (!t->fc) { fail(kNoMonitor); return nullptr; }
+  if (!t->lev_on) { fail("the level monitor is off: asdr_tuner_levels_enable"); return nullptr; }
+  if (t->device == ASDR_NO_DEVICE) { fail(kNoDevice); return nullptr; }
+  return t->d_lev;
+}
+
+int asdr_tuner_levels_clear(asdr_tuner_t *t) { return asdr_tuner_levels_read(t, nullptr, nullptr, 1); }
 
 }  // extern "C"

@@ -15,7 +15,11 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_output_position", "asdr_tuner_set_resampler", "asdr_tuner_get_resampler", "asdr_tuner_out_blocks",
                  "asdr_tuner_update_rate_device", "asdr_tuner_update_rate", "asdr_tuner_create_fastconv", "asdr_tuner_fft_size",
                  "asdr_tuner_set_channel_filter", "asdr_tuner_get_channel_filter", "asdr_tuner_set_input_format",
-                 "asdr_tuner_input_format", "asdr_tuner_update_samples_device", "asdr_tuner_update_samples"]
+                 "asdr_tuner_input_format", "asdr_tuner_update_samples_device", "asdr_tuner_update_samples",
+                 "asdr_tuner_spectrum_enable", "asdr_tuner_spectrum_bins", "asdr_tuner_spectrum_window", "asdr_tuner_spectrum_mode",
+                 "asdr_tuner_spectrum_read", "asdr_tuner_spectrum_device", "asdr_tuner_spectrum_frames", "asdr_tuner_spectrum_clear",
+                 "asdr_tuner_levels_enable", "asdr_tuner_levels_enabled", "asdr_tuner_levels_read", "asdr_tuner_levels_device",
+                 "asdr_tuner_levels_frames", "asdr_tuner_levels_clear"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
@@ -23,6 +27,9 @@ MAX_CHANNEL_TAPS = 129
 # input formats (include/asdr_tuner.h, "Input formats"): name -> (ASDR_TUNER_IN_*, numpy dtype, values per stored sample)
 INPUT_FORMATS = {"cs16": (0, np.int16, 2), "cu8": (1, np.uint8, 2), "cs8": (2, np.int8, 2), "cf32": (3, np.float32, 2),
                  "rs16": (4, np.int16, 1)}
+# monitors (include/asdr_tuner.h, "Monitors"): ASDR_TUNER_WIN_* and ASDR_TUNER_MON_* by name
+SPECTRUM_WINDOWS = {"rect": 0, "hann": 1}
+SPECTRUM_MODES = {"sum": 0, "peak": 1}
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
@@ -70,6 +77,15 @@ def _lib():
     L.asdr_tuner_input_format.argtypes = [vp]; L.asdr_tuner_input_format.restype = i
     L.asdr_tuner_update_samples_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_samples_device.restype = i
     L.asdr_tuner_update_samples.argtypes = [vp, vp, i, i16p, i16p, i]; L.asdr_tuner_update_samples.restype = i
+    dp, llp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    L.asdr_tuner_spectrum_enable.argtypes = [vp, i, i, i]; L.asdr_tuner_spectrum_enable.restype = i
+    for n in ("spectrum_bins", "spectrum_window", "spectrum_mode", "spectrum_clear", "levels_enabled", "levels_clear"):
+        getattr(L, "asdr_tuner_" + n).argtypes = [vp]; getattr(L, "asdr_tuner_" + n).restype = i
+    for n in ("spectrum", "levels"):
+        getattr(L, "asdr_tuner_%s_read" % n).argtypes = [vp, dp, llp, i]; getattr(L, "asdr_tuner_%s_read" % n).restype = i
+        getattr(L, "asdr_tuner_%s_device" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_device" % n).restype = vp
+        getattr(L, "asdr_tuner_%s_frames" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_frames" % n).restype = ll
+    L.asdr_tuner_levels_enable.argtypes = [vp, i]; L.asdr_tuner_levels_enable.restype = i
     _typed = True
     return L
 
@@ -120,6 +136,22 @@ def suggest_fft_decimation(fs_in):
         if ud is not None and (best is None or ud[0] <= best[0]):
             best = (ud[0], R)
     return None if best is None else best[1]
+
+
+def spectrum_frequencies(fs_in, n_bins):
+    """Start frequency in Hz, relative to the capture's centre, of each of the n_bins output bins of the spectrum monitor (bin
+    width fs_in / n_bins; FFT order: bins n_bins / 2 and up are the negative frequencies).  float64 [n_bins]."""
+    n_bins = int(n_bins)
+    j = np.arange(n_bins, dtype=np.float64)
+    return np.where(j < n_bins // 2, j, j - n_bins) * (float(fs_in) / n_bins)
+
+
+class _DeviceRows:
+    """A device allocation as a __cuda_array_interface__ object, so that torch.as_tensor wraps it without a copy."""
+
+    def __init__(self, ptr, shape, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
 
 
 class TunerBank:
@@ -332,3 +364,82 @@ class TunerBank:
 
     def last_kernel_ms(self):
         return float(self._L.asdr_tuner_last_kernel_ms(self._h))
+
+    # monitors of a fast-convolution bank (include/asdr_tuner.h, "Monitors")
+    def enable_spectrum(self, n_bins, window="hann", mode="sum"):
+        """Accumulate every source's wideband power spectrum in n_bins bins (a power of two in 256..N; 0 switches it off) from the
+        next update call on.  window: "rect" or "hann"; mode: "sum" or "peak" (or the ASDR_TUNER_* values)."""
+        if isinstance(window, str):
+            if window.lower() not in SPECTRUM_WINDOWS:
+                raise AsdrError("unknown spectrum window %r (one of %s)" % (window, " ".join(SPECTRUM_WINDOWS)))
+            window = SPECTRUM_WINDOWS[window.lower()]
+        if isinstance(mode, str):
+            if mode.lower() not in SPECTRUM_MODES:
+                raise AsdrError("unknown spectrum mode %r (one of %s)" % (mode, " ".join(SPECTRUM_MODES)))
+            mode = SPECTRUM_MODES[mode.lower()]
+        self._chk(self._L.asdr_tuner_spectrum_enable(self._h, int(n_bins), int(window), int(mode)))
+
+    def spectrum_bins(self):
+        """B, 0 when the spectrum monitor is off."""
+        return int(self._L.asdr_tuner_spectrum_bins(self._h))
+
+    def spectrum_config(self):
+        """(n_bins, window, mode) by name, or None when the spectrum monitor is off."""
+        B = self.spectrum_bins()
+        if not B:
+            return None
+        w, m = int(self._L.asdr_tuner_spectrum_window(self._h)), int(self._L.asdr_tuner_spectrum_mode(self._h))
+        return (B, next(k for k, v in SPECTRUM_WINDOWS.items() if v == w), next(k for k, v in SPECTRUM_MODES.items() if v == m))
+
+    def spectrum(self, clear=True):
+        """(float64 [n_sources, B], frames accumulated); waits for the bank's work.  Mode sum: acc / frames is the mean power per
+        bin (int16^2 units); mode peak: acc is the largest frame.  Bin j starts at spectrum_frequencies(fs_in, B)[j]."""
+        out = np.zeros((self.n_sources, self.spectrum_bins()), dtype=np.float64)
+        frames = C.c_longlong()
+        self._chk(self._L.asdr_tuner_spectrum_read(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(frames), int(bool(clear))))
+        return out, int(frames.value)
+
+    def spectrum_frames(self):
+        return int(self._L.asdr_tuner_spectrum_frames(self._h))
+
+    def clear_spectrum(self):
+        self._chk(self._L.asdr_tuner_spectrum_clear(self._h))
+
+    def spectrum_tensor(self):
+        """The device rows as a torch float64 [n_sources, B] view (no copy, no synchronisation): valid in stream order after an
+        update call, until the next enable_spectrum() or close()."""
+        import torch
+        p = self._L.asdr_tuner_spectrum_device(self._h)
+        if not p:
+            raise AsdrError(self._L.asdr_last_error().decode())
+        return torch.as_tensor(_DeviceRows(p, (self.n_sources, self.spectrum_bins()), self), device="cuda")
+
+    def enable_levels(self, on=True):
+        """Accumulate every channel's power before rounding and clamp (sum of |y|^2 over its Fs_mid samples) from the next update
+        call on."""
+        self._chk(self._L.asdr_tuner_levels_enable(self._h, int(bool(on))))
+
+    def levels_enabled(self):
+        return bool(self._L.asdr_tuner_levels_enabled(self._h))
+
+    def levels(self, clear=True):
+        """(float64 [n_channels] in channel order, frames accumulated); waits for the bank's work.  level / (128 frames) is the mean
+        power per Fs_mid sample.  A retune does not clear a channel's level."""
+        out = np.zeros(self.n_channels, dtype=np.float64)
+        frames = C.c_longlong()
+        self._chk(self._L.asdr_tuner_levels_read(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(frames), int(bool(clear))))
+        return out, int(frames.value)
+
+    def levels_frames(self):
+        return int(self._L.asdr_tuner_levels_frames(self._h))
+
+    def clear_levels(self):
+        self._chk(self._L.asdr_tuner_levels_clear(self._h))
+
+    def levels_tensor(self):
+        """The device accumulators as a torch float64 [n_channels] view, as spectrum_tensor()."""
+        import torch
+        p = self._L.asdr_tuner_levels_device(self._h)
+        if not p:
+            raise AsdrError(self._L.asdr_last_error().decode())
+        return torch.as_tensor(_DeviceRows(p, (self.n_channels,), self), device="cuda")

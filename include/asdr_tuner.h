@@ -92,7 +92,29 @@
  * The conversion happens in the loads of the kernels that read the caller's rows.  A fast-convolution bank
  * computes X of an RS16 window by a transform of N / 2 complex points on z[n] = w[2n] + j w[2n + 1] and the untangling step
  * X[k] = (Z[k] + conj Z[N/2 - k]) / 2 - (j / 2) W_N^k (Z[k] - conj Z[N/2 - k]), X[N - k] = conj X[k]: the same X in exact
- * arithmetic, so the statement of X above holds as it stands.
+ * arithmetic, so the statement of X above holds as it stands. *
+ * Monitors (fast-convolution banks only; both off at creation).  They observe what stage 1 computes anyway and change nothing of
+ * it: a bank that enables neither launches and allocates as before, and a bank with both on writes bit for bit the same I and Q.
+ * The statements are exact (float64); the kernels compute |.|^2 and the sums inside one frame in float32 and accumulate frames in
+ * float64 (DESIGN.md 3.8.4 gives the tolerance).
+ *   spectrum  per source s and frame b, from the X of "frame b" above (so formats, RS16, history across calls and the zeros before
+ *             position 0 are as stated there).  Window rect: W[k] = X[k].  Window hann: W[k] = X[k] / 2 - (X[(k - 1) mod N] +
+ *             X[(k + 1) mod N]) / 4, the DFT of the window's samples times 0.5 - 0.5 cos(2 pi n / N); the frames overlap by half, so
+ *             a hann sum is Welch's estimator at 50 % overlap.  p_b[k] = |W[k]|^2 / N^2: a complex tone of amplitude A on a bin
+ *             centre reads A^2 with rect and A^2 / 4 with hann (not corrected).  B output bins, a power of two in [256, N],
+ *             g = N / B: P_b[j] = sum_{k = j g}^{j g + g - 1} p_b[k], j in FFT order (j = 0 starts at the capture's centre
+ *             frequency, bin width Fs_in / B; j >= B / 2 are the negative frequencies), as asdr_grab_spectrum orders its bins.
+ *             Mode sum: acc[s][j] += P_b[j]; mode peak: acc[s][j] = max(acc[s][j], P_b[j]); frames in order; a bank-wide count of
+ *             accumulated frames goes up by one per frame in both.  acc is float64.
+ *   level     per channel c and frame b, with y[n], n = 128 .. 255, the "output" line's y (1 / N included) before the fine NCO,
+ *             the rounding and the clamp (the NCO has unit modulus, the coarse sign too): e_b[c] = sum_n |y[n]|^2, in int16^2
+ *             units; level[c] += e_b[c] in float64, with a bank-wide frame count of its own.  level[c] / (128 frames) is the mean
+ *             power per Fs_mid sample; it is taken before the clamp, so it passes 32767^2 where the output saturates.  A retune
+ *             does not clear a channel's level: clear after retuning.
+ *   state     enable / disable / re-configuration clear that monitor's accumulators and count and apply from the next update call;
+ *             asdr_tuner_reset clears both monitors and keeps their configuration; retunes, filter and format changes touch
+ *             neither.  Direct-form and rate banks have no X: every monitor function fails on them (asdr_last_error).  An
+ *             ASDR_NO_DEVICE bank takes the configuration calls and fails the reads, the clears and the device getters.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -205,6 +227,34 @@ int asdr_tuner_input_format(const asdr_tuner_t *t);   /* ASDR_TUNER_IN_*, -1 for
 int asdr_tuner_update_samples_device(asdr_tuner_t *t, const void *dIn, long in_stride_samples, int n_frames, int16_t *dI, int16_t *dQ,
                                      int out_capacity_blocks, long out_stride_blocks, void *stream);
 int asdr_tuner_update_samples(asdr_tuner_t *t, const void *In, int n_frames, int16_t *I, int16_t *Q, int out_capacity_blocks);
+
+/* Monitors (the "Monitors" section above).  All return 0 / -1 unless said otherwise and fail on a bank that is not a
+ * fast-convolution bank. */
+#define ASDR_TUNER_WIN_RECT 0
+#define ASDR_TUNER_WIN_HANN 1
+#define ASDR_TUNER_MON_SUM 0
+#define ASDR_TUNER_MON_PEAK 1
+/* n_bins = B, a power of two in [256, N], or 0 to switch the monitor off (window and mode are then not looked at).  Rejected with
+ * the old configuration and accumulators kept: any other B, an unknown window or mode.  Synchronises with the bank's work. */
+int asdr_tuner_spectrum_enable(asdr_tuner_t *t, int n_bins, int window, int mode);
+int asdr_tuner_spectrum_bins(const asdr_tuner_t *t);      /* B, 0 when off (and for a NULL or direct-form bank) */
+int asdr_tuner_spectrum_window(const asdr_tuner_t *t);    /* ASDR_TUNER_WIN_*, -1 when off */
+int asdr_tuner_spectrum_mode(const asdr_tuner_t *t);      /* ASDR_TUNER_MON_*, -1 when off */
+/* Waits for the bank's work, then copies acc to dst [n_sources][B] (if not NULL) and the frame count to *frames (if not NULL);
+ * clear != 0 then clears both.  Fails when the monitor is off. */
+int asdr_tuner_spectrum_read(asdr_tuner_t *t, double *dst, long long *frames, int clear);
+/* acc [n_sources][B] in device memory, valid in stream order after an update call, until the next enable / destroy; NULL
+ * (asdr_last_error) when off or without a device. */
+const double *asdr_tuner_spectrum_device(asdr_tuner_t *t);
+long long asdr_tuner_spectrum_frames(const asdr_tuner_t *t);   /* frames accumulated by the update calls so far; -1 when off */
+int asdr_tuner_spectrum_clear(asdr_tuner_t *t);           /* waits for the bank's work; accumulators and count to 0 */
+int asdr_tuner_levels_enable(asdr_tuner_t *t, int on);
+int asdr_tuner_levels_enabled(const asdr_tuner_t *t);     /* 1 / 0 (0 for a NULL or direct-form bank) */
+/* As asdr_tuner_spectrum_read: dst [n_channels] in channel order (not the kernels' schedule order). */
+int asdr_tuner_levels_read(asdr_tuner_t *t, double *dst, long long *frames, int clear);
+const double *asdr_tuner_levels_device(asdr_tuner_t *t);
+long long asdr_tuner_levels_frames(const asdr_tuner_t *t);
+int asdr_tuner_levels_clear(asdr_tuner_t *t);
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */

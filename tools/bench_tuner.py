@@ -18,6 +18,8 @@
   R64       skimmer on a direct-sampling receiver: 1 source of real int16 (RS16) at 64.8 MS/s, R = 512 (N = 131,072; Fs_mid =
             126.5625 kHz, 392 / 1125), 512 channels, 16 frames per call
   R64z      R64's signal as CS16 with zero Q (what such a source had to be blown up to before), for comparison
+  F4m       F4 with both monitors on (include/asdr_tuner.h, "Monitors"): spectrum of 4,096 bins, hann, sum, and the levels
+  F20m      F20 with both monitors on, likewise; run beside F4 / F20 in one process: monitors off is the code path without them
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
@@ -27,7 +29,7 @@ time per call over call time.  The first call of each config is checked against 
 channels.  Fast-convolution banks (F*) have no operation model here (DESIGN.md 3.8.2 counts them); their first call is checked
 against tests/tuner_fastconv_ref.py, a float64 statement, so "parity" there means every sample within +-2.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z F4m F20m]
 """
 import json
 import os
@@ -65,15 +67,20 @@ CONFIGS = {
     "F20s8": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, fmt="cs8"),
     "R64": dict(n_src=1, D=512, n_ch=512, L=None, nb=16, fs_in=64800000, fastconv=True, fmt="rs16", seed=648),
     "R64z": dict(n_src=1, D=512, n_ch=512, L=None, nb=16, fs_in=64800000, fastconv=True, real=True, seed=648),
+    "F4m": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, monitors=True, seed=sum(map(ord, "F4"))),
+    "F20m": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, monitors=True, seed=sum(map(ord, "F20"))),
 }
 
 
-def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None):
+def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None, monitors=False):
     """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank.
-    fmt: the bank's input format (rows go through update_samples_device); real: CS16 rows with zero Q."""
+    fmt: the bank's input format (rows go through update_samples_device); real: CS16 rows with zero Q; monitors: the spectrum
+    (4,096 bins, hann, sum) and the levels of a fast-convolution bank are on."""
     rng = np.random.default_rng(sum(map(ord, name)) if seed is None else seed)
     bank = A.TunerBank.fastconv(n_ch, n_src, fs_in, D) if fastconv else A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
     bank.set_input_format(fmt)
+    if monitors:
+        bank.enable_spectrum(4096, "hann", "sum"); bank.enable_levels()
     rate = fs_in is not None
     cap = nb + 1 if rate else nb
     if L is not None:
@@ -191,6 +198,12 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
            "parity_channels": len(check), "parity": parity}
     if fastconv:
         out.update({"kind": "fastconv", "fft_size": bank.fft_size(), "parity_max_abs_diff": dmax})
+    if monitors:
+        spec, frames = bank.spectrum()
+        lev, lframes = bank.levels()
+        out.update({"monitors": {"spectrum_bins": 4096, "window": "hann", "mode": "sum", "spectrum_frames": frames, "level_frames": lframes,
+                                 "mean_power_per_source": [round(float(v), 1) for v in spec.sum(axis=1) / max(frames, 1)],
+                                 "channels_with_level": int((lev > 0).sum())}})
     print(json.dumps(out), flush=True)
     bank.close()
     if sdr is not None:
