@@ -179,6 +179,45 @@ def test_pass_through_then_a_resampler_starts_from_zero_history(gpu):
     bank.close()
 
 
+def rail_resampler(rng, U, K):
+    """U K taps with sum |h2| = 65535 in every phase exactly: all negative in phases 0, 3, 6, ..., all positive in 1, 4, 7, ...,
+    random signs in the rest."""
+    h2 = np.zeros((K, U), dtype=np.int64)
+    for ph in range(U):
+        a = rng.multinomial(65535, rng.dirichlet(np.ones(K)))
+        while a.max() > 32767:
+            a = rng.multinomial(65535, rng.dirichlet(np.ones(K)))
+        h2[:, ph] = a * (-1 if ph % 3 == 0 else 1 if ph % 3 == 1 else rng.choice([-1, 1], size=K))
+    return h2.reshape(-1).astype(np.int16)
+
+
+@pytest.mark.parametrize("g2", [0, 4, 15])
+def test_stage2_rails_and_gain_shifts(gpu, g2):
+    """Stage 2 at its int32 edge: 96 kHz, D = 1 (147 / 320), stage 1 the pass filter, every phase of h2 with sum |h2| = 65535,
+    inputs drawn from {-32768, 32767, -32767, 0} with runs of (-32768, -32768) and (32767, 32767).  The channels sit at fw = 0;
+    those at a phase of +-45 degrees saturate the mixer, so u holds runs of -32768 exactly and an all-negative phase over such a
+    run sums to 65535 * 32768 (+ 16384 at g2 = 0): the case behind the kernel's "exact in int32"."""
+    fs, D, K, nf = 96000, 1, 8, 12
+    rng = np.random.default_rng(200 + g2)
+    bank = gpu.TunerBank(4, 1, D, fs_in=fs)
+    U, M = bank.ratio()
+    h2 = rail_resampler(rng, U, K)
+    bank.set_filter([16384], 1); bank.set_resampler(h2, g2)
+    ref = RR.TunerRateRef(4, 1, D, fs, [16384], 1, h2, g2)
+    for c, ph in enumerate([0, 512 << 20, 3584 << 20, 1536 << 20]):
+        for o in (bank, ref):
+            o.set_phase(ph, ch=c)
+    iq = rng.choice(np.array([-32768, 32767, -32767, 0], dtype=np.int16), size=(1, nf * 128, 2))
+    iq[0, 300:400], iq[0, 700:800] = -32768, 32767
+    I, Q = check(bank, ref, iq)
+    assert not ref.fw.any() and (ref.u == -32768).any() and (ref.u == 32767).any()
+    acc = RR.accumulate(ref.u, h2, U, M, 0, I.shape[1] * 128)                # the reference's sums reach both edges
+    assert acc.max() == 65535 * 32768 == -acc.min() and acc.max() + 16384 < 1 << 31
+    for y in (I, Q):
+        assert (y == 32767).any() and (y == -32768).any()
+    bank.close()
+
+
 def test_strided_rows_and_the_capacity_error(gpu):
     fs, D, n_ch, n_src = 2400000, 50, 4, 2
     rng = np.random.default_rng(9)

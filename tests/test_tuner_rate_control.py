@@ -1,6 +1,8 @@
 """Rate banks of the digital tuner (include/asdr_tuner.h, "Rate banks") on ASDR_NO_DEVICE banks: creation constraints, U / M,
 the frequency word at Fs_in, the set_resampler rules, the block timing against tests/tuner_rate_ref.py, the default filters'
 responses, and the reference's stage 2 against a direct float64 statement."""
+import warnings
+
 import numpy as np
 import pytest
 
@@ -200,3 +202,120 @@ def test_rate_bank_update_calls_need_a_device(A, T):
         t.update_rate(np.zeros((1, 128, 2), dtype=np.int16))
     with pytest.raises(A.AsdrError):
         t.update(np.zeros((1, 128, 2), dtype=np.int16))
+
+
+PLACED = {(48000, 1): (33, 12), (10000000, 64): (1024, 64)}         # (Fs_in, D): (L, K)
+
+
+def placed_pair(fs, D, rng, n_ch=3):
+    L, K = PLACED[fs, D]
+    U, _ = RR.ratio(fs, D)
+    h, h2 = rng.integers(-60, 60, size=L, endpoint=True), rng.integers(-500, 500, size=U * K, endpoint=True)
+    a, b = (RR.TunerRateRef(n_ch, 1, D, fs, h, 2, h2, 1) for _ in range(2))
+    for o in (a, b):
+        for c, fw in enumerate([0x01234567, 1 << 31, 0xFFFFFFFF][:n_ch]):
+            o.set_frequency_word(fw, ch=c)
+        o.set_phase(0xCAFEF00D, ch=1)
+    return a, b
+
+
+def cs16(rng, n):
+    return rng.integers(-20000, 20000, size=(1, n, 2), endpoint=True)
+
+
+def same_state(a, b):
+    return a.P == b.P and a.out_pos == b.out_pos and all(list(getattr(a, k)) == list(getattr(b, k)) for k in ("src", "fw", "pos_a", "ph_a"))
+
+
+@pytest.mark.parametrize("fs,D", list(PLACED))
+def test_a_placed_rate_reference_equals_a_stepped_one(fs, D):
+    """TunerRateRef.place_at(P, tail) against 281 frames of stepping, one buffer of 20 frames fed over and over as the GPU suite
+    feeds its banks (tests/test_gpu_tuner_positions.py places references where stepping is out of reach).  A channel is retuned
+    during the feed (the placed reference is moved there by place_at(P) alone).  The tail is exactly as long as place_at asks.
+    Then a retune of every kind, a new resampler and a new filter: the next calls' I and Q and block counts bit for bit, both
+    positions and the anchors."""
+    rng = np.random.default_rng(fs + D)
+    blk = 128 * D
+    a, b = placed_pair(fs, D, rng)
+    L, K = PLACED[fs, D]
+    fed = cs16(rng, 20 * blk)
+    counts = []
+    for rep in range(14):
+        if rep == 6:
+            b.place_at(a.P)
+            for o in (a, b):
+                o.set_frequency_word(0x2468ACE1, ch=2)
+        a.update(fed)
+        counts.append(fed.shape[1])
+    a.update(fed[:, :blk])
+    counts.append(blk)
+    T = max(1024, a.tail_needed())
+    assert a.tail_needed() == max(L - D, 0) + D * (K - 1 + -(-127 * a.M // a.U) + 2)
+    b.place_at(a.P, R.fed_tail(fed, counts, T))
+    assert same_state(a, b) and a.P == 281 * blk and b.u0 > 0
+    h1, r1 = rng.integers(-60, 60, size=L - 8, endpoint=True), rng.integers(-500, 500, size=a.U * 7, endpoint=True)
+    steps = [lambda o: None,
+             lambda o: o.set_frequency(1_234.5, ch=1),
+             lambda o: o.set_frequency_word(0x0FEDCBA9, ch=0),
+             lambda o: o.set_phase(0xDEADBEEF, ch=2),
+             lambda o: o.set_source(0, ch=1),
+             lambda o: o.set_resampler(r1, 2),
+             lambda o: o.set_filter(h1, 3),
+             lambda o: o.set_phase(77 << 20),
+             lambda o: o.set_frequency(-7_000.0)]
+    for k, st in enumerate(steps):
+        st(a); st(b)
+        iq = cs16(rng, (1, 2, 7)[k % 3] * blk)
+        assert a.out_blocks(iq.shape[1] // blk) == b.out_blocks(iq.shape[1] // blk)
+        (aI, aQ), (bI, bQ) = a.update(iq), b.update(iq)
+        assert np.array_equal(aI, bI) and np.array_equal(aQ, bQ), k
+        assert same_state(a, b), k
+    assert aI.any() and aQ.any()
+
+
+@pytest.mark.parametrize("fs,D", list(PLACED))
+def test_rate_reference_placed_past_2_to_the_32_nothing_overflows(fs, D):
+    """Placed at 2^32 + 12,345 * 128 D with a seeded tail, then two calls with a retune between them, every numpy warning and
+    floating-point flag an error; the block counts and positions against Python-integer arithmetic."""
+    rng = np.random.default_rng(fs - D)
+    blk = 128 * D
+    ref, _ = placed_pair(fs, D, rng)
+    P = (1 << 32) + 12345 * blk
+    with warnings.catch_warnings(), np.errstate(all="raise"):
+        warnings.simplefilter("error")
+        ref.place_at(P, cs16(rng, max(1024, ref.tail_needed())))
+        assert ref.out_pos == 128 * RR.blocks_out(P // D, ref.U, ref.M)
+        for nf in (7, 16):
+            n = ref.out_blocks(nf)
+            I, Q = ref.update(cs16(rng, nf * blk))
+            P += nf * blk
+            assert n >= 1 and I.shape == (3, n, 128) and I.any() and Q.any()
+            assert ref.P == P and ref.out_pos == 128 * RR.blocks_out(P // D, ref.U, ref.M)
+            assert (128 * RR.blocks_out(P // D, ref.U, ref.M) - 1) * ref.M // ref.U <= P // D - 1      # the last block out is complete
+            ref.set_frequency(-1_234.5)
+            assert list(ref.pos_a) == [P] * 3
+
+
+def test_a_rate_reference_read_outside_what_it_holds_raises():
+    """Neither stage makes up a sample: a tail shorter than place_at asks, a retune inside the tail, a pass-through stage 2, u
+    before what is held, and an update() after a place_at(P) without a tail are all refused."""
+    fs, D = 48000, 1
+    rng = np.random.default_rng(5)
+    ref, _ = placed_pair(fs, D, rng)
+    P = 4000 * 128
+    with pytest.raises(AssertionError, match="needed"):
+        ref.place_at(P, cs16(rng, 1024)[:, :ref.tail_needed() - 1])
+    ref.place_at(P, cs16(rng, 1024))
+    with pytest.raises(AssertionError, match="before"):
+        RR.resample(ref.u, ref.h2, ref.U, ref.M, ref.g2, ref.out_pos - 128 * 8, 128, 0, ref.u0)
+    ref.update(cs16(rng, 128))
+    ref.place_at(P)
+    with pytest.raises(AssertionError):
+        ref.update(cs16(rng, 128))
+    ref.place_at(P - 128)
+    ref.set_frequency_word(5, ch=0)                                      # an anchor at P - 128
+    with pytest.raises(AssertionError, match="retune inside"):
+        ref.place_at(P, cs16(rng, 1024))
+    plain = RR.TunerRateRef(1, 1, 2, 88200)                              # U = M = 1, the pass-through
+    with pytest.raises(AssertionError):
+        plain.place_at(P, cs16(rng, 1024))

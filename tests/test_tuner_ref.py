@@ -4,8 +4,10 @@ import os
 import re
 import subprocess
 import sys
+import warnings
 
 import numpy as np
+import pytest
 
 import tuner_ref as R
 
@@ -145,3 +147,125 @@ def test_frequency_word_rounding():
     assert R.fw_from_hz(-22050.0, 1) == 1 << 31
     assert R.fw_from_hz(-1.0, 48) == (2**32 - round(2**32 / (44100.0 * 48))) & 0xFFFFFFFF
     assert R.fw_from_hz(44100.0 * 2 / 2**32 * 0.5, 2) == 1                   # exactly half a word: away from zero
+
+
+def small_taps(rng, L):
+    """L random taps with sum |h| <= 65535."""
+    return rng.integers(-60, 60, size=L, endpoint=True)
+
+
+PLACED_FWS = [0, 1 << 31, 0x01234567, 0xFFFFFFFF, R.fw_from_hz(-7_123.5, 1), 0x80000001]
+
+
+def placed_pair(D, L, rng):
+    h = small_taps(rng, L)
+    a, b = (R.TunerRef(len(PLACED_FWS), 2, D, h, 2) for _ in range(2))
+    for o in (a, b):
+        for c, fw in enumerate(PLACED_FWS):
+            o.set_source(c % 2, ch=c); o.set_frequency_word(fw, ch=c)
+        o.set_phase(0xCAFEF00D, ch=3)
+    return a, b
+
+
+def retunes(rng, L):
+    """One setter of every kind, a filter change and the all-channel forms."""
+    h1 = small_taps(rng, max(1, L - 8))
+    return [lambda o: o.set_frequency(12_345.6, ch=1),
+            lambda o: o.set_frequency_word(0x0FEDCBA9, ch=0),
+            lambda o: o.set_phase(0xDEADBEEF, ch=3),
+            lambda o: o.set_source(0, ch=5),
+            lambda o: o.set_filter(h1, 3),
+            lambda o: o.set_phase(77 << 20),
+            lambda o: o.set_frequency(-40_000.0),
+            lambda o: o.set_source(1)]
+
+
+def same_state(a, b):
+    return a.P == b.P and all(list(getattr(a, k)) == list(getattr(b, k)) for k in ("src", "fw", "pos_a", "ph_a"))
+
+
+@pytest.mark.parametrize("D,L", [(7, 85), (64, 1024)])
+def test_a_placed_reference_equals_a_stepped_one(D, L):
+    """place_at(P, tail) against 281 blocks of stepping, the same buffer of 20 blocks fed over and over as the GPU suite feeds its
+    banks (tests/test_gpu_tuner_positions.py places references past 2^30 and 2^32, where stepping is out of reach).  One channel
+    is retuned during the feed -- the placed reference is moved there by place_at(P) alone -- and the last call is one block, so
+    that at D = 7 the tail of 1024 samples spans two calls.  Then every kind of retune: the next calls' I and Q bit for bit, P and
+    the anchors."""
+    rng = np.random.default_rng(300 + D)
+    blk = 128 * D
+    a, b = placed_pair(D, L, rng)
+    fed = rng.integers(-20000, 20000, size=(2, 20 * blk, 2), endpoint=True)
+    counts = []
+    for rep in range(14):
+        if rep == 6:
+            b.place_at(a.P)
+            for o in (a, b):
+                o.set_frequency_word(0x2468ACE1, ch=2); o.set_phase(0x13579BDF, ch=4)
+        a.update(fed)
+        counts.append(fed.shape[1])
+    a.update(fed[:, :blk])
+    counts.append(blk)
+    b.place_at(a.P, R.fed_tail(fed, counts, 1024))
+    assert b.x0 == b.P - 1024 and same_state(a, b) and a.P == 281 * blk
+    assert list(a.pos_a) == [0, 0, 120 * blk, 0, 120 * blk, 0]
+    for k, st in enumerate([lambda o: None] + retunes(rng, L)):
+        st(a); st(b)
+        iq = rng.integers(-20000, 20000, size=(2, (1 + k % 3) * blk, 2), endpoint=True)
+        (aI, aQ), (bI, bQ) = a.update(iq), b.update(iq)
+        assert np.array_equal(aI, bI) and np.array_equal(aQ, bQ), k
+        assert same_state(a, b), k
+    assert aI.any() and aQ.any()
+
+
+@pytest.mark.parametrize("D,L", [(7, 85), (64, 1024)])
+def test_placed_past_2_to_the_32_nothing_overflows(D, L):
+    """A reference placed 12,345 blocks past 2^32 (at D = 64 that is 2^32 + 12,345 * 128 D; at D = 7 the first block boundary
+    past 2^32 takes the place of 2^32) with a seeded tail, two calls with a retune between them, every numpy warning and
+    floating-point flag an error.  The outputs equal those of a reference placed at 12,345 * 128 D with the same tail, whose
+    anchor phases were advanced by the distance between the two in Python integers."""
+    rng = np.random.default_rng(32 + D)
+    blk = 128 * D
+    far, near = placed_pair(D, L, rng)
+    tail = rng.integers(-20000, 20000, size=(2, 1500, 2), endpoint=True)
+    P_far, P_near = (-(-(1 << 32) // blk) + 12345) * blk, 12345 * blk
+    for c in range(near.n):
+        near.ph_a[c] = (int(near.ph_a[c]) + (P_far - P_near) * int(near.fw[c])) % (1 << 32)
+    with warnings.catch_warnings(), np.errstate(all="raise"):
+        warnings.simplefilter("error")
+        far.place_at(P_far, tail)
+        near.place_at(P_near, tail)
+        for k in range(2):
+            iq = rng.integers(-20000, 20000, size=(2, (2 - k) * blk, 2), endpoint=True)
+            (fI, fQ), (nI, nQ) = far.update(iq), near.update(iq)
+            assert np.array_equal(fI, nI) and np.array_equal(fQ, nQ) and fI.any()
+            assert far.P == near.P + P_far - P_near
+            for o in (far, near):
+                o.set_frequency_word(0x0FEDCBA9, ch=1); o.set_frequency(-1_234.5)
+            assert list(far.ph_a) == list(near.ph_a)
+            assert list(far.pos_a) == [far.P] * far.n and int(far.P) > 1 << 32
+
+
+def test_a_read_outside_the_held_tail_raises():
+    """z() never makes up a sample: before the tail's first sample, after its last, and in an update() that follows a place_at(P)
+    without a tail (unless every channel was re-anchored at P: then nothing before P is read)."""
+    D, L = 7, 85
+    rng = np.random.default_rng(8)
+    blk = 128 * D
+    ref, _ = placed_pair(D, L, rng)
+    tail = rng.integers(-20000, 20000, size=(2, 1024, 2), endpoint=True)
+    P = 5000 * blk
+    ref.place_at(P, tail)
+    ref.z(0, np.arange(P - 1024, P))
+    for m in (P - 1025, P):
+        with pytest.raises(AssertionError, match="outside"):
+            ref.z(0, np.array([m]))
+    with pytest.raises(AssertionError):
+        ref.place_at(P, tail[:, :1023])                                # shorter than the longest filter's reach
+    iq = rng.integers(-20000, 20000, size=(2, blk, 2), endpoint=True)
+    ref.place_at(P)
+    with pytest.raises(AssertionError, match="outside"):
+        ref.update(iq)
+    ref.place_at(P)
+    ref.set_phase(0)                                                   # every anchor at P: zeros before it, by the statement
+    I, _ = ref.update(iq)
+    assert I.any() and ref.P == P + blk

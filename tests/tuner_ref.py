@@ -32,7 +32,7 @@ def fw_from_hz(hz, D):
 
 def theta(m, pos_a, ph_a, fw):
     """NCO phase at global sample indices m (int64 array, m >= pos_a meaningful): ph_a + (m - pos_a) fw mod 2^32."""
-    d = (np.asarray(m, dtype=np.int64) - np.int64(pos_a)).astype(np.uint64)
+    d = (np.asarray(m, dtype=np.int64) - np.int64(pos_a)).astype(np.uint64) & np.uint64(0xFFFFFFFF)   # the product stays below 2^64
     return ((np.uint64(ph_a) + d * np.uint64(fw)) & np.uint64(0xFFFFFFFF)).astype(np.int64)
 
 
@@ -62,8 +62,22 @@ def default_filter_spec(D):
     return 11200.0, 32100.0, 44100.0 * D
 
 
+def fed_tail(buf, counts, T):
+    """The last T samples per row of a feed whose call i took the first counts[i] samples of every row of buf."""
+    parts, need = [], T
+    for n in reversed(counts):
+        take = min(n, need)
+        parts.append(buf[:, n - take:n])
+        need -= take
+        if need == 0:
+            break
+    assert need == 0
+    return np.concatenate(parts[::-1], axis=1)
+
+
 class TunerRef:
-    """The bank's state machine: position P, per-channel (src, fw, pos_a, ph_a), one filter, every source's whole input kept."""
+    """The bank's state machine: position P, per-channel (src, fw, pos_a, ph_a), one filter, and every source's input from sample
+    x0 on (x0 = 0: the whole input; place_at() keeps a tail only)."""
 
     def __init__(self, n_channels, n_sources, D, h=(16384,), g=1):
         self.n, self.n_src, self.D = n_channels, n_sources, D
@@ -72,6 +86,7 @@ class TunerRef:
         self.fw = np.zeros(n_channels, dtype=np.int64)
         self.pos_a = np.zeros(n_channels, dtype=np.int64)
         self.ph_a = np.zeros(n_channels, dtype=np.int64)
+        self.x0 = 0
         self.x = [np.zeros((0, 2), dtype=np.int64) for _ in range(n_sources)]
         self.set_filter(h, g)
 
@@ -100,24 +115,38 @@ class TunerRef:
         for c in self._chans(ch):
             self.pos_a[c] = self.P; self.ph_a[c] = int(ph) & 0xFFFFFFFF
 
+    def place_at(self, P, tail=None):
+        """Put the reference where a run of P input samples per source would have left it, without running it.  tail
+        [n_sources][T][2] holds the last T samples fed (samples P - T .. P - 1), T >= 1024 or all P of them: the longest filter
+        reaches 1023 samples back.  Channels (src, fw, anchors) stay as they are -- an anchor set at position 0 stays (0, ph_a), as
+        it would have; the bank keeps nothing else between calls.  Without a tail only P moves (setters then re-anchor there) and no
+        sample is held: the next update() needs a place_at() with a tail first, unless every channel was re-anchored."""
+        P = int(P)
+        assert P >= 0 and P % (BLOCK * self.D) == 0
+        if tail is None:
+            tail = np.zeros((self.n_src, 0, 2), dtype=np.int64)
+        else:
+            tail = np.asarray(tail, dtype=np.int64)
+            assert tail.shape[0] == self.n_src and tail.shape[2:] == (2,) and (tail.shape[1] >= 1024 or tail.shape[1] == P)
+            assert tail.shape[1] <= P
+        self.P, self.x0 = P, P - tail.shape[1]
+        self.x = [tail[s].copy() for s in range(self.n_src)]
+
     def z(self, c, m):
-        """zr, zi of channel c at global sample indices m (zero before the anchor and before 0)."""
+        """zr, zi of channel c at global sample indices m: zero before the anchor and before 0, as the statement has it; every other
+        sample must be one of those held (a sample that is not there is an error, never a zero)."""
         x = self.x[self.src[c]]
         ok = (m >= self.pos_a[c]) & (m >= 0)
-        mm = np.where(ok, m, 0)
-        zr, zi = mix(x[mm, 0], x[mm, 1], theta(mm, self.pos_a[c], self.ph_a[c], self.fw[c]))
+        i = m - self.x0
+        assert ((i >= 0) & (i < x.shape[0]))[ok].all(), "sample outside the %d held from %d on" % (x.shape[0], self.x0)
+        mm, i = np.where(ok, m, self.pos_a[c]), np.where(ok, i, 0)
+        zr, zi = mix(x[i, 0], x[i, 1], theta(mm, self.pos_a[c], self.ph_a[c], self.fw[c]))
         return np.where(ok, zr, 0), np.where(ok, zi, 0)
 
-    def update(self, iq):
-        """iq: [n_sources][n_blocks * 128 * D][2].  Returns (I, Q) int16 [n][n_blocks][128]."""
-        iq = np.asarray(iq, dtype=np.int64)
-        N = iq.shape[1]
-        nb = N // (BLOCK * self.D)
-        assert N == nb * BLOCK * self.D
-        for s in range(self.n_src):
-            self.x[s] = np.concatenate([self.x[s], iq[s]])
-        L, n_out = len(self.h), nb * BLOCK
-        m = np.arange(self.P + self.D - L, self.P + N, dtype=np.int64)
+    def outputs(self, n0, n_out):
+        """(I, Q) int16 [n][n_out]: outputs n0 .. n0 + n_out - 1 of every channel as it stands, from the samples held."""
+        L = len(self.h)
+        m = np.arange(n0 * self.D + self.D - L, (n0 + n_out) * self.D, dtype=np.int64)
         I = np.empty((self.n, n_out), dtype=np.int16)
         Q = np.empty_like(I)
         done = {}
@@ -127,5 +156,16 @@ class TunerRef:
                 zr, zi = self.z(c, m)
                 done[key] = (fir_decimate(zr, self.h, self.D, self.g, n_out), fir_decimate(zi, self.h, self.D, self.g, n_out))
             I[c], Q[c] = done[key]
+        return I, Q
+
+    def update(self, iq):
+        """iq: [n_sources][n_blocks * 128 * D][2].  Returns (I, Q) int16 [n][n_blocks][128]."""
+        iq = np.asarray(iq, dtype=np.int64)
+        N = iq.shape[1]
+        nb = N // (BLOCK * self.D)
+        assert N == nb * BLOCK * self.D
+        for s in range(self.n_src):
+            self.x[s] = np.concatenate([self.x[s], iq[s]])
+        I, Q = self.outputs(self.P // self.D, nb * BLOCK)
         self.P += N
         return I.reshape(self.n, nb, BLOCK), Q.reshape(self.n, nb, BLOCK)
