@@ -98,6 +98,13 @@ typedef struct {
   double *acc;                      /* [n_channels] */
 } FcLevelArgs;
 
+/* The palette of a fast-convolution bank (asdr_tuner_palette.hip; include/asdr_tuner.h, "Filter palette and gain"). */
+typedef struct {
+  const float *tab;                 /* [ASDR_TUNER_FC_MAX_FILTERS][256]: G_s[m] at m' = m mod 256 (rows of undefined slots are never read) */
+  const int32_t *slot;              /* [n_channels]: f_c, channel order */
+  const float *gain;                /* [n_channels]: a_c */
+} FcPaletteArgs;
+
 #ifdef __HIP__
 /* The formats' loads (include/asdr_tuner.h, "Input formats"): sample m >= 0 of a row as the CS16 word of x (xr low, xi high).
  * Rows start 16-byte aligned, so the 2-byte formats are read as aligned dwords (two samples) and never as bytes or shorts. */
@@ -148,10 +155,19 @@ extern "C" {
  * kernel, with sp asdr_launch_tuner_spectrum runs between the channel step and the history step. */
 int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLevelArgs *lv,
                                void *stream);
+/* the same with asdr_launch_tuner_channel_palette as the channel step (with or without lv): a bank with a channel off slot 0 or
+ * gain 1 */
+int asdr_launch_tuner_fastconv_palette(const FcForwardArgs *f, const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLevelArgs *lv,
+                                       const FcPaletteArgs *pal, void *stream);
+/* asdr_tuner_palette.hip: the channel step with G from row f_c of the table and a_c in the scale; with lv, the level epilogue and
+ * asdr_launch_tuner_level_fold */
+int asdr_launch_tuner_channel_palette(const FcChannelArgs *c, const FcPaletteArgs *pal, const FcLevelArgs *lv, void *stream);
 /* asdr_tuner_monitor.hip: every source x span of bins of X into the spectrum accumulators; the channel step with the level
  * epilogue, then the fold of the call's partials into the level accumulators */
 int asdr_launch_tuner_spectrum(const FcSpectrumArgs *sp, void *stream);
 int asdr_launch_tuner_channel_levels(const FcChannelArgs *c, const FcLevelArgs *lv, void *stream);
+/* the fold alone: the call's partials [n_frames][n_channels] into the level accumulators */
+int asdr_launch_tuner_level_fold(const FcLevelArgs *lv, int n_channels, int n_frames, void *stream);
 /* the stage-2 step: every channel x 512-output tile (at least one tile: the carry is written even when no block is) */
 int asdr_launch_tuner_resample(const ResampleArgs *a, void *stream);
 /* the filter step (every channel x 128-output block) followed by the history step, in order on `stream` */

@@ -15,6 +15,8 @@
 //  * history: the call's last H samples per source into the other history buffer.
 //  * monitors (asdr_tuner_monitor.hip): when a bank has them on, the launch function below puts that file's
 //    level sibling in the channel kernel's place and its spectrum kernel between the channel step and the history step.
+//  * palette (asdr_tuner_palette.hip): when a bank has a channel off slot 0 or gain 1, the launch function puts
+//    that file's channel step in the place of the channel kernel and of its level sibling.
 //  * input formats (include/asdr_tuner.h): asdr_tuner_fc_forward_kernel / _history_kernel are the CS16 bank's, as
 //    they were.  asdr_tuner_fc_fmt_forward_kernel<F> / asdr_tuner_fc_fmt_history_kernel<F> convert in the window load (asdr_fetch);
 //    a converted value is an integer of at most 16 bits, exact as a float, and everything after the load is the same code.
@@ -347,9 +349,12 @@ int launch_real_forward(const FcForwardArgs *f, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 // the channel step (with the level epilogue when lv is given), then the spectrum monitor when sp is given: X is read once more
-// before the history step, while the channel step's reads still have it in L2 / MALL
-int launch_channel(const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLevelArgs *lv, hipStream_t stream) {
-  if (lv) {
+// before the history step, while the channel step's reads still have it in L2 / MALL.  pal: the bank has a palette in use
+// (asdr_tuner_palette.hip's channel step, with or without lv)
+int launch_channel(const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLevelArgs *lv, const FcPaletteArgs *pal, hipStream_t stream) {
+  if (pal) {
+    if (asdr_launch_tuner_channel_palette(c, pal, lv, stream) != 0) return -1;
+  } else if (lv) {
     if (asdr_launch_tuner_channel_levels(c, lv, stream) != 0) return -1;
   } else {
     hipLaunchKernelGGL(asdr_tuner_fc_channel_kernel, dim3(c->n_channels, c->n_frames), dim3(ASDR_TUNER_FC_CH_LANES), 0, stream, *c);
@@ -361,6 +366,11 @@ int launch_channel(const FcChannelArgs *c, const FcSpectrumArgs *sp, const FcLev
 
 extern "C" int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChannelArgs *c, const FcSpectrumArgs *sp,
                                           const FcLevelArgs *lv, void *stream_) {
+  return asdr_launch_tuner_fastconv_palette(f, c, sp, lv, nullptr, stream_);
+}
+
+extern "C" int asdr_launch_tuner_fastconv_palette(const FcForwardArgs *f, const FcChannelArgs *c, const FcSpectrumArgs *sp,
+                                                  const FcLevelArgs *lv, const FcPaletteArgs *pal, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (f->fmt != ASDR_TUNER_IN_CS16) {
     int rc;
@@ -372,7 +382,7 @@ extern "C" int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChanne
       default: rc = -1;
     }
     if (rc != 0) return -1;
-    if (launch_channel(c, sp, lv, stream) != 0) return -1;
+    if (launch_channel(c, sp, lv, pal, stream) != 0) return -1;
     switch (f->fmt) {
       case ASDR_TUNER_IN_CU8: return launch_fmt_history<ASDR_TUNER_IN_CU8>(f, stream);
       case ASDR_TUNER_IN_CS8: return launch_fmt_history<ASDR_TUNER_IN_CS8>(f, stream);
@@ -391,7 +401,7 @@ extern "C" int asdr_launch_tuner_fastconv(const FcForwardArgs *f, const FcChanne
     hipLaunchKernelGGL(asdr_tuner_fc_forward_kernel, dim3(1 << p.log2n1, p.n_frames, p.n_sources), dim3(ASDR_TUNER_FC_LANES), 0, stream, p);
   }
   if (hipGetLastError() != hipSuccess) return -1;
-  if (launch_channel(c, sp, lv, stream) != 0) return -1;
+  if (launch_channel(c, sp, lv, pal, stream) != 0) return -1;
   hipLaunchKernelGGL(asdr_tuner_fc_history_kernel, dim3((f->hop + 255) / 256, f->n_sources), dim3(256), 0, stream, *f);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

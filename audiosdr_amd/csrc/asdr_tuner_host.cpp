@@ -2,7 +2,8 @@
 // mirror (channel anchors, the source-sorted schedule, the polyphase taps) that is pushed before a launch when a setter touched it;
 // the per-source history rows live on the device only, double-buffered so that the launch that reads one writes the other.
 // Fast-convolution banks share all of it; their stage 1 (asdr_tuner_fastconv.hip) adds the channel filter's response G and the
-// twiddle tables, pushed the same way, and keeps H samples per source in the history rows.
+// twiddle tables, pushed the same way, and keeps H samples per source in the history rows.  A bank with a channel off slot 0 or
+// gain 1 also pushes the palette's table and the channels' slots and gains, and runs asdr_tuner_palette.hip's channel step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -161,6 +162,20 @@ struct asdr_tuner_bank {
   std::vector<float> gch;
   bool g_dirty = true;
   float *d_fc_tab = nullptr;          // [N] W_N, [256] W_256, [256] G (float pairs)
+  // palette and gain (include/asdr_tuner.h, "Filter palette and gain"): slots 1 .. 63 (slot 0 is gch), every channel's slot and
+  // gain in channel order, and how many channels are off (slot 0, gain 1): none -> the bank launches as a bank without a palette.
+  // The device side is allocated by the first call that needs it; pal_dirty has a bit per slot whose row awaits its upload
+  // (bit 0: set with g_dirty), sg_dirty says the same of the slot and gain arrays.
+  struct PaletteSlot { std::vector<float> taps; bool cx = false; int n = 0; };   // n = Lg, 0 = undefined
+  std::vector<PaletteSlot> pal;
+  std::vector<int32_t> slot;
+  std::vector<float> gain;
+  int n_off = 0;
+  uint64_t pal_dirty = 1;
+  bool sg_dirty = true;
+  float *d_pal_tab = nullptr;         // [64][256] float pairs
+  int32_t *d_slot = nullptr;
+  float *d_gain = nullptr;
   float *d_fc_x = nullptr;            // X, then the four-step scratch: [2][n_sources][n_frames][N] float pairs
   size_t fc_x_cap = 0;
   // monitors (fast-convolution banks; include/asdr_tuner.h, "Monitors"): spectrum [n_sources][B] and its frame count; levels
@@ -229,8 +244,32 @@ int retune(asdr_tuner_t *t, int ch, F f) {
   return 0;
 }
 
+// G[m] = sum_n g[n] e^{-j 2 pi m n / 256} in float64, at m' = m mod 256, each part rounded to float; g real [n] or complex [n][2]
+void response(const float *g, int n_taps, bool cx, float *G) {
+  const double pi = 3.14159265358979323846;
+  for (int mp = 0; mp < 256; mp++) {
+    const int m = mp < 128 ? mp : mp - 256;
+    double re = 0.0, im = 0.0;
+    for (int n = 0; n < n_taps; n++) {
+      const double a = 2.0 * pi * (double)(((m * n) % 256 + 256) % 256) / 256.0;
+      if (cx) {   // (gr + j gi) (cos a - j sin a)
+        re += (double)g[2 * n] * std::cos(a) + (double)g[2 * n + 1] * std::sin(a);
+        im += (double)g[2 * n + 1] * std::cos(a) - (double)g[2 * n] * std::sin(a);
+      } else {
+        re += (double)g[n] * std::cos(a);
+        im -= (double)g[n] * std::sin(a);
+      }
+    }
+    G[2 * mp] = (float)re; G[2 * mp + 1] = (float)im;
+  }
+}
+
+// a fast-convolution bank with a channel off (slot 0, gain 1): its channel step is asdr_tuner_palette.hip's
+bool palette_in_use(const asdr_tuner_t *t) { return t->fc && t->n_off > 0; }
+
 int push(asdr_tuner_t *t, hipStream_t stream) {
-  if (!t->chan_dirty && !t->order_dirty && !t->taps_dirty && !(t->fc && t->g_dirty)) return 0;
+  const bool pal_push = palette_in_use(t) && (t->pal_dirty || t->sg_dirty || !t->d_pal_tab || !t->d_slot || !t->d_gain);
+  if (!t->chan_dirty && !t->order_dirty && !t->taps_dirty && !(t->fc && t->g_dirty) && !pal_push) return 0;
   if (t->order_dirty) {
     t->order.resize(t->n);
     for (int i = 0; i < t->n; i++) t->order[i] = i;
@@ -244,20 +283,34 @@ int push(asdr_tuner_t *t, hipStream_t stream) {
     HIPCHK(hipMemcpyAsync(t->d_order, t->order.data(), t->n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
   std::vector<float> G;
-  if (t->fc && t->g_dirty) {   // G[m] = sum_n g[n] e^{-j 2 pi m n / 256} in float64, at m' = m mod 256, rounded to float
-    const double pi = 3.14159265358979323846;
+  if (t->fc && t->g_dirty) {
     G.assign(512, 0.0f);
-    for (int mp = 0; mp < 256; mp++) {
-      const int m = mp < 128 ? mp : mp - 256;
-      double re = 0.0, im = 0.0;
-      for (size_t n = 0; n < t->gch.size(); n++) {
-        const double a = 2.0 * pi * (double)(((m * (int)n) % 256 + 256) % 256) / 256.0;
-        re += (double)t->gch[n] * std::cos(a);
-        im -= (double)t->gch[n] * std::sin(a);
-      }
-      G[2 * mp] = (float)re; G[2 * mp + 1] = (float)im;
-    }
+    response(t->gch.data(), (int)t->gch.size(), false, G.data());
     HIPCHK(hipMemcpyAsync(t->d_fc_tab + 2 * ((1 << t->log2n) + 256), G.data(), G.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+  }
+  std::vector<float> rows;
+  if (pal_push) {   // the rows that changed since their last upload (all defined ones the first time), then the channels' arrays
+    if (!t->d_pal_tab || !t->d_slot || !t->d_gain) {   // each under its own check: a failed allocation is tried again by the next call
+      if (!t->d_pal_tab) HIPCHK(hipMalloc(&t->d_pal_tab, (size_t)ASDR_TUNER_FC_MAX_FILTERS * 512 * sizeof(float)));
+      if (!t->d_slot) HIPCHK(hipMalloc(&t->d_slot, t->n * sizeof(int32_t)));
+      if (!t->d_gain) HIPCHK(hipMalloc(&t->d_gain, t->n * sizeof(float)));
+      t->sg_dirty = true;
+    }
+    int n_rows = 0;   // staging for the rows to upload only: a call that changed gains alone stages nothing
+    for (int k = 0; k < ASDR_TUNER_FC_MAX_FILTERS; k++) n_rows += ((t->pal_dirty >> k) & 1) && (k == 0 || t->pal[k].n > 0);
+    rows.resize((size_t)n_rows * 512);
+    float *row = rows.data();
+    for (int k = 0; k < ASDR_TUNER_FC_MAX_FILTERS; k++) {
+      if (!((t->pal_dirty >> k) & 1) || (k > 0 && t->pal[k].n == 0)) continue;
+      if (k == 0) response(t->gch.data(), (int)t->gch.size(), false, row);
+      else response(t->pal[k].taps.data(), t->pal[k].n, t->pal[k].cx, row);
+      HIPCHK(hipMemcpyAsync(t->d_pal_tab + (size_t)k * 512, row, 512 * sizeof(float), hipMemcpyHostToDevice, stream));
+      row += 512;
+    }
+    if (t->sg_dirty) {
+      HIPCHK(hipMemcpyAsync(t->d_slot, t->slot.data(), t->n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(t->d_gain, t->gain.data(), t->n * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
   }
   std::vector<int32_t> taps;
   if (t->taps_dirty && !t->fc) {
@@ -277,6 +330,7 @@ int push(asdr_tuner_t *t, hipStream_t stream) {
   HIPCHK(hipStreamSynchronize(stream));   // the host mirrors may change as soon as this returns
   t->chan_dirty = t->order_dirty = t->taps_dirty = false;
   if (t->fc) t->g_dirty = false;
+  if (pal_push) { t->pal_dirty = 0; t->sg_dirty = false; }
   return 0;
 }
 
@@ -360,8 +414,14 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16
   sp.window = t->spec_win; sp.mode = t->spec_mode;
   FcLevelArgs lv;
   lv.part = t->d_lev_part; lv.acc = t->d_lev;
-  if (asdr_launch_tuner_fastconv(&f, &c, t->spec_bins ? &sp : nullptr, t->lev_on ? &lv : nullptr, stream) != 0)
+  if (palette_in_use(t)) {   // push() has brought the table and the channels' slots and gains up to date
+    FcPaletteArgs pal;
+    pal.tab = t->d_pal_tab; pal.slot = t->d_slot; pal.gain = t->d_gain;
+    if (asdr_launch_tuner_fastconv_palette(&f, &c, t->spec_bins ? &sp : nullptr, t->lev_on ? &lv : nullptr, &pal, stream) != 0)
+      return fail("fast-convolution kernel launch failed");
+  } else if (asdr_launch_tuner_fastconv(&f, &c, t->spec_bins ? &sp : nullptr, t->lev_on ? &lv : nullptr, stream) != 0) {
     return fail("fast-convolution kernel launch failed");
+  }
   if (t->spec_bins) t->spec_frames += n_frames;
   if (t->lev_on) t->lev_frames += n_frames;
   t->pos += (long long)n_frames * H;
@@ -476,6 +536,9 @@ asdr_tuner_t *create_fastconv(int n_channels, int n_sources, long long fs_in, in
   for (t->log2n = 0; (1 << t->log2n) < 256 * R; t->log2n++) {}
   t->hist_slots = 128 * R;
   t->chan.assign(n_channels, fresh_state());
+  t->pal.resize(ASDR_TUNER_FC_MAX_FILTERS);
+  t->slot.assign(n_channels, 0);
+  t->gain.assign(n_channels, 1.0f);
   default_channel_filter((double)fs_in / R, t->gch);
   default_fastconv_resampler(t->up, t->down, fs_in, R, t->h2, t->g2);
   t->k2 = (int)t->h2.size() / t->up;
@@ -523,6 +586,7 @@ int asdr_tuner_set_channel_filter(asdr_tuner_t *t, const float *g, int n_taps) {
     if (!std::isfinite(g[k])) return fail("channel filter taps must be finite");
   t->gch.assign(g, g + n_taps);
   t->g_dirty = true;
+  t->pal_dirty |= 1;   // slot 0 of the palette's table
   return 0;
 }
 
@@ -542,6 +606,7 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipFree(t->d_chan); hipFree(t->d_order); hipFree(t->d_taps); hipFree(t->d_hist[0]); hipFree(t->d_hist[1]); hipFree(t->d_io);
     hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
     hipFree(t->d_fc_tab); hipFree(t->d_fc_x); hipFree(t->d_spec); hipFree(t->d_lev); hipFree(t->d_lev_part);
+    hipFree(t->d_pal_tab); hipFree(t->d_slot); hipFree(t->d_gain);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -565,6 +630,12 @@ int asdr_tuner_reset(asdr_tuner_t *t) {
   t->carry_stale = false;
   std::fill(t->chan.begin(), t->chan.end(), fresh_state());
   t->chan_dirty = t->order_dirty = true;
+  if (t->fc) {   // every channel back to slot 0 and gain 1; the palette's slots stay
+    std::fill(t->slot.begin(), t->slot.end(), 0);
+    std::fill(t->gain.begin(), t->gain.end(), 1.0f);
+    t->n_off = 0;
+    t->sg_dirty = true;
+  }
   return 0;
 }
 
@@ -990,5 +1061,102 @@ const double *asdr_tuner_levels_device(asdr_tuner_t *t) {
 }
 
 int asdr_tuner_levels_clear(asdr_tuner_t *t) { return asdr_tuner_levels_read(t, nullptr, nullptr, 1); }
+
+}  // extern "C"
+
+// ---- filter palette and gain (include/asdr_tuner.h, "Filter palette and gain")
+namespace {
+const char *kNoPalette = "only a fast-convolution bank has a filter palette and channel gains: a direct-form or rate bank has one integer filter";
+
+bool channel_off(const asdr_tuner_t *t, int c) { return t->slot[c] != 0 || t->gain[c] != 1.0f; }
+
+// f(c) on channel `ch` or on every channel, keeping the count of channels off (slot 0, gain 1)
+template <typename F>
+int each_channel(asdr_tuner_t *t, int ch, F f) {
+  if (ch != ASDR_ALL && (ch < 0 || ch >= t->n)) return fail("bad channel");
+  for (int c = (ch == ASDR_ALL ? 0 : ch); c < (ch == ASDR_ALL ? t->n : ch + 1); c++) {
+    t->n_off -= channel_off(t, c);
+    f(c);
+    t->n_off += channel_off(t, c);
+  }
+  t->sg_dirty = true;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int asdr_tuner_palette_set(asdr_tuner_t *t, int slot, const float *taps, int n_taps, int is_complex) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (slot == 0) return fail("palette slot 0 is the bank's channel filter: use asdr_tuner_set_channel_filter");
+  if (slot < 0 || slot >= ASDR_TUNER_FC_MAX_FILTERS) return fail("palette slot must be in 1..63");
+  if (!taps) return fail("null taps");
+  if (n_taps < 1 || n_taps > ASDR_TUNER_FC_MAX_TAPS) return fail("palette filter length must be in 1..129");
+  const int n_values = is_complex ? 2 * n_taps : n_taps;
+  for (int k = 0; k < n_values; k++)
+    if (!std::isfinite(taps[k])) return fail("palette filter taps must be finite");
+  asdr_tuner_bank::PaletteSlot &p = t->pal[slot];
+  p.taps.assign(taps, taps + n_values);
+  p.cx = is_complex != 0;
+  p.n = n_taps;
+  t->pal_dirty |= 1ull << slot;
+  return 0;
+}
+
+int asdr_tuner_palette_get(const asdr_tuner_t *t, int slot, float *taps, int cap, int *is_complex) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (slot < 0 || slot >= ASDR_TUNER_FC_MAX_FILTERS) return fail("palette slot must be in 0..63");
+  const bool cx = slot != 0 && t->pal[slot].cx;
+  const int L = slot == 0 ? (int)t->gch.size() : t->pal[slot].n;
+  const float *src = slot == 0 ? t->gch.data() : t->pal[slot].taps.data();
+  const int per = cx ? 2 : 1;
+  if (taps) for (int k = 0; k < per * L && k < per * cap; k++) taps[k] = src[k];
+  if (is_complex) *is_complex = cx ? 1 : 0;
+  return L;
+}
+
+int asdr_tuner_palette_clear(asdr_tuner_t *t, int slot) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (slot == 0) return fail("palette slot 0 is the bank's channel filter and cannot be cleared");
+  if (slot < 0 || slot >= ASDR_TUNER_FC_MAX_FILTERS) return fail("palette slot must be in 1..63");
+  for (int c = 0; c < t->n; c++)
+    if (t->slot[c] == slot) return fail("palette slot " + std::to_string(slot) + " is in use by channel " + std::to_string(c));
+  t->pal[slot] = asdr_tuner_bank::PaletteSlot();
+  return 0;
+}
+
+int asdr_tuner_set_channel_slot(asdr_tuner_t *t, int ch, int slot) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (slot < 0 || slot >= ASDR_TUNER_FC_MAX_FILTERS) return fail("palette slot must be in 0..63");
+  if (slot != 0 && t->pal[slot].n == 0) return fail("palette slot " + std::to_string(slot) + " is undefined: asdr_tuner_palette_set");
+  return each_channel(t, ch, [t, slot](int c) { t->slot[c] = slot; });
+}
+
+int asdr_tuner_read_slots(const asdr_tuner_t *t, int32_t *dst) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (!dst) return fail("null destination");
+  memcpy(dst, t->slot.data(), t->n * sizeof(int32_t));
+  return 0;
+}
+
+int asdr_tuner_set_channel_gain(asdr_tuner_t *t, int ch, float gain) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (!std::isfinite(gain) || std::fabs(gain) > ASDR_TUNER_FC_MAX_GAIN) return fail("channel gain must be finite with |gain| <= 32768");
+  return each_channel(t, ch, [t, gain](int c) { t->gain[c] = gain; });
+}
+
+int asdr_tuner_read_gains(const asdr_tuner_t *t, float *dst) {
+  if (!t) return fail("null tuner bank");
+  if (!t->fc) return fail(kNoPalette);
+  if (!dst) return fail("null destination");
+  memcpy(dst, t->gain.data(), t->n * sizeof(float));
+  return 0;
+}
 
 }  // extern "C"

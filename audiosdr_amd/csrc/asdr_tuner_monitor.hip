@@ -202,6 +202,11 @@ extern "C" int asdr_launch_tuner_channel_levels(const FcChannelArgs *c, const Fc
   hipStream_t stream = (hipStream_t)stream_;
   hipLaunchKernelGGL(asdr_tuner_fc_channel_level_kernel, dim3(c->n_channels, c->n_frames), dim3(ASDR_TUNER_FC_CH_LANES), 0, stream, *c, *lv);
   if (hipGetLastError() != hipSuccess) return -1;
-  hipLaunchKernelGGL(asdr_tuner_fc_level_fold_kernel, dim3((c->n_channels + 255) / 256), dim3(256), 0, stream, *lv, c->n_channels, c->n_frames);
+  return asdr_launch_tuner_level_fold(lv, c->n_channels, c->n_frames, stream_);
+}
+
+extern "C" int asdr_launch_tuner_level_fold(const FcLevelArgs *lv, int n_channels, int n_frames, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(asdr_tuner_fc_level_fold_kernel, dim3((n_channels + 255) / 256), dim3(256), 0, stream, *lv, n_channels, n_frames);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -19,11 +19,17 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_spectrum_enable", "asdr_tuner_spectrum_bins", "asdr_tuner_spectrum_window", "asdr_tuner_spectrum_mode",
                  "asdr_tuner_spectrum_read", "asdr_tuner_spectrum_device", "asdr_tuner_spectrum_frames", "asdr_tuner_spectrum_clear",
                  "asdr_tuner_levels_enable", "asdr_tuner_levels_enabled", "asdr_tuner_levels_read", "asdr_tuner_levels_device",
-                 "asdr_tuner_levels_frames", "asdr_tuner_levels_clear"]
+                 "asdr_tuner_levels_frames", "asdr_tuner_levels_clear", "asdr_tuner_palette_set", "asdr_tuner_palette_get",
+                 "asdr_tuner_palette_clear", "asdr_tuner_set_channel_slot", "asdr_tuner_read_slots", "asdr_tuner_set_channel_gain",
+                 "asdr_tuner_read_gains"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
 MAX_CHANNEL_TAPS = 129
+MAX_FILTERS = 64             # palette slots of a fast-convolution bank (include/asdr_tuner.h, "Filter palette and gain")
+MAX_GAIN = 32768.0
+CHANNEL_FILTER_BETA = 7.857  # Kaiser window of the default channel filter: 80 dB
+CHANNEL_FILTER_DELTA = 0.0392   # its transition width for 129 taps, in units of Fs_mid
 # input formats (include/asdr_tuner.h, "Input formats"): name -> (ASDR_TUNER_IN_*, numpy dtype, values per stored sample)
 INPUT_FORMATS = {"cs16": (0, np.int16, 2), "cu8": (1, np.uint8, 2), "cs8": (2, np.int8, 2), "cf32": (3, np.float32, 2),
                  "rs16": (4, np.int16, 1)}
@@ -86,6 +92,13 @@ def _lib():
         getattr(L, "asdr_tuner_%s_device" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_device" % n).restype = vp
         getattr(L, "asdr_tuner_%s_frames" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_frames" % n).restype = ll
     L.asdr_tuner_levels_enable.argtypes = [vp, i]; L.asdr_tuner_levels_enable.restype = i
+    L.asdr_tuner_palette_set.argtypes = [vp, i, fp, i, i]; L.asdr_tuner_palette_set.restype = i
+    L.asdr_tuner_palette_get.argtypes = [vp, i, fp, i, ip]; L.asdr_tuner_palette_get.restype = i
+    L.asdr_tuner_palette_clear.argtypes = [vp, i]; L.asdr_tuner_palette_clear.restype = i
+    L.asdr_tuner_set_channel_slot.argtypes = [vp, i, i]; L.asdr_tuner_set_channel_slot.restype = i
+    L.asdr_tuner_read_slots.argtypes = [vp, C.POINTER(C.c_int32)]; L.asdr_tuner_read_slots.restype = i
+    L.asdr_tuner_set_channel_gain.argtypes = [vp, i, C.c_float]; L.asdr_tuner_set_channel_gain.restype = i
+    L.asdr_tuner_read_gains.argtypes = [vp, fp]; L.asdr_tuner_read_gains.restype = i
     _typed = True
     return L
 
@@ -146,6 +159,32 @@ def spectrum_frequencies(fs_in, n_bins):
     return np.where(j < n_bins // 2, j, j - n_bins) * (float(fs_in) / n_bins)
 
 
+def design_channel_filter(fs_mid, lo_hz, hi_hz):
+    """129 taps at fs_mid for a palette slot (TunerBank.set_palette_filter) that passes [lo_hz, hi_hz] about the tuned frequency:
+    the default channel filter's design with another passband.  A low-pass prototype -- Kaiser window (beta 7.857: 80 dB), sum of
+    the taps 1, cut-off (hi - lo) / 2 + fs_mid / 512 + delta / 2 with delta = 0.0392 fs_mid, the window's transition width --
+    modulated to the centre (lo + hi) / 2 about tap 64.  The fs_mid / 512 on each side is there because the filter acts at a
+    tone's offset from the channel's coarse bin, up to that far from its offset from the tuned frequency.  Flat over [lo, hi]
+    whatever the residual tuning; 80 dB down beyond delta + fs_mid / 512 outside it.  complex64 [129]; float32 when lo = -hi.
+    delta is 1.7 kHz at 44.1 kHz and 5.9 kHz at 150 kHz: this chooses among bandwidths of a few kHz and up, and sidedness."""
+    fs_mid, lo, hi = float(fs_mid), float(lo_hz), float(hi_hz)
+    L = MAX_CHANNEL_TAPS
+    if not (fs_mid > 0 and lo < hi):
+        raise AsdrError("design_channel_filter: needs fs_mid > 0 and lo_hz < hi_hz")
+    fc = (0.5 * (hi - lo) + fs_mid / 512.0 + 0.5 * CHANNEL_FILTER_DELTA * fs_mid) / fs_mid
+    if not (fc < 0.5 and -0.5 * fs_mid <= lo and hi <= 0.5 * fs_mid):
+        raise AsdrError("design_channel_filter: [%g, %g] Hz with its transition does not fit fs_mid = %g Hz" % (lo, hi, fs_mid))
+    n = np.arange(L, dtype=np.float64)
+    x = n - 0.5 * (L - 1)
+    u = 2.0 * n / (L - 1) - 1.0
+    proto = np.where(x == 0, 2.0 * fc, np.sin(2.0 * np.pi * fc * x) / (np.pi * np.where(x == 0, 1.0, x)))
+    proto = proto * np.i0(CHANNEL_FILTER_BETA * np.sqrt(np.maximum(0.0, 1.0 - u * u))) / np.i0(CHANNEL_FILTER_BETA)
+    proto = proto / proto.sum()
+    if lo == -hi:
+        return proto.astype(np.float32)
+    return (proto * np.exp(2j * np.pi * (0.5 * (lo + hi) / fs_mid) * x)).astype(np.complex64)
+
+
 class _DeviceRows:
     """A device allocation as a __cuda_array_interface__ object, so that torch.as_tensor wraps it without a copy."""
 
@@ -198,6 +237,51 @@ class TunerBank:
         g = np.zeros(n, dtype=np.float32)
         self._chk(self._L.asdr_tuner_get_channel_filter(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), n))
         return g
+
+    # filter palette and gain of a fast-convolution bank (include/asdr_tuner.h, "Filter palette and gain")
+    def set_palette_filter(self, slot, taps):
+        """Define (or redefine) slot 1..63: 1..129 taps at Fs_mid; a complex dtype gives complex taps, anything else real ones.
+        Applies to the frames of the next update call, for every channel on the slot."""
+        taps = np.asarray(taps)
+        cx = np.iscomplexobj(taps)
+        taps = np.ascontiguousarray(taps, dtype=np.complex64 if cx else np.float32).reshape(-1)
+        self._chk(self._L.asdr_tuner_palette_set(self._h, int(slot), taps.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)),
+                                                 int(taps.size), int(cx)))
+
+    def get_palette_filter(self, slot):
+        """The slot's taps, float32 or complex64 [Lg]; None for an undefined slot.  Slot 0 is the channel filter."""
+        cx = C.c_int()
+        n = self._chk(self._L.asdr_tuner_palette_get(self._h, int(slot), None, 0, C.byref(cx)))
+        if n == 0:
+            return None
+        g = np.zeros(n, dtype=np.complex64 if cx.value else np.float32)
+        self._chk(self._L.asdr_tuner_palette_get(self._h, int(slot), g.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)), n, None))
+        return g
+
+    def clear_palette_filter(self, slot):
+        """Slot 1..63 back to undefined; refused while a channel is on it."""
+        self._chk(self._L.asdr_tuner_palette_clear(self._h, int(slot)))
+
+    def set_channel_slot(self, slot, ch=ALL):
+        """The channel's filter is the palette's slot (0, the bank's channel filter, or a defined one) from the next update call."""
+        self._chk(self._L.asdr_tuner_set_channel_slot(self._h, int(ch), int(slot)))
+
+    def slots(self):
+        """int32 [n_channels]."""
+        out = np.zeros(self.n_channels, dtype=np.int32)
+        self._chk(self._L.asdr_tuner_read_slots(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def set_gain(self, gain, ch=ALL):
+        """The channel's output is multiplied by gain (finite, |gain| <= 32768) before the rounding, from the next update call;
+        the level monitor reads the signal without it."""
+        self._chk(self._L.asdr_tuner_set_channel_gain(self._h, int(ch), float(gain)))
+
+    def gains(self):
+        """float32 [n_channels]."""
+        out = np.zeros(self.n_channels, dtype=np.float32)
+        self._chk(self._L.asdr_tuner_read_gains(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -115,6 +115,32 @@
  *             asdr_tuner_reset clears both monitors and keeps their configuration; retunes, filter and format changes touch
  *             neither.  Direct-form and rate banks have no X: every monitor function fails on them (asdr_last_error).  An
  *             ASDR_NO_DEVICE bank takes the configuration calls and fails the reads, the clears and the device getters.
+ *
+ * Filter palette and gain (fast-convolution banks only; everything not named here is unchanged).  In the frequency domain another
+ * filter for a channel is another row of a small table: a bank holds up to 64 responses and every channel names one, and a gain.
+ *   palette   slots 0 .. 63 (ASDR_TUNER_FC_MAX_FILTERS).  Slot 0 is the bank's channel filter: the default, or what
+ *             asdr_tuner_set_channel_filter set; only that function touches it.  Slots 1 .. 63 are undefined at creation.  A slot
+ *             holds Lg taps, 1 <= Lg <= 129, at Fs_mid, real or complex (interleaved re, im floats); its response is
+ *             G_s[m] = sum_n g[n] e^{-j 2 pi m n / 256}, m in [-128, 128), computed in float64 with each part rounded to float:
+ *             the rule of "filter" above, with complex g.
+ *   channel   a slot f_c and a gain a_c; 0 and 1.0 at creation.  a_c is a finite float with |a_c| <= 32768; negative values and
+ *             zero are allowed.  In the "output" line G[m] becomes G_{f_c}[m]; after the 1 / N scale and the coarse sign y is
+ *             multiplied by a_c; then the fine NCO, the rounding and the clamp follow as stated there.
+ *   level     the level monitor takes y with G_{f_c} but without a_c: the level is the signal's, so a change of gain needs no
+ *             recalibration.
+ *   timing    setting a channel's slot, defining a slot, redefining a slot (every channel on it follows) and setting a gain apply
+ *             to the frames of the next update call.  No history is flushed and no NCO re-anchored: overlap-save keeps no
+ *             per-channel state.  asdr_tuner_reset puts every channel back to slot 0 and gain 1 (the creation state) and keeps the
+ *             palette's slots, as it keeps the filter.
+ *   place     as today the filter acts at a tone's offset from the coarse bin, at most Fs_mid / 512 from the tuned frequency: a
+ *             passband meant for [lo, hi] about the tuned frequency should be Fs_mid / 512 wider on each side.
+ *   sharpness 129 taps at Fs_mid set the transition width: 0.0392 Fs_mid for 80 dB, i.e. 1.7 kHz at Fs_mid = 44.1 kHz and 5.9 kHz
+ *             at 150 kHz.  The palette chooses among bandwidths of a few kHz and up, and sidedness (a complex slot states a
+ *             one-sided SSB passband, which real taps cannot); it is not a 100 Hz CW filter.  An R that puts Fs_mid near 44.1 -
+ *             75 kHz gives the sharper filters.
+ *   cost      a bank whose channels are all on slot 0 at gain 1 launches and allocates exactly as before; any other bank runs
+ *             one other channel kernel in the old one's place.  A channel on slot 0 at gain 1 of such a bank
+ *             is written bit for bit as before.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -135,6 +161,8 @@ extern "C" {
 #define ASDR_TUNER_MAX_RESAMPLER_TAPS 64 /* K, taps per phase */
 #define ASDR_TUNER_FC_MAX_R 1024
 #define ASDR_TUNER_FC_MAX_TAPS 129       /* Lg, channel filter taps of a fast-convolution bank */
+#define ASDR_TUNER_FC_MAX_FILTERS 64     /* palette slots of a fast-convolution bank; slot 0 is the channel filter */
+#define ASDR_TUNER_FC_MAX_GAIN 32768.0f  /* |a_c| at most */
 #define ASDR_TUNER_IN_CS16 0             /* input formats (the table above) */
 #define ASDR_TUNER_IN_CU8 1
 #define ASDR_TUNER_IN_CS8 2
@@ -255,6 +283,22 @@ int asdr_tuner_levels_read(asdr_tuner_t *t, double *dst, long long *frames, int 
 const double *asdr_tuner_levels_device(asdr_tuner_t *t);
 long long asdr_tuner_levels_frames(const asdr_tuner_t *t);
 int asdr_tuner_levels_clear(asdr_tuner_t *t);
+
+/* Filter palette and gain (the section above).  All fail on a bank that is not a fast-convolution bank; an ASDR_NO_DEVICE bank
+ * takes all of them.  Setters return 0 / -1; a rejected call keeps the old state.
+ * palette_set: slot in 1 .. 63 (slot 0 belongs to asdr_tuner_set_channel_filter); n_taps = Lg in 1 .. 129; taps holds Lg floats, or
+ * 2 Lg (re, im) when is_complex != 0; every value finite.  Redefining a slot is allowed while channels are on it.
+ * palette_get: slot in 0 .. 63; copies min(Lg, cap) taps (cap counts taps: pairs of floats for a complex slot) to taps (if not
+ * NULL) and 0 / 1 to *is_complex (if not NULL); returns Lg, 0 for an undefined slot, -1 on error.  Slot 0 reads the channel filter.
+ * palette_clear: slot in 1 .. 63 back to undefined; fails while a channel is on it.
+ * set_channel_slot: ch or ASDR_ALL; the slot must be 0 or defined.  set_channel_gain: finite, |gain| <= 32768. */
+int asdr_tuner_palette_set(asdr_tuner_t *t, int slot, const float *taps, int n_taps, int is_complex);
+int asdr_tuner_palette_get(const asdr_tuner_t *t, int slot, float *taps, int cap, int *is_complex);
+int asdr_tuner_palette_clear(asdr_tuner_t *t, int slot);
+int asdr_tuner_set_channel_slot(asdr_tuner_t *t, int ch, int slot);
+int asdr_tuner_read_slots(const asdr_tuner_t *t, int32_t *dst /* [n_channels] */);
+int asdr_tuner_set_channel_gain(asdr_tuner_t *t, int ch, float gain);
+int asdr_tuner_read_gains(const asdr_tuner_t *t, float *dst /* [n_channels] */);
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */

@@ -20,6 +20,9 @@
   R64z      R64's signal as CS16 with zero Q (what such a source had to be blown up to before), for comparison
   F4m       F4 with both monitors on (include/asdr_tuner.h, "Monitors"): spectrum of 4,096 bins, hann, sum, and the levels
   F20m      F20 with both monitors on, likewise; run beside F4 / F20 in one process: monitors off is the code path without them
+  F4p       F4 with a palette in use (include/asdr_tuner.h, "Filter palette and gain"): channel c on slot c mod 4 -- the default
+            filter, +-5 kHz, 300 .. 3000 Hz, -3000 .. -300 Hz (design_channel_filter at Fs_mid = 150 kHz) -- at gain 1, 0.5, 2, -1,
+            4 by c mod 5; F4's inputs.  Run beside F4 in one process: F4 is the code path without the palette
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
@@ -29,7 +32,7 @@ time per call over call time.  The first call of each config is checked against 
 channels.  Fast-convolution banks (F*) have no operation model here (DESIGN.md 3.8.2 counts them); their first call is checked
 against tests/tuner_fastconv_ref.py, a float64 statement, so "parity" there means every sample within +-2.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z F4m F20m]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z F4m F20m F4p]
 """
 import json
 import os
@@ -45,6 +48,7 @@ import torch  # noqa: E402  (first: one HIP runtime per process, INTEGRATION.md 
 import audiosdr_amd as A  # noqa: E402
 import tuner_fastconv_ref as FR  # noqa: E402
 import tuner_formats_ref as FM  # noqa: E402
+import tuner_palette_ref as PR  # noqa: E402
 import tuner_rate_ref as RR  # noqa: E402
 import tuner_ref as R  # noqa: E402
 
@@ -69,13 +73,18 @@ CONFIGS = {
     "R64z": dict(n_src=1, D=512, n_ch=512, L=None, nb=16, fs_in=64800000, fastconv=True, real=True, seed=648),
     "F4m": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, monitors=True, seed=sum(map(ord, "F4"))),
     "F20m": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, monitors=True, seed=sum(map(ord, "F20"))),
+    "F4p": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, palette=True, seed=sum(map(ord, "F4"))),
 }
+PALETTE_BANDS = [None, (-5000.0, 5000.0), (300.0, 3000.0), (-3000.0, -300.0)]   # slot 0 is the default filter
+PALETTE_GAINS = [1.0, 0.5, 2.0, -1.0, 4.0]
 
 
-def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None, monitors=False):
+def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None, monitors=False,
+        palette=False):
     """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank.
     fmt: the bank's input format (rows go through update_samples_device); real: CS16 rows with zero Q; monitors: the spectrum
-    (4,096 bins, hann, sum) and the levels of a fast-convolution bank are on."""
+    (4,096 bins, hann, sum) and the levels of a fast-convolution bank are on; palette: channel c is on slot c mod 4 of
+    PALETTE_BANDS at gain PALETTE_GAINS[c mod 5]."""
     rng = np.random.default_rng(sum(map(ord, name)) if seed is None else seed)
     bank = A.TunerBank.fastconv(n_ch, n_src, fs_in, D) if fastconv else A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
     bank.set_input_format(fmt)
@@ -92,6 +101,12 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
     fws = rng.integers(0, 2**32, size=n_ch, dtype=np.uint64)
     for c in range(n_ch):
         bank.set_source(int(srcs[c]), ch=c); bank.set_frequency_word(int(fws[c]), ch=c)
+    if palette:
+        for k, band in enumerate(PALETTE_BANDS):
+            if band:
+                bank.set_palette_filter(k, A.design_channel_filter(fs_in / D, *band))
+        for c in range(n_ch):
+            bank.set_channel_slot(c % len(PALETTE_BANDS), ch=c); bank.set_gain(PALETTE_GAINS[c % len(PALETTE_GAINS)], ch=c)
     N = nb * 128 * D
     calls = 4                                              # distinct seeded inputs, cycled
     if fmt == "rs16" or real:
@@ -136,7 +151,13 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
     check = sorted(set([0, 1, n_ch - 1] + [int(c) for c in rng.integers(0, n_ch, size=5)]))
     if fastconv:
         h2, g2 = bank.get_resampler()
-        ref = FR.TunerFastconvRef(len(check), n_src, fs_in, D, h, h2, g2)
+        ref = (PR.TunerPaletteRef if palette else FR.TunerFastconvRef)(len(check), n_src, fs_in, D, h, h2, g2)
+        if palette:
+            for k, band in enumerate(PALETTE_BANDS):
+                if band:
+                    ref.set_palette_filter(k, bank.get_palette_filter(k))
+            for i, c in enumerate(check):
+                ref.set_channel_slot(c % len(PALETTE_BANDS), ch=i); ref.set_gain(PALETTE_GAINS[c % len(PALETTE_GAINS)], ch=i)
     elif rate:
         h2, g2 = bank.get_resampler()
         ref = RR.TunerRateRef(len(check), n_src, D, fs_in, h, g, h2, g2)
@@ -198,6 +219,9 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
            "parity_channels": len(check), "parity": parity}
     if fastconv:
         out.update({"kind": "fastconv", "fft_size": bank.fft_size(), "parity_max_abs_diff": dmax})
+    if palette:
+        out.update({"palette": {"slots_in_use": sorted(set(int(v) for v in bank.slots())), "bands_hz": PALETTE_BANDS,
+                                "gains": PALETTE_GAINS}})
     if monitors:
         spec, frames = bank.spectrum()
         lev, lframes = bank.levels()
