@@ -54,7 +54,7 @@ _GETTERS_I = ["getMute", "getAudioFilter", "ALSfilterIsEnabled", "ALSfilterIsNot
 # every symbol include/asdr.h declares (checked by the CPU test-suite against the built library)
 EXPORTS = (["asdr_create", "asdr_destroy", "asdr_last_error", "asdr_n_channels", "asdr_update", "asdr_update_device",
             "asdr_synchronize", "asdr_setDemodMode", "asdr_getDemodMode", "asdr_setALSfilterParams", "asdr_getAGClookup",
-            "asdr_read_status", "asdr_control_plane_flush", "asdr_get_chain_constants", "asdr_stream_pipeline_launches", "asdr_schedule_layout", "asdr_set_exact_unknown_mode", "asdr_get_exact_unknown_mode", "asdr_stream_pipeline_recoveries", "asdr_stream_pipeline_max_groups", "asdr_set_stream_fir_helpers", "asdr_stream_pipeline_h3_calls", "asdr_set_stream_pipeline", "asdr_set_sam_launch_form", "asdr_set_als_launch_form", "asdr_debug_set_stream_spin_limit", "asdr_debug_set_stream_max_groups", "asdr_enable_taps", "asdr_read_taps", "asdr_last_kernel_ms", "asdr_version",
+            "asdr_read_status", "asdr_control_plane_flush", "asdr_params_uniform_groups", "asdr_get_chain_constants", "asdr_stream_pipeline_launches", "asdr_schedule_layout", "asdr_set_exact_unknown_mode", "asdr_get_exact_unknown_mode", "asdr_stream_pipeline_recoveries", "asdr_stream_pipeline_max_groups", "asdr_set_stream_fir_helpers", "asdr_stream_pipeline_h3_calls", "asdr_set_stream_pipeline", "asdr_set_sam_launch_form", "asdr_set_als_launch_form", "asdr_debug_set_stream_spin_limit", "asdr_debug_set_stream_max_groups", "asdr_enable_taps", "asdr_read_taps", "asdr_last_kernel_ms", "asdr_version",
             "asdr_kernel_timing_begin", "asdr_kernel_timing_end", "asdr_set_launch_timing", "asdr_region_timing_begin", "asdr_region_timing_end", "asdr_update_device_strided", "asdr_capture_open",
             "asdr_capture_close", "asdr_capture_capacity", "asdr_capture_position", "asdr_capture_rewind",
             "asdr_capture_device_ptr", "asdr_capture_update_device", "asdr_capture_read",
@@ -151,6 +151,8 @@ def load_library(path=None):
         L.asdr_get_chain_constants.argtypes = [vp, _i, C.POINTER(C.c_float)]; L.asdr_get_chain_constants.restype = C.c_uint
     if path is None or hasattr(L, "asdr_control_plane_flush"):   # older builds timed by tools/ablate.py lack it
         L.asdr_control_plane_flush.argtypes = [vp, C.POINTER(C.c_longlong)]; L.asdr_control_plane_flush.restype = _i
+    if path is None or hasattr(L, "asdr_params_uniform_groups"):
+        L.asdr_params_uniform_groups.argtypes = [vp, C.POINTER(C.c_long)]; L.asdr_params_uniform_groups.restype = _i
     L.asdr_enable_taps.argtypes = [vp, _i]; L.asdr_enable_taps.restype = _i
     L.asdr_read_taps.argtypes = [vp, fp]; L.asdr_read_taps.restype = _i
     L.asdr_kernel_timing_begin.argtypes = [vp, _i]; L.asdr_kernel_timing_begin.restype = _i
@@ -387,6 +389,15 @@ class AudioSDRBatch:
         self._chk(self._L.asdr_control_plane_flush(self._h, st))
         return {"rows_refilled": int(st[0]), "schedule_rebuilt": bool(st[1]), "waves_plain": int(st[2]) & 0x1FFFFF,
                 "waves_sam": (int(st[2]) >> 21) & 0x1FFFFF, "waves_als": (int(st[2]) >> 42) & 0x1FFFFF, "agc_tables_alive": int(st[3])}
+
+    def params_uniform_groups(self):
+        """(settings groups whose parameter rows are equal -- their large launches carry the row as launch constants --, parameter rows
+        compared so far to know it), as of the last flush (include/asdr.h)."""
+        rows = C.c_long(0)
+        g = int(self._L.asdr_params_uniform_groups(self._h, C.byref(rows)))
+        if g < 0:
+            self._chk(g)
+        return g, int(rows.value)
 
     def last_kernel_ms(self):
         return float(self._L.asdr_last_kernel_ms(self._h))

@@ -196,6 +196,10 @@ typedef struct {
   LoEntry *lo_ring;       /* [ASDR_LO_RING] the streaming pipeline's oscillator role leaves block b's pairs in entry b % ASDR_LO_RING;
                              its progress counter is stream_prog[3 * stream_waves] */
   ChainConsts k;
+  ChanParams uni;         /* uni_valid: the parameter row of EVERY channel of the direct launch's settings group (asdr_host.cpp params_uniform: the
+                             rows are equal in every field the kernels read) -- launch constants instead of a row of `params` per lane */
+  uint32_t uni_valid;     /* 1: `uni` is filled and the launcher may take the instantiation that reads it (asdr_update_kernel_mw_u) */
+  uint32_t pad_uni_;
 } UpdateArgs;
 #define ASDR_ALS_STAGE_SLOTS 32  /* ALS role streams: slots of UpdateArgs.als_stage per channel (16 KB) */
 #define ASDR_ALS_CHUNK 8         /* ... and blocks per chain / filter launch: the chain launches run up to STAGE_SLOTS / CHUNK - 2 chunks ahead */

@@ -220,6 +220,16 @@ struct asdr_batch {
   int kind_first[ASDR_KERNEL_KINDS] = {}, kind_slots[ASDR_KERNEL_KINDS] = {}, kind_uniform_slots[ASDR_KERNEL_KINDS] = {};
   int left_first = 0, left_slots = 0, left_kind = ASDR_KERNEL_PLAIN;   // the key groups' remainders of all kinds: one sub-range, one launch
   bool kind_direct[ASDR_KERNEL_KINDS] = {};   // the uniform part is ONE key group of consecutive channel ids (checked when the schedule is built)
+  // params_uniform: the rows of hp of a kind's direct group (kind_direct) are equal in every field the kernels read -- such a group's
+  // direct launches carry the row as launch constants (UpdateArgs.uni).  Kept incrementally: puni_differs[c] = channel c's row differs
+  // from the row of its group's first channel, puni_diff[k] = how many of kind k's group do.  A per-channel setter costs ONE row
+  // comparison at the next flush; a whole pass over a group's rows runs only after a bulk refill (broadcast setters), a schedule
+  // rebuild or a change of the group's first row -- never at a flush or launch with no setter in front of it.
+  bool kind_puni[ASDR_KERNEL_KINDS] = {}, puni_recheck[ASDR_KERNEL_KINDS] = {};
+  long puni_diff[ASDR_KERNEL_KINDS] = {};
+  std::vector<uint8_t> puni_differs;
+  long stat_puni_rows_compared = 0;    // rows compared so far (asdr_params_uniform_groups)
+  bool uniform_params = true;          // (ASDR_NO_UNIFORM_PARAMS: off, for measurements and tests)
   // counters for the control-plane tests (ASDR_NO_DEVICE): what the last flush did
   long stat_rows_refilled = 0, stat_sched_rebuilds = 0, stat_bulk_uploads = 0;
   int stat_lo_groups_without_entry = 0;   // settings groups that mix early but got none of the ASDR_LO_ENTRIES cache entries (the smallest ones)
@@ -493,6 +503,38 @@ void mark_dirty(asdr_batch *b, int i) {
   if (b->dirty.size() > (size_t)b->n / 8 + 64) { b->all_dirty = true; }   // a bulk refill is cheaper from here on
 }
 
+// params_uniform (asdr_batch::kind_puni).  The comparison covers every field a kernel reads: `reset` is consumed by the reset kernel in
+// front of the launch, the padding is never read.
+inline bool params_rows_equal(const ChanParams &x, const ChanParams &y) {
+  return memcmp(&x, &y, offsetof(ChanParams, reset)) == 0 &&
+         memcmp(&x.if_table, &y.if_table, offsetof(ChanParams, pad_) - offsetof(ChanParams, if_table)) == 0;
+}
+// one pass over the rows of kind k's direct group
+void puni_pass(asdr_batch *b, int k) {
+  b->puni_recheck[k] = false; b->puni_diff[k] = 0; b->kind_puni[k] = false;
+  if (!b->kind_direct[k]) return;
+  const int ch0 = b->sched[b->kind_first[k]].ch, nu = b->kind_uniform_slots[k];
+  const ChanParams &r = b->hp[ch0];
+  long diff = 0;
+  for (int c = ch0; c < ch0 + nu; c++) { const uint8_t d = params_rows_equal(b->hp[c], r) ? 0 : 1; b->puni_differs[c] = d; diff += d; }
+  b->stat_puni_rows_compared += nu;
+  b->puni_diff[k] = diff; b->kind_puni[k] = (diff == 0);
+}
+// channel c's row was refilled: one comparison against its group's first row (that row itself: the group is passed over again)
+void puni_row_changed(asdr_batch *b, int c) {
+  for (int k = 0; k < ASDR_KERNEL_KINDS; k++) {
+    if (!b->kind_direct[k] || b->puni_recheck[k]) continue;
+    const int ch0 = b->sched[b->kind_first[k]].ch;
+    if (c < ch0 || c >= ch0 + b->kind_uniform_slots[k]) continue;
+    if (c == ch0) { b->puni_recheck[k] = true; return; }
+    const uint8_t d = params_rows_equal(b->hp[c], b->hp[ch0]) ? 0 : 1;
+    b->stat_puni_rows_compared++;
+    b->puni_diff[k] += (long)d - (long)b->puni_differs[c]; b->puni_differs[c] = d;
+    b->kind_puni[k] = (b->puni_diff[k] == 0);
+    return;
+  }
+}
+
 // Host half of flush(): refill the parameter rows that changed, decide whether the schedule has to be rebuilt, rebuild it.
 // Returns the sorted list of refilled rows in `rows_out` (empty + all_dirty = every row).  No HIP call in here, so the
 // control-plane tests can time it on a device-less batch.
@@ -510,6 +552,7 @@ void flush_host(asdr_batch *b, std::vector<int32_t> &rows_out, bool &bulk, bool 
     }
     b->stat_rows_refilled = rows;
     b->stat_bulk_uploads++;
+    for (int k = 0; k < ASDR_KERNEL_KINDS; k++) b->puni_recheck[k] = true;
   } else if (!b->dirty.empty()) {
     std::sort(b->dirty.begin(), b->dirty.end());
     for (int32_t i : b->dirty) {
@@ -518,6 +561,7 @@ void flush_host(asdr_batch *b, std::vector<int32_t> &rows_out, bool &bulk, bool 
       if (sched_key(b->hp[i]) != old_key) b->sched_dirty = true;
       b->dirty_flag[i] = 0;
     }
+    if (!b->sched_dirty) for (int32_t i : b->dirty) if (i < b->n) puni_row_changed(b, i);   // (a rebuilt schedule: every group is passed over below)
     rows_out = b->dirty;
     b->stat_rows_refilled = (long)rows_out.size();
   }
@@ -641,7 +685,9 @@ void flush_host(asdr_batch *b, std::vector<int32_t> &rows_out, bool &bulk, bool 
     b->sched_dirty = false;
     sched_rebuilt = true;
     b->stat_sched_rebuilds++;
+    for (int k = 0; k < ASDR_KERNEL_KINDS; k++) b->puni_recheck[k] = true;
   }
+  for (int k = 0; k < ASDR_KERNEL_KINDS; k++) if (b->puni_recheck[k]) puni_pass(b, k);
 }
 
 int flush(asdr_batch *b, hipStream_t stream) {
@@ -695,6 +741,13 @@ void fill_args(asdr_batch *b, UpdateArgs &a) {
   a.nb_phase = b->nb_phase; a.als_phase = b->als_phase;
   a.lo_cache = b->d_lo; a.lo_parity = b->lo_parity; a.lo_write = 0; a.lo_writer_bit = ASDR_LO_WRITER;
   a.k = b->k;
+}
+
+// a direct launch of (a piece of) the group whose first channel is ch0: the group's one parameter row as launch constants, when it has one
+void set_uni(asdr_batch *b, UpdateArgs &a, int ch0) {
+  const int k = kernel_kind(b->hp[ch0]);
+  a.uni_valid = 0u;
+  if (b->uniform_params && b->kind_direct[k] && b->kind_puni[k] && b->sched[b->kind_first[k]].ch == ch0) { a.uni = b->hp[ch0]; a.uni_valid = 1u; }
 }
 
 int apply_resets(asdr_batch *b, hipStream_t stream) {
@@ -914,6 +967,7 @@ asdr_batch_t *asdr_create(int n_channels, int device) {
   b->sam_fused = getenv("ASDR_SAM_FUSED") != nullptr;
   b->sam_split_min = getenv("ASDR_SAM_SPLIT_MIN") ? atoi(getenv("ASDR_SAM_SPLIT_MIN")) : ASDR_SAM_SPLIT_MIN_CHANNELS;
   b->stream_pipeline = getenv("ASDR_NO_STREAM_PIPELINE") == nullptr;
+  b->uniform_params = getenv("ASDR_NO_UNIFORM_PARAMS") == nullptr;
   b->als_split_min = getenv("ASDR_ALS_SPLIT_MIN") ? atoi(getenv("ASDR_ALS_SPLIT_MIN")) : 0x7fffffff;
   if (getenv("ASDR_LAUNCH_SPLIT")) b->launch_split = std::max(1, std::min(atoi(getenv("ASDR_LAUNCH_SPLIT")), 8));
   if (getenv("ASDR_LAUNCH_SPLIT_MIN_WAVES")) b->launch_split_min_waves = std::max(8, atoi(getenv("ASDR_LAUNCH_SPLIT_MIN_WAVES")));
@@ -1011,6 +1065,7 @@ asdr_batch_t *asdr_create(int n_channels, int device) {
   b->hp.resize(rows);
   memset(b->hp.data(), 0, rows * sizeof(ChanParams));
   b->dirty_flag.assign(rows, 0);
+  b->puni_differs.assign(rows, 0);
   b->reset.assign(rows, ASDR_R_ALL);
   b->reset_lo = 0; b->reset_hi = (int)rows - 1;
   for (size_t i = 0; i < rows; i++) chan_init(b, (int)i);  // constructor -> init()
@@ -1263,8 +1318,8 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     HIPCHK(hipMemsetAsync(b->d_stream_prog, 0, (size_t)(3 * w + 1) * sizeof(uint32_t), stream));   // stream-ordered behind the previous launch
     if (n_sub > 1) HIPCHK(hipEventRecord(b->ev_fork, stream));
     a.sched = b->d_sched + subs[pipe_sub].first; a.n_sched = subs[pipe_sub].slots;
-    a.direct_ch0 = -1;
-    if (b->kind_direct[ASDR_KERNEL_PLAIN]) { const SlotInfo &s0 = b->sched[subs[pipe_sub].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; }
+    a.direct_ch0 = -1; a.uni_valid = 0u;
+    if (b->kind_direct[ASDR_KERNEL_PLAIN]) { const SlotInfo &s0 = b->sched[subs[pipe_sub].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
     a.lo_write = 0u;
     a.xch_a = b->d_xch_a; a.xch_b = b->d_xch_b; a.xch_c = b->d_xch_b + (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * ASDR_N; a.stream_prog = b->d_stream_prog; a.stream_err = b->d_stream_prog + 3 * ((b->n + 7) / 8) + 1;
     a.stream_waves = w; a.lo_ring = b->d_lo_ring; a.stream_spin_limit = b->stream_spin_limit;
@@ -1291,8 +1346,8 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
         if (!s) return fail("stream creation failed");
         HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
         UpdateArgs o = a_side;
-        o.sched = b->d_sched + subs[i].first; o.n_sched = subs[i].slots; o.direct_ch0 = -1; o.lo_write = 1u;
-        if (subs[i].uniform && b->kind_direct[subs[i].kind]) { const SlotInfo &s0 = b->sched[subs[i].first]; o.direct_ch0 = s0.ch; o.direct_mode = s0.mode; o.direct_flags = s0.flags; o.direct_lo = s0.lo; }
+        o.sched = b->d_sched + subs[i].first; o.n_sched = subs[i].slots; o.direct_ch0 = -1; o.uni_valid = 0u; o.lo_write = 1u;
+        if (subs[i].uniform && b->kind_direct[subs[i].kind]) { const SlotInfo &s0 = b->sched[subs[i].first]; o.direct_ch0 = s0.ch; o.direct_mode = s0.mode; o.direct_flags = s0.flags; o.direct_lo = s0.lo; set_uni(b, o, s0.ch); }
         if (asdr_launch_update(&o, subs[i].kind, subs[i].uniform, s) != 0) return fail("update kernel launch failed");
         HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
       }
@@ -1340,8 +1395,8 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
           if (cnt == 0) continue;
           UpdateArgs al = a;
           al.sched = b->d_sched + first; al.n_sched = cnt;
-          al.direct_ch0 = -1;
-          if (su.uniform && b->kind_direct[su.kind]) { const SlotInfo &s0 = b->sched[su.first]; al.direct_ch0 = s0.ch + lo; al.direct_mode = s0.mode; al.direct_flags = s0.flags; al.direct_lo = s0.lo; }
+          al.direct_ch0 = -1; al.uni_valid = 0u;
+          if (su.uniform && b->kind_direct[su.kind]) { const SlotInfo &s0 = b->sched[su.first]; al.direct_ch0 = s0.ch + lo; al.direct_mode = s0.mode; al.direct_flags = s0.flags; al.direct_lo = s0.lo; set_uni(b, al, s0.ch); }
           al.lo_cache = b->d_lo + (size_t)(1 + (l % ASDR_LANES)) * 2 * ASDR_LO_ENTRIES;   // this lane's own set: its writers fill it, its waves read it (general-kernel waves have no entry)
           al.lo_write = 1u;
           al.lo_writer_bit = ASDR_LO_WRITER_LANE(l % ASDR_LANES);   // (lane 0: ASDR_LO_WRITER; a direct launch: its wave 0, under any name)
@@ -1418,8 +1473,8 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     for (int i = 0; i < 3 * R; i++) if (!b->ev_samc[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_samc[i], hipEventDisableTiming));
     const int i0 = items[0].sub, first0 = items[0].first;
     const size_t slots = b->xch_sam_chunk_slots;
-    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.lo_write = 1u;
-    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; }
+    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.uni_valid = 0u; a.lo_write = 1u;
+    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
     a.xch_sam = b->d_xch_sam_chunk; a.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam_chunk + (size_t)S * slots * 2 * ASDR_N);
     a.sam_sets = (uint32_t)S; a.sam_set_stride = (uint32_t)(slots * 2 * ASDR_N); a.sam_lock_stride = (uint32_t)slots;
     a.taps = nullptr;
@@ -1469,8 +1524,8 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     HIPCHK(hipEventRecord(b->ev_fork, stream));
     HIPCHK(hipStreamWaitEvent(s_chain, b->ev_fork, 0));
     const int i0 = items[0].sub, first0 = items[0].first;
-    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.lo_write = 1u;
-    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; }
+    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.uni_valid = 0u; a.lo_write = 1u;
+    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
     // the stage's "previous block" slot of the call's first block: the als_x ring's other slot as the last call left it
     a.als_stage = b->d_als_stage; a.als_stage_cur = 0u; a.als_stage_prev = (uint32_t)(S - 1); a.als_phase = b->als_phase;
     if (asdr_launch_als_stage_seed(&a, 0, b->n, s_chain) != 0) return fail("update kernel launch failed");
@@ -1530,11 +1585,11 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
       if (!s && it != main_item) return fail("stream creation failed");
       if (it != main_item) HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
       a.sched = b->d_sched + first; a.n_sched = items[it].slots;
-      a.direct_ch0 = -1;
+      a.direct_ch0 = -1; a.uni_valid = 0u;
       a.lo_write = 1u;   // the first wave of every settings group fills the group's entry of the other half of the local-oscillator cache
       if (subs[i].uniform && b->kind_direct[subs[i].kind]) {   // one key group of consecutive channels: no schedule reads in the waves
         const SlotInfo &s0 = b->sched[subs[i].first];
-        a.direct_ch0 = s0.ch + (first - subs[i].first); a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo;
+        a.direct_ch0 = s0.ch + (first - subs[i].first); a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch);
         if (first != subs[i].first) a.lo_write = 0u;   // (a direct launch's wave 0 is the writer: only the piece that holds the group's first wave)
       }
       const bool sam3 = sam_split && (subs[i].kind == ASDR_KERNEL_SAM || subs[i].kind == ASDR_KERNEL_SAM_ALS);
@@ -2546,6 +2601,20 @@ int asdr_schedule_layout(asdr_batch_t *b, int out[8]) {
   for (int k = 0; k < ASDR_KERNEL_KINDS; k++) out[k] = b->kind_slots[k];
   out[5] = b->left_slots; out[6] = b->left_slots ? b->left_kind : -1; out[7] = (b->sam_split ? 1 : 0) | (b->als_split ? 2 : 0);
   return 0;
+}
+
+int asdr_params_uniform_groups(asdr_batch_t *b, long *rows_compared) {
+  if (!b) return fail("null batch");
+  if (is_sharded(b)) {
+    int acc = 0; long rows = 0;
+    for (asdr_batch *sh : b->shards) { long r = 0; const int g = asdr_params_uniform_groups(sh, &r); if (g < 0) return -1; acc += g; rows += r; }
+    if (rows_compared) *rows_compared = rows;
+    return acc;
+  }
+  int g = 0;
+  for (int k = 0; k < ASDR_KERNEL_KINDS; k++) g += (b->kind_direct[k] && b->kind_puni[k]) ? 1 : 0;
+  if (rows_compared) *rows_compared = b->stat_puni_rows_compared;
+  return g;
 }
 
 int asdr_control_plane_flush(asdr_batch_t *b, long long stats[4]) {

@@ -1166,7 +1166,7 @@ __device__ __forceinline__ void als_compute(float *L, bool als_en, bool adaptive
 // call of a large schedule block by block -- and always the SAM / two-launch ALS roles).  The block loop below is then no loop at all:
 // nothing is loop-invariant, so nothing is hoisted in front of the body and kept in registers across all of it (lane masks, cache-entry
 // addresses, flag words: the plain kernel's 66 SGPR spills and 8 of its VGPRs were exactly that).
-template <int STRIDE, bool HAS_ALS, bool HAS_SAM, bool UNIFORM, int WAVES, int ROLE = 0, bool ONEBLK_ = false, int FIR_HELPERS = 1>
+template <int STRIDE, bool HAS_ALS, bool HAS_SAM, bool UNIFORM, int WAVES, int ROLE = 0, bool ONEBLK_ = false, int FIR_HELPERS = 1, bool UPAR = false>
 __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds_wg) {
   // ROLE 4 / 5: the SAM sub-range as three launches -- 4 = everything in front of the PLL (scale, blanker, IF filter), then the
   // stand-alone PLL kernel (asdr_sam_pll_kernel: one LANE per channel, 64 channels per wave -- the PLL is a 128-step dependent chain
@@ -1269,6 +1269,9 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   const int loff_ = c8 * STRIDE;
 #define P (*Pp)
   const ChainConsts K = a.k;
+  // UPAR: a launch constant that is an operand of a hot loop goes to a VGPR where the loop starts (tools/ubench/issue_rate.hip: a stream dense in
+  // scalar operands does not share a SIMD) -- the constants replace loads and address arithmetic, not the loops' operands
+  auto pv = [](float x) -> float { if constexpr (UPAR) asm volatile("" : "+v"(x)); return x; };
 
   const uint32_t mode = UNIFORM ? (uint32_t)__builtin_amdgcn_readfirstlane(slot.y) : (uint32_t)slot.y;
   const uint32_t pflags = UNIFORM ? (uint32_t)__builtin_amdgcn_readfirstlane(slot.z) : (uint32_t)slot.z;
@@ -1354,7 +1357,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       if (need_in) { seen_in = stream_wait(prog + (ROLE - 2) * a.stream_waves + wave_g, b1, err, a.stream_spin_limit); if (seen_in == ASDR_STREAM_FAIL) break; }   // the previous role has stored block blk
       if (need_free) { seen_free = stream_wait(prog + ROLE * a.stream_waves + wave_g, freed, err, a.stream_spin_limit); if (seen_free == ASDR_STREAM_FAIL) break; }   // the next role has left slot blk % DEPTH
     }
-    const ChanParams *Pp = row_ptr(a.params, (uint32_t)ch * (uint32_t)sizeof(ChanParams));
+    // UPAR: the group's parameter rows are identical (UpdateArgs.uni): launch constants, no lane loads a row of a.params
+    const ChanParams *Pp = UPAR ? &a.uni : row_ptr(a.params, (uint32_t)ch * (uint32_t)sizeof(ChanParams));
     ChanSmall *S = row_ptr(a.small, (uint32_t)ch * (uint32_t)sizeof(ChanSmall));
     float *L = lds + loff;
     int *Li = reinterpret_cast<int *>(L);
@@ -1374,8 +1378,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #define PL_CH(c) (__builtin_amdgcn_ds_bpermute((c) << 5, ch))   /* lane 8 c holds channel c's index */
 #define Sp row_ptr(a.small, (uint32_t)PL_CH(pl_c) * (uint32_t)sizeof(ChanSmall))
 #define Spa row_ptr(a.small, (uint32_t)PL_CH(pa_c) * (uint32_t)sizeof(ChanSmall))
-#define Ppl row_ptr(a.params, (uint32_t)PL_CH(pl_c) * (uint32_t)sizeof(ChanParams))
-#define Ppa row_ptr(a.params, (uint32_t)PL_CH(pa_c) * (uint32_t)sizeof(ChanParams))
+#define Ppl (UPAR ? &a.uni : row_ptr(a.params, (uint32_t)PL_CH(pl_c) * (uint32_t)sizeof(ChanParams)))
+#define Ppa (UPAR ? &a.uni : row_ptr(a.params, (uint32_t)PL_CH(pa_c) * (uint32_t)sizeof(ChanParams)))
 #define Lp (lds + pl_c * STRIDE)
 #define Lpa (lds + pa_c * STRIDE)
 #else   /* round 5's lanes: a channel's cascades on its own eight lanes */
@@ -1493,7 +1497,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     uint32_t mkc[5] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};   // defined on every path
     float gain_i, gain_q;
     if (ROLE == 1 && ASDR_STREAM_R1_CARRY && blk > 0) { gain_i = r1_gain_i; gain_q = r1_gain_q; }
-    else { gain_i = P.in_gain_i; gain_q = P.in_gain_q; if (ROLE == 1) { r1_gain_i = gain_i; r1_gain_q = gain_q; } }
+    else { gain_i = pv(P.in_gain_i); gain_q = pv(P.in_gain_q); if (ROLE == 1) { r1_gain_i = gain_i; r1_gain_q = gain_q; } }
     float g_oi = gain_i, g_oq = gain_q, g_mi = 0.0f, g_mq = 0.0f, nb_avg0 = 0.0f;
     uint32_t agc_hc_early = 0u, agc_hang_early = 0u;
     bool agc_piped = false;   // (the four-wave form: the AGC duty runs the lean chain beside the audio duty: see the audio filter)
@@ -1554,7 +1558,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     if (nb_wave) {
       // (the newest block goes to its ring slot after the envelopes, below)
     } else if (DO1) {
-      const bool unit_in = UNIT_OK && __all(gain_i == 1.0f && gain_q == 1.0f);
+      const bool unit_in = UNIT_OK && (UPAR ? (a.uni.in_gain_i == 1.0f && a.uni.in_gain_q == 1.0f) : __all(gain_i == 1.0f && gain_q == 1.0f));   // (launch constants: a scalar test)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         float xi[8], xq[8];
@@ -1898,7 +1902,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       // VGPRs for the whole kernel): bit 15 - (8h + j) <-> this lane's sample kA + 64h + j of the middle block / bit 7 - j <-> 64 + kA + j of the oldest
       uint32_t fm = 0u, ft = 0u;
       if (nb_en) {
-        const float thr = nb_thr;
+        const float thr = pv(nb_thr);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           float av[8];
@@ -2454,7 +2458,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           const int chq = mw_channel(16 * (mw_rel - 1) + mw_casc);
           mw_af_S = row_ptr(a.small, (uint32_t)chq * (uint32_t)sizeof(ChanSmall));
           af_s4 = *reinterpret_cast<const float4 *>(&mw_af_S->af_state[4 * pl_st]);
-          const float *cf = &c_bq_pool[row_ptr(a.params, (uint32_t)chq * (uint32_t)sizeof(ChanParams))->audio_table][5 * pl_st];
+          const float *cf = &c_bq_pool[(UPAR ? &a.uni : row_ptr(a.params, (uint32_t)chq * (uint32_t)sizeof(ChanParams)))->audio_table][5 * pl_st];
 #pragma unroll
           for (int z = 0; z < 5; ++z) af_cf[z] = cf[z];
         }
@@ -2586,7 +2590,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           r2_pref = true;
         }
       }
-      constexpr bool IDL_EARLY = (ROLE == 2);   // the pipeline's role 2 has the registers to request the delayed I before the FIR
+#ifndef ASDR_UPAR_IDL_EARLY
+#define ASDR_UPAR_IDL_EARLY 1   /* the launch-constant form requests the delayed I before the FIR too: the registers its parameter row no longer takes */
+#endif
+      constexpr bool IDL_EARLY = (ROLE == 2) || (UPAR && ASDR_UPAR_IDL_EARLY != 0);   // the pipeline's role 2 and the launch-constant form have the registers to request the delayed I before the FIR
       if (IDL_EARLY && is_ssb) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) load4(hi_ring + (hs ^ 1u) * 128 + 32 * m, idl + 4 * m);
@@ -3160,7 +3167,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             } else {
             const int chq = mw_channel(q);
             ChanSmall *Sq = row_ptr(a.small, (uint32_t)chq * (uint32_t)sizeof(ChanSmall));
-            const ChanParams *Pq = row_ptr(a.params, (uint32_t)chq * (uint32_t)sizeof(ChanParams));
+            const ChanParams *Pq = UPAR ? &a.uni : row_ptr(a.params, (uint32_t)chq * (uint32_t)sizeof(ChanParams));
             mwx[MWX * q + 7] = agc_chain(std::false_type{}, lds_wg + q * STRIDE, Sq, Sq->agc_old_abs, Sq->agc_hang_counter, Sq->agc_gain, Pq->agc_alpha_att, Pq->agc_beta_att,
                                        Pq->agc_alpha_rel, Pq->agc_beta_rel, Pq->agc_hang_count, is_am, mwx[MWX * q + 6]);
             }
@@ -3352,7 +3359,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     }
     {
       // ---- output, AudioSDR.cpp:158-161: float product, x 32767.0 in binary64, truncate, wrap to int16 ------
-      const float og = P.output_gain;
+      const float og = pv(P.output_gain);
       union { int4 v; int16_t s[8]; } ro[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -3463,6 +3470,12 @@ extern "C" __global__ __launch_bounds__(64, 4) void asdr_update_kernel_c16(Updat
 extern "C" __global__ __launch_bounds__(64 * ASDR_MW_WAVES, ASDR_WAVES_PER_EU) void asdr_update_kernel_mw(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[ASDR_MW_WAVES * 8 * ASDR_STRIDE + ASDR_MW_WAVES * 8 * 16 + 260 + 12];   // rows | hand-off scratch | sine table | progress words | flags
   asdr_update_body<ASDR_STRIDE, false, false, true, ASDR_MW_WAVES, 0, true>(a, lds);
+}
+// ... whose settings group has ONE parameter row (UpdateArgs.uni_valid: receivers configured by broadcast setters): the row is a launch
+// constant, the table rows are addressed from it and no lane reads a.params
+extern "C" __global__ __launch_bounds__(64 * ASDR_MW_WAVES, ASDR_WAVES_PER_EU) void asdr_update_kernel_mw_u(UpdateArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[ASDR_MW_WAVES * 8 * ASDR_STRIDE + ASDR_MW_WAVES * 8 * 16 + 260 + 12];
+  asdr_update_body<ASDR_STRIDE, false, false, true, ASDR_MW_WAVES, 0, true, 1, true>(a, lds);
 }
 // SAM: 4 waves = 32 channels per workgroup (50,704 B of LDS -> 3 workgroups = 12 waves per CU), general form only
 ASDR_KERNEL(asdr_update_kernel_sam, ASDR_SAM_WAVES * 8 * ASDR_STRIDE + 260, ASDR_WAVES_PER_EU, ASDR_STRIDE, false, true, false, ASDR_SAM_WAVES)
@@ -3835,6 +3848,7 @@ static const char *const k_kernel_names[] = {
   "asdr_update_kernel_c16",
   "asdr_update_kernel_mixed",
   "asdr_update_kernel_mw",
+  "asdr_update_kernel_mw_u",
   "asdr_update_kernel_one",
   "asdr_update_kernel_sam"
 };
@@ -3989,6 +4003,9 @@ extern "C" int asdr_launch_update(const UpdateArgs *a, int variant, int uniform,
     const bool ssb_class = dm == ASDR_USBmode || dm == ASDR_LSBmode || dm == ASDR_CW_USBmode || dm == ASDR_CW_LSBmode || dm == ASDR_WSPRmode;
     if (uniform && c16_on && a->n_blocks == 1 && a->run_if == nullptr && a->direct_ch0 >= 0 && a->taps == nullptr && ssb_class && n_waves >= c16_min)
       ASDR_LAUNCH(asdr_update_kernel_c16, dim3(n_waves), dim3(64), (size_t)c16_pad, stream, *a);   // (c16_pad: dynamic LDS that takes the occupancy back, measurements)
+    else
+    if (uniform && mw_on && a->n_blocks == 1 && a->run_if == nullptr && a->direct_ch0 >= 0 && n_waves >= mw_min && a->uni_valid)
+      ASDR_LAUNCH(asdr_update_kernel_mw_u, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a);
     else
     if (uniform && mw_on && a->n_blocks == 1 && a->run_if == nullptr && a->direct_ch0 >= 0 && n_waves >= mw_min)
       ASDR_LAUNCH(asdr_update_kernel_mw, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a);

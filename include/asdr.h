@@ -328,6 +328,15 @@ int asdr_kernel_timing_end(asdr_batch_t *b, float *ms, int cap);
  *   stats[0] = parameter rows refilled, stats[1] = 1 if the schedule was rebuilt, stats[2] = waves in the plain / SAM / ALS
  *   sub-ranges (ALS: the three kinds with the filter enabled together) packed as plain | sam << 21 | als << 42, stats[3] = AGC gain tables alive in the pool. */
 int asdr_control_plane_flush(asdr_batch_t *b, long long stats[4]);
+/* Launch constants for banks configured together.  A settings group of consecutive channels whose parameter rows are equal in every
+ * field the kernels read (`params_uniform`: receivers set up by broadcast setters, ch = ASDR_ALL) has its large one-block launches
+ * carry that row in the kernel arguments (asdr_update_kernel_mw_u) instead of every lane loading its channel's row; a per-channel
+ * setter that makes one row differ sends the group back to the kernels that read the rows, and a setter that makes the rows equal
+ * again brings it back.  Results are the same bit for bit either way; ASDR_NO_UNIFORM_PARAMS=1 in the environment when the batch is
+ * created keeps the form off.  Returns the number of such groups as of the last flush (update() or asdr_control_plane_flush());
+ * *rows_compared (may be NULL) = parameter rows compared so far to keep that knowledge: one per row a per-channel setter changed, a
+ * group's rows after a broadcast setter or a schedule rebuild, none at a flush with no setter in front of it. */
+int asdr_params_uniform_groups(asdr_batch_t *b, long *rows_compared);
 /* The derived constants the hot path runs with, as the host evaluated them from the reference's in-class initialisers and
  * setters (AudioSDR.h:238-239, 249-284; AudioSDR.cpp:447, 563-566) -- exposed so that an independent restatement of that
  * arithmetic can pin them bit for bit (tests/test_control_plane_independent.py).  out[12] = pll_b0, pll_b1, pll_a1, alpha_freq,
