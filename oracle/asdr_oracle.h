@@ -117,6 +117,8 @@ float ao_getAGClookup(const asdr_oracle_t *o, int i);
 float ao_getAGCstaticGain(const asdr_oracle_t *o);
 float ao_getAMcarrierLevel(const asdr_oracle_t *o);
 uint32_t ao_getAGChangCount(const asdr_oracle_t *o); /* not in the reference API; test aid */
+uint32_t ao_test_get_agc_hang_counter(const asdr_oracle_t *o); /* test aids: the running hang counter (.cpp:420, 423) ... */
+float ao_test_get_agc_envelope(const asdr_oracle_t *o);            /* ... and the envelope (_agc_oldAbs), after the last block */
 
 void ao_enableNoiseBlanker(asdr_oracle_t *o);
 void ao_disableNoiseBlanker(asdr_oracle_t *o);

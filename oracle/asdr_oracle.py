@@ -92,6 +92,8 @@ def lib():
         sig("ao_" + n, [], f32)
     sig("ao_getAGClookup", [i32], f32)
     sig("ao_getAGChangCount", [], C.c_uint32)
+    sig("ao_test_get_agc_hang_counter", [], C.c_uint32)
+    sig("ao_test_get_agc_envelope", [], f32)
     sig("ao_getDemodMode", [], C.c_int16)
     for n in ["getMute", "getAudioFilter", "ALSfilterIsEnabled", "ALSfilterIsNotch", "ALSfilterIsPeak",
               "ALSfilterIsAdaptive", "AGCisEnabled", "AGCisActive", "NoiseBlankerisEnabled", "NoiseBlankerDetection",
@@ -176,6 +178,10 @@ class OracleSDR:
         out = np.zeros(12, dtype=np.float32)
         self._L.ao_get_chain_constants(self._h, _fp(out))
         return int(self._L.ao_getAGChangCount(self._h)), out
+
+    def agc_running(self):
+        """(running hang counter, envelope) as the last block left them: test aid, read-only."""
+        return int(self._L.ao_test_get_agc_hang_counter(self._h)), float(self._L.ao_test_get_agc_envelope(self._h))
 
     def set_unknown_mode_silence(self, on=True):
         """Model the HIP product's defined difference for unknown mode values (oracle/asdr_oracle.h)."""
