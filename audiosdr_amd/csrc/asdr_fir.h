@@ -55,4 +55,49 @@ __device__ __forceinline__ void hilbert_fir_rows(const float *hist, int p0, v2f 
     }
   }
 }
+
+// The same sums with SLIDING windows in a closed register ring, for the four-wave update kernels (all eight output pairs of a lane).  Tap T of the
+// output pair e reads D[63 - T + e] and U[T + e], D[t] = PX[64 + p0 + t], U[t] = PX[p0 + t]: from tap to tap the down window moves one pair down, the up
+// window one pair up.  Pair t of a window lives in register pair t mod 16 -- the eight live ones plus the pieces requested ahead -- and every second tap
+// requests one 16-byte piece per window, the pairs that taps T + 4 .. T + 6 bring in: no tap waits on a read issued less than four taps before it, and the
+// FIR issues 2 x (6 + 32) = 76 LDS reads where the chunked form issues 8 x 16 and drains them eight times.  Sixteen taps move a window by exactly 16 pairs, so a trip of 16
+// taps closes the register naming: 4 trips, one load of 16 taps each (a scalar load shares its counter with the LDS reads: inside a trip it would drain them).
+// The last trip's last two requests bring in pairs no tap uses (D[-4 .. -1], U[72 .. 75]: words 2 p0 + 120 .. 127 and 2 p0 + 144 .. 151 <= 263 of the row).
+// D[71], requested with D[70] in front of the loop, ends at word 383 for the last lane of a channel: inside the row, the value unused.
+// Per accumulator the same sub, mul, add on the same operands in the same order as above: bit-identical.
+__device__ __forceinline__ void hilbert_fir_rows_ring(const float *hist, int p0, v2f *acc2, const float *taps) {
+  constexpr int NE = 8;
+  const v2f *PD = reinterpret_cast<const v2f *>(hist) + 64 + p0;   // D[0]
+  const v2f *PU = reinterpret_cast<const v2f *>(hist) + p0;        // U[0]
+  v2f D[16], U[16];   // D[t] at D[t & 15], U[t] at U[t & 15]
+  auto ld2 = [](const v2f *p, v2f &a, v2f &b) { const float4 q = *reinterpret_cast<const float4 *>(p); a = (v2f){q.x, q.y}; b = (v2f){q.z, q.w}; };
+  // taps 0..3: D[60..70] and U[0..10], whole 16-byte pieces
+#pragma unroll
+  for (int t = 60; t < 72; t += 2) ld2(PD + t, D[t & 15], D[(t + 1) & 15]);
+#pragma unroll
+  for (int t = 0; t < 12; t += 2) ld2(PU + t, U[t], U[t + 1]);
+#pragma unroll 1
+  for (int tc = 0; tc < 4; ++tc) {
+    float h[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) h[i] = taps[16 * tc + i];
+#pragma unroll
+    for (int tt = 0; tt < 16; ++tt) {   // tap T = 16 tc + tt
+      if ((tt & 1) == 0) {   // D[58 - T], D[59 - T] and U[12 + T], U[13 + T]
+        ld2(PD + 58 - tt, D[(58 - tt) & 15], D[(59 - tt) & 15]);
+        ld2(PU + 12 + tt, U[(12 + tt) & 15], U[(13 + tt) & 15]);
+      }
+      const v2f hk2 = (v2f){h[tt], h[tt]};
+      v2f d[NE];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) d[e] = D[(63 - tt + e) & 15] - U[(tt + e) & 15];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) d[e] = hk2 * d[e];
+#pragma unroll
+      for (int e = 0; e < NE; ++e) acc2[e] += d[e];
+      if ((tt & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // (the requests stay where they are written: nothing is asked for more than two taps early)
+    }
+    PD -= 16; PU += 16;
+  }
+}
 #endif

@@ -865,6 +865,36 @@ template <int E0, int NE, bool TAPS_V = (ASDR_FIR_TAPS_IN_VGPRS != 0)>
 __device__ __forceinline__ void hilbert_fir(const float *Lrow, int p0, v2f *acc2) {
   hilbert_fir_rows<E0, NE, TAPS_V>(Lrow + XP, p0, acc2, c_hilbert);
 }
+// ... and of the four-wave kernels: sliding windows in a register ring (asdr_fir.h).
+#ifndef ASDR_MW_FIR_RING
+#define ASDR_MW_FIR_RING 1   /* 0: the four-wave kernels run the chunked FIR of every other form (measurements) */
+#endif
+#ifndef ASDR_MW_HIST_B128
+#define ASDR_MW_HIST_B128 0   /* 1: the four-wave kernels stage the Hilbert history with one LDS store per 16 bytes (hilbert_hist_store16: 12 ds_write_b128 for 38 stores).  Built,
+                                 bit-exact, measured (profiles/README.md): 28 LDS instructions and 288 bank-conflict cycles fewer per wave, 35 DPP moves / selects and 36 register
+                                 moves more -- +0.6 % alone, +0.8 % on top of the ring FIR, every run above every run of the build without it -- off */
+#endif
+__device__ __forceinline__ void hilbert_fir_ring(const float *Lrow, int p0, v2f *acc2) {
+  hilbert_fir_rows_ring(Lrow + XP, p0, acc2, c_hilbert);
+}
+// One block of the Hilbert history, 16-byte stores.  v[4 m + j] = x[B + kF + 32 m + j] goes to word B + kF + 32 m + j - 1: the aligned piece at word
+// B + kF + 32 m holds this lane's j = 1..3 and the j = 0 of the lane that follows in the channel (DPP row_shl:1, lane i <- lane i + 1) or, behind the
+// channel's last lane, the first lane's j = 0 of piece m + 1 (row_shr:7, lane i <- lane i - 7; next0 = v[0] of the block that follows).  All 64 lanes run it.
+// LAST: no block follows -- the seam word of piece 3 is word 383, which nothing reads.
+template <bool LAST>
+__device__ __forceinline__ void hilbert_hist_store16(float *dst, const float *v, float next0, bool seam) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    float w = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[4 * m]), 0x101, 0xF, 0xF, true));
+    float p1 = v[4 * m + 1], p2 = v[4 * m + 2], p3 = v[4 * m + 3];
+    asm volatile("" : "+v"(p1), "+v"(p2), "+v"(p3));   // (the piece is put together HERE: a register quadruple that starts at j = 1 from the load on costs a fifth register per piece while the block waits)
+    if (!(LAST && m == 3)) {
+      const float s = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m < 3 ? v[4 * m + 4] : next0), 0x117, 0xF, 0xF, true));
+      w = seam ? s : w;
+    }
+    *reinterpret_cast<float4 *>(dst + 32 * m) = make_float4(p1, p2, p3, w);
+  }
+}
 // Second wave of a role-2 workgroup of the streaming pipeline: nothing but the other half of the FIR, in step with the first
 // wave's three barriers per block (history staged | all reads done | both halves in W1).
 // E0, NE: this wave's output pairs (round 6: asdr_stream_kernel_h3 runs THREE helper waves beside the role wave, two pairs each).
@@ -2545,6 +2575,14 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             load4(hq_ring + (hs ^ 1u) * 128 + 32 * m, hq_m + 4 * m);
           }
         }
+        constexpr bool HIST_B128 = MW && WAVES == 4 && (ASDR_MW_HIST_B128 != 0);   // (is_ssb is wave-uniform there: every lane is here for the DPP moves)
+        if constexpr (HIST_B128) {
+          hilbert_hist_store16<false>(L + XP + kF, hq_o, hq_m[0], s8 == 7);
+          __builtin_amdgcn_sched_barrier(0);   // (block by block: a block's registers are free before the next one's pieces are put together)
+          hilbert_hist_store16<false>(L + XP + 128 + kF, hq_m, qn[0], s8 == 7);
+          __builtin_amdgcn_sched_barrier(0);
+          hilbert_hist_store16<true>(L + XP + 256 + kF, qn, 0.0f, s8 == 7);
+        } else {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -2554,10 +2592,13 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             L[XP + 127 + k] = hq_m[4 * m + j];
           }
         }
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
+          if constexpr (!HIST_B128) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) L[XP + 255 + kF + 32 * m + j] = qn[4 * m + j];
+          }
 #ifndef ASDR_TEMPORAL_RINGS
           store4_nt(hq_ring + hs * 128 + 32 * m, qn + 4 * m);
 #else
@@ -2606,7 +2647,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #pragma unroll
       for (int e = 0; e < FIR_NE; ++e) acc2[e] = (v2f){0.0f, 0.0f};
       if (ROLE == 2) __syncthreads();   // the history is staged: the helper may read it
-      if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir<0, FIR_NE>(L, k0 >> 1, acc2);
+      if constexpr (MW && WAVES == 4 && ASDR_MW_FIR_RING != 0 && ASDR_FIR_TAPS_IN_VGPRS == 0) { if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir_ring(L, k0 >> 1, acc2); }
+      else if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir<0, FIR_NE>(L, k0 >> 1, acc2);
       if (ROLE == 2) __syncthreads(); else WAVE_SYNC();   // all history reads done: rows W0/W1 may overwrite the start of the history
       TL(9);
       if (!IDL_EARLY && is_ssb) {   // delayed I = previous block's mixed I (:111); requested here: the FIR has no registers to spare for it
