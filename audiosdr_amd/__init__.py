@@ -12,7 +12,8 @@ from .binding import (STREAM_BATCH, AGCfast, AGCmedium, AGCoff, AGCslow, ALL, AM
                       library_sha256, load_library, host_alloc, host_free)
 from .front import (NO_DEVICE, AudioGrabberComplex256Batch, AudioIQgeneratorBatch, AudioSDRpreProcessorBatch,  # noqa: E402
                     FRONT_EXPORTS)
-from .tuner import (TUNER_EXPORTS, TUNER_STATE_DTYPE, TunerBank, design_channel_filter, fastconv_ratio, rate_ratio,  # noqa: E402
-                    spectrum_frequencies, suggest_decimation, suggest_fft_decimation)
+from .tuner import (IQ_CORRECTION_DTYPE, IQ_IDENTITY, IQ_STATS_DTYPE, TUNER_EXPORTS, TUNER_STATE_DTYPE, TunerBank,  # noqa: E402
+                    design_channel_filter, estimate_iq_correction, fastconv_ratio, rate_ratio, spectrum_frequencies,
+                    suggest_decimation, suggest_fft_decimation)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -105,6 +105,24 @@ typedef struct {
   const float *gain;                /* [n_channels]: a_c */
 } FcPaletteArgs;
 
+/* Source conditioning (asdr_tuner_condition.hip; include/asdr_tuner.h, "Source conditioning"): the pre-pass over the call's rows. */
+#define ASDR_TUNER_COND_LANES 256     /* a lane takes 16 bytes of output (or of input, whichever is more) per step */
+#define ASDR_TUNER_COND_MAX_BLOCKS 2048   /* grid cap (x times y); a workgroup strides over the rest of its row */
+#define ASDR_TUNER_IQ_STATS_WORDS 7   /* asdr_tuner_iq_stats_t: n, sum_re, sum_im, sum_re2, sum_im2, sum_reim, clipped */
+
+typedef struct {
+  const void *in;                   /* [n_sources][in_stride] samples of format fmt: the caller's rows */
+  void *out;                        /* [n_sources][out_stride]: x' as CS16 words (RS16: int16); NULL = the rows are only read */
+  const int32_t *corr;              /* [n_sources][4]: d_r, d_i, p, g (read only when out is given) */
+  unsigned long long *stats;        /* [n_sources][7]: the int64 sums of asdr_tuner_iq_stats_t, two's complement; NULL = off */
+  int64_t in_stride, out_stride;    /* samples */
+  int64_t n_samples;                /* per row: a multiple of 128 */
+  int32_t n_sources;
+  int32_t fmt;                      /* ASDR_TUNER_IN_* of the caller's rows */
+  int32_t aligned;                  /* every row of `in` starts 16-byte aligned (always so but for CS16 rows through the int16 entry
+                                       points, whose stride is any number of samples) */
+} ConditionArgs;
+
 #ifdef __HIP__
 /* The formats' loads (include/asdr_tuner.h, "Input formats"): sample m >= 0 of a row as the CS16 word of x (xr low, xi high).
  * Rows start 16-byte aligned, so the 2-byte formats are read as aligned dwords (two samples) and never as bytes or shorts. */
@@ -168,6 +186,8 @@ int asdr_launch_tuner_spectrum(const FcSpectrumArgs *sp, void *stream);
 int asdr_launch_tuner_channel_levels(const FcChannelArgs *c, const FcLevelArgs *lv, void *stream);
 /* the fold alone: the call's partials [n_frames][n_channels] into the level accumulators */
 int asdr_launch_tuner_level_fold(const FcLevelArgs *lv, int n_channels, int n_frames, void *stream);
+/* asdr_tuner_condition.hip: the pre-pass (out and / or stats given) on `stream` */
+int asdr_launch_tuner_condition(const ConditionArgs *a, void *stream);
 /* the stage-2 step: every channel x 512-output tile (at least one tile: the carry is written even when no block is) */
 int asdr_launch_tuner_resample(const ResampleArgs *a, void *stream);
 /* the filter step (every channel x 128-output block) followed by the history step, in order on `stream` */

@@ -4,6 +4,8 @@
 // Fast-convolution banks share all of it; their stage 1 (asdr_tuner_fastconv.hip) adds the channel filter's response G and the
 // twiddle tables, pushed the same way, and keeps H samples per source in the history rows.  A bank with a channel off slot 0 or
 // gain 1 also pushes the palette's table and the channels' slots and gains, and runs asdr_tuner_palette.hip's channel step.
+// Source conditioning (asdr_tuner_condition.hip) is a pre-pass of run_stage1: a bank with a correction off the identity reads its
+// stage-1 input from a scratch of corrected CS16 / RS16 rows instead of the caller's; one with the statistics on also sums there.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -188,6 +190,17 @@ struct asdr_tuner_bank {
   double *d_lev = nullptr;
   float *d_lev_part = nullptr;
   size_t lev_part_cap = 0;
+  // source conditioning (include/asdr_tuner.h, "Source conditioning"): every source's correction and how many are off the identity
+  // (none, with the statistics off: no pre-pass, nothing allocated); the device copy awaits its upload while corr_dirty; the
+  // scratch of corrected rows [n_sources][the call's samples] grows as d_fc_x does; the statistics [n_sources][7] exist while on
+  std::vector<asdr_tuner_iq_t> corr;
+  int n_cond = 0;
+  bool corr_dirty = true, iq_stats_on = false;
+  long long cond_launches = 0;
+  int32_t *d_corr = nullptr;
+  void *d_cond = nullptr;
+  size_t cond_cap = 0;
+  unsigned long long *d_iq_stats = nullptr;
   // device
   asdr_tuner_state_t *d_chan = nullptr;
   int32_t *d_order = nullptr, *d_taps = nullptr, *d_hist[2] = {nullptr, nullptr};
@@ -374,8 +387,44 @@ int push_resampler(asdr_tuner_t *t, hipStream_t stream) {
   return 0;
 }
 
-// A fast-convolution bank's stage 1 (asdr_tuner_fastconv.hip): n_frames frames of every channel into rows out_stride_blocks apart.
-int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_frames,
+const asdr_tuner_iq_t kIdentity = {0, 0, 0, 65536};
+bool is_identity(const asdr_tuner_iq_t &c) { return c.dc_re == 0 && c.dc_im == 0 && c.cross_q16 == 0 && c.gain_q16 == 65536; }
+
+// The pre-pass of a call (asdr_tuner_condition.hip) over n_in samples of every caller's row.  With a correction off the identity it
+// writes x' of every source to the scratch and points in / in_stride / fmt at it (CS16, or RS16 for real rows); with only the
+// statistics on it reads and sums, and the three stay the caller's; otherwise it does nothing at all.
+int run_condition(asdr_tuner_t *t, const void *&in, long &in_stride, int &fmt, long long n_in, hipStream_t stream) {
+  if (t->n_cond == 0 && !t->iq_stats_on) return 0;
+  const bool write = t->n_cond > 0, real = fmt == ASDR_TUNER_IN_RS16;
+  if (write) {
+    const size_t bytes = (size_t)t->n_src * n_in * (real ? 2 : 4);
+    if (bytes > t->cond_cap) {   // grow the scratch: nothing of ours may be in flight
+      if (asdr_tuner_synchronize(t) != 0) return -1;
+      if (t->d_cond) HIPCHK(hipFree(t->d_cond));
+      t->d_cond = nullptr; t->cond_cap = 0;
+      HIPCHK(hipMalloc(&t->d_cond, bytes));
+      t->cond_cap = bytes;
+    }
+    if (t->corr_dirty || !t->d_corr) {
+      if (!t->d_corr) HIPCHK(hipMalloc(&t->d_corr, (size_t)t->n_src * sizeof(asdr_tuner_iq_t)));
+      HIPCHK(hipMemcpyAsync(t->d_corr, t->corr.data(), (size_t)t->n_src * sizeof(asdr_tuner_iq_t), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));   // the host mirror may change as soon as this returns
+      t->corr_dirty = false;
+    }
+  }
+  ConditionArgs c;
+  c.in = in; c.out = write ? t->d_cond : nullptr; c.corr = t->d_corr; c.stats = t->iq_stats_on ? t->d_iq_stats : nullptr;
+  c.in_stride = in_stride; c.out_stride = n_in; c.n_samples = n_in; c.n_sources = t->n_src; c.fmt = fmt;
+  c.aligned = (((uintptr_t)in | (uintptr_t)((unsigned long long)in_stride * ASDR_TUNER_FMT_BYTES(fmt))) & 15u) == 0;
+  if (asdr_launch_tuner_condition(&c, stream) != 0) return fail("tuner conditioning kernel launch failed");
+  t->cond_launches++;
+  if (write) { in = t->d_cond; in_stride = (long)n_in; fmt = real ? ASDR_TUNER_IN_RS16 : ASDR_TUNER_IN_CS16; }
+  return 0;
+}
+
+// A fast-convolution bank's stage 1 (asdr_tuner_fastconv.hip): n_frames frames of every channel into rows out_stride_blocks apart;
+// fmt is the format of the rows at dIQ (the bank's, or the conditioning scratch's).
+int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int fmt, int16_t *dI, int16_t *dQ, int n_frames,
                  long out_stride_blocks, hipStream_t stream) {
   const int log2n = t->log2n, N = 1 << log2n, H = N / 2;
   const size_t x_floats = (size_t)t->n_src * n_frames * N * 2;
@@ -399,10 +448,10 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16
   f.in = (const int32_t *)dIQ; f.hist_rd = t->d_hist[t->cur]; f.hist_wr = t->d_hist[t->cur ^ 1];
   f.tw = t->d_fc_tab; f.x = t->d_fc_x; f.scratch = t->d_fc_x + x_floats;
   f.in_stride = in_stride_samples; f.n_sources = t->n_src; f.n_frames = n_frames; f.hop = H;
-  const int log2t = t->fmt == ASDR_TUNER_IN_RS16 ? log2n - 1 : log2n;   // RS16: a transform of N / 2 points, then the untangle
+  const int log2t = fmt == ASDR_TUNER_IN_RS16 ? log2n - 1 : log2n;   // RS16: a transform of N / 2 points, then the untangle
   f.log2n = log2n; f.log2n1 = (log2t + 1) / 2; f.log2n2 = log2t - f.log2n1;
   f.pass = log2n > 12 ? 1 : 0;
-  f.fmt = t->fmt;
+  f.fmt = fmt;
   FcChannelArgs c;
   c.x = t->d_fc_x; c.tw256 = t->d_fc_tab + 2 * N; c.g = t->d_fc_tab + 2 * (N + 256);
   c.chan = t->d_chan; c.order = t->d_order; c.out_i = dI; c.out_q = dQ;
@@ -432,7 +481,9 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16
 // The stage-1 launch of a call: n_blocks blocks of every channel into rows out_stride_blocks apart, then P advances.
 int run_stage1(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
                long out_stride_blocks, hipStream_t stream) {
-  if (t->fc) return run_fastconv(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream);
+  int fmt = t->fmt;
+  if (run_condition(t, dIQ, in_stride_samples, fmt, (long long)n_blocks * 128 * t->D, stream) != 0) return -1;
+  if (t->fc) return run_fastconv(t, dIQ, in_stride_samples, fmt, dI, dQ, n_blocks, out_stride_blocks, stream);
   TunerArgs a;
   a.in = (const int32_t *)dIQ; a.hist_rd = t->d_hist[t->cur]; a.hist_wr = t->d_hist[t->cur ^ 1];
   a.chan = t->d_chan; a.order = t->d_order; a.taps = t->d_taps; a.out_i = dI; a.out_q = dQ;
@@ -440,7 +491,7 @@ int run_stage1(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t
   a.n_channels = t->n; a.n_sources = t->n_src; a.n_blocks = n_blocks; a.decimation = t->D;
   a.n_phase_rows = t->n_rows; a.n_phase_pairs = t->n_pairs;
   a.shift = 15 - t->g; a.round = a.shift ? 1 << (a.shift - 1) : 0;
-  a.fmt = t->fmt;
+  a.fmt = fmt;
   if (asdr_launch_tuner(&a, stream) != 0) return fail("tuner kernel launch failed");
   t->pos += (long long)n_blocks * 128 * t->D;
   t->cur ^= 1;
@@ -478,6 +529,7 @@ asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int de
   t->n = n_channels; t->n_src = n_sources; t->D = decimation; t->device = device;
   t->fs_in = fs_in; t->up = (int)(44100 / gd); t->down = (int)(fs_mid / gd);
   t->chan.assign(n_channels, fresh_state());
+  t->corr.assign(n_sources, kIdentity);
   default_rate_filter(decimation, fs_mid, t->h, t->g);
   default_resampler(t->up, t->down, fs_mid, t->h2, t->g2);
   t->k2 = (int)t->h2.size() / t->up;
@@ -536,6 +588,7 @@ asdr_tuner_t *create_fastconv(int n_channels, int n_sources, long long fs_in, in
   for (t->log2n = 0; (1 << t->log2n) < 256 * R; t->log2n++) {}
   t->hist_slots = 128 * R;
   t->chan.assign(n_channels, fresh_state());
+  t->corr.assign(n_sources, kIdentity);
   t->pal.resize(ASDR_TUNER_FC_MAX_FILTERS);
   t->slot.assign(n_channels, 0);
   t->gain.assign(n_channels, 1.0f);
@@ -607,6 +660,7 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
     hipFree(t->d_fc_tab); hipFree(t->d_fc_x); hipFree(t->d_spec); hipFree(t->d_lev); hipFree(t->d_lev_part);
     hipFree(t->d_pal_tab); hipFree(t->d_slot); hipFree(t->d_gain);
+    hipFree(t->d_corr); hipFree(t->d_cond); hipFree(t->d_iq_stats);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -622,6 +676,7 @@ int asdr_tuner_reset(asdr_tuner_t *t) {
     if (t->d_carry[t->ccur]) HIPCHK(hipMemset(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t)));
     if (t->d_spec) HIPCHK(hipMemset(t->d_spec, 0, (size_t)t->n_src * t->spec_bins * sizeof(double)));
     if (t->d_lev) HIPCHK(hipMemset(t->d_lev, 0, (size_t)t->n * sizeof(double)));
+    if (t->d_iq_stats) HIPCHK(hipMemset(t->d_iq_stats, 0, (size_t)t->n_src * sizeof(asdr_tuner_iq_stats_t)));
     HIPCHK(hipDeviceSynchronize());
   }
   t->spec_frames = t->lev_frames = 0;
@@ -1158,5 +1213,142 @@ int asdr_tuner_read_gains(const asdr_tuner_t *t, float *dst) {
   memcpy(dst, t->gain.data(), t->n * sizeof(float));
   return 0;
 }
+
+}  // extern "C"
+
+// ---- source conditioning (include/asdr_tuner.h, "Source conditioning")
+static_assert(sizeof(asdr_tuner_iq_t) == 4 * sizeof(int32_t), "the kernel reads a correction as four int32");
+static_assert(sizeof(asdr_tuner_iq_stats_t) == ASDR_TUNER_IQ_STATS_WORDS * sizeof(int64_t), "the kernel adds into seven int64 per source");
+
+namespace {
+std::string correction_error(const asdr_tuner_iq_t &c) {
+  if (c.dc_re < -32768 || c.dc_re > 32767 || c.dc_im < -32768 || c.dc_im > 32767) return "dc_re and dc_im must be in -32768..32767";
+  if (c.cross_q16 < -32768 || c.cross_q16 > 32768) return "cross_q16 must be in -32768..32768";
+  if (c.gain_q16 < 32768 || c.gain_q16 > 131072) return "gain_q16 must be in 32768..131072";
+  return "";
+}
+
+void set_correction(asdr_tuner_t *t, int s, const asdr_tuner_iq_t &c) {
+  t->n_cond -= !is_identity(t->corr[s]);
+  t->corr[s] = c;
+  t->n_cond += !is_identity(c);
+  t->corr_dirty = true;
+}
+
+// wait for the bank's work, copy the statistics out (dst may be NULL), clear them on request
+int stats_read(asdr_tuner_t *t, asdr_tuner_iq_stats_t *dst, int clear) {
+  if (!t->iq_stats_on) return fail("the I/Q statistics are off: asdr_tuner_iq_stats_enable");
+  if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (asdr_tuner_synchronize(t) != 0) return -1;
+  const size_t bytes = (size_t)t->n_src * sizeof(asdr_tuner_iq_stats_t);
+  if (dst) HIPCHK(hipMemcpy(dst, t->d_iq_stats, bytes, hipMemcpyDeviceToHost));
+  if (clear) {
+    HIPCHK(hipMemset(t->d_iq_stats, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int asdr_tuner_set_iq_correction(asdr_tuner_t *t, int source, const asdr_tuner_iq_t *c) {
+  if (!t) return fail("null tuner bank");
+  if (!c) return fail("null correction");
+  if (source != ASDR_ALL && (source < 0 || source >= t->n_src)) return fail("source index out of range");
+  const std::string e = correction_error(*c);
+  if (!e.empty()) return fail(e);
+  for (int s = (source == ASDR_ALL ? 0 : source); s < (source == ASDR_ALL ? t->n_src : source + 1); s++) set_correction(t, s, *c);
+  return 0;
+}
+
+int asdr_tuner_get_iq_correction(const asdr_tuner_t *t, int source, asdr_tuner_iq_t *c) {
+  if (!t) return fail("null tuner bank");
+  if (!c) return fail("null destination");
+  if (source < 0 || source >= t->n_src) return fail("source index out of range");
+  *c = t->corr[source];
+  return 0;
+}
+
+int asdr_tuner_iq_stats_enable(asdr_tuner_t *t, int on) {
+  if (!t) return fail("null tuner bank");
+  if (t->device != ASDR_NO_DEVICE) {   // (re)allocate cleared, or free: nothing of ours may be in flight
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    HIPCHK(hipSetDevice(t->device));
+    unsigned long long *fresh = nullptr;
+    if (on) {
+      const size_t bytes = (size_t)t->n_src * sizeof(asdr_tuner_iq_stats_t);
+      HIPCHK(hipMalloc(&fresh, bytes));
+      if (hipMemset(fresh, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        hipFree(fresh);
+        return fail("tuner I/Q statistics: clearing the sums failed");
+      }
+    }
+    if (t->d_iq_stats) hipFree(t->d_iq_stats);
+    t->d_iq_stats = fresh;
+  }
+  t->iq_stats_on = on != 0;
+  return 0;
+}
+
+int asdr_tuner_iq_stats_enabled(const asdr_tuner_t *t) { return t && t->iq_stats_on ? 1 : 0; }
+
+int asdr_tuner_iq_stats_read(asdr_tuner_t *t, asdr_tuner_iq_stats_t *dst, int clear) {
+  if (!t) return fail("null tuner bank");
+  if (!dst) return fail("null destination");
+  return stats_read(t, dst, clear);
+}
+
+int asdr_tuner_iq_stats_clear(asdr_tuner_t *t) {
+  if (!t) return fail("null tuner bank");
+  return stats_read(t, nullptr, 1);
+}
+
+// The statement's order of operations, one rounding each: the library is built without FMA contraction.
+int asdr_tuner_iq_estimate(const asdr_tuner_iq_stats_t *s, asdr_tuner_iq_t *c) {
+  if (!s) return fail("null statistics");
+  if (!c) return fail("null destination");
+  if (s->n < 2) return fail("I/Q estimate: fewer than two samples");
+  const double n = (double)s->n;
+  const double m_r = (double)s->sum_re / n, m_i = (double)s->sum_im / n;
+  asdr_tuner_iq_t out = kIdentity;
+  double p = 0.0, g = 65536.0;
+  if (s->sum_im != 0 || s->sum_im2 != 0 || s->sum_reim != 0) {
+    const double v_rr = (double)s->sum_re2 / n - m_r * m_r;
+    const double v_ii = (double)s->sum_im2 / n - m_i * m_i;
+    const double v_ri = (double)s->sum_reim / n - m_r * m_i;
+    if (!(v_rr > 0.0)) return fail("I/Q estimate: the real part has no variance");
+    const double det = v_rr * v_ii - v_ri * v_ri;
+    if (!(det > 0.0)) return fail("I/Q estimate: the parts are fully correlated (or the imaginary part has no variance)");
+    const double gh = v_rr / std::sqrt(det);
+    const double ph = -gh * v_ri / v_rr;
+    p = std::rint(65536.0 * ph);
+    g = std::rint(65536.0 * gh);
+  }
+  const double d_r = std::rint(m_r), d_i = std::rint(m_i);
+  if (!(d_r >= -32768.0 && d_r <= 32767.0 && d_i >= -32768.0 && d_i <= 32767.0 && p >= -32768.0 && p <= 32768.0 && g >= 32768.0 &&
+        g <= 131072.0))
+    return fail("I/Q estimate: a word falls outside its range");
+  out.dc_re = (int32_t)d_r; out.dc_im = (int32_t)d_i; out.cross_q16 = (int32_t)p; out.gain_q16 = (int32_t)g;
+  *c = out;
+  return 0;
+}
+
+int asdr_tuner_iq_track(asdr_tuner_t *t, int source) {
+  if (!t) return fail("null tuner bank");
+  if (source != ASDR_ALL && (source < 0 || source >= t->n_src)) return fail("source index out of range");
+  std::vector<asdr_tuner_iq_stats_t> st(t->n_src);
+  if (stats_read(t, st.data(), 1) != 0) return -1;
+  int n_set = 0;
+  for (int s = (source == ASDR_ALL ? 0 : source); s < (source == ASDR_ALL ? t->n_src : source + 1); s++) {
+    asdr_tuner_iq_t c;
+    if (asdr_tuner_iq_estimate(&st[s], &c) != 0) continue;   // this source keeps its correction
+    set_correction(t, s, c);
+    n_set++;
+  }
+  return n_set;
+}
+
+long long asdr_tuner_condition_launches(const asdr_tuner_t *t) { return t ? t->cond_launches : -1; }
 
 }  // extern "C"

@@ -21,7 +21,9 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_levels_enable", "asdr_tuner_levels_enabled", "asdr_tuner_levels_read", "asdr_tuner_levels_device",
                  "asdr_tuner_levels_frames", "asdr_tuner_levels_clear", "asdr_tuner_palette_set", "asdr_tuner_palette_get",
                  "asdr_tuner_palette_clear", "asdr_tuner_set_channel_slot", "asdr_tuner_read_slots", "asdr_tuner_set_channel_gain",
-                 "asdr_tuner_read_gains"]
+                 "asdr_tuner_read_gains", "asdr_tuner_set_iq_correction", "asdr_tuner_get_iq_correction",
+                 "asdr_tuner_iq_stats_enable", "asdr_tuner_iq_stats_enabled", "asdr_tuner_iq_stats_read", "asdr_tuner_iq_stats_clear",
+                 "asdr_tuner_iq_estimate", "asdr_tuner_iq_track", "asdr_tuner_condition_launches"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
@@ -36,6 +38,13 @@ INPUT_FORMATS = {"cs16": (0, np.int16, 2), "cu8": (1, np.uint8, 2), "cs8": (2, n
 # monitors (include/asdr_tuner.h, "Monitors"): ASDR_TUNER_WIN_* and ASDR_TUNER_MON_* by name
 SPECTRUM_WINDOWS = {"rect": 0, "hann": 1}
 SPECTRUM_MODES = {"sum": 0, "peak": 1}
+
+# source conditioning (include/asdr_tuner.h, "Source conditioning"): asdr_tuner_iq_t and asdr_tuner_iq_stats_t
+IQ_CORRECTION_DTYPE = np.dtype([("dc_re", "<i4"), ("dc_im", "<i4"), ("cross_q16", "<i4"), ("gain_q16", "<i4")])
+IQ_STATS_DTYPE = np.dtype([("n", "<i8"), ("sum_re", "<i8"), ("sum_im", "<i8"), ("sum_re2", "<i8"), ("sum_im2", "<i8"),
+                           ("sum_reim", "<i8"), ("clipped", "<i8")])
+IQ_IDENTITY = (0, 0, 0, 65536)
+assert IQ_CORRECTION_DTYPE.itemsize == 16 and IQ_STATS_DTYPE.itemsize == 56
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
@@ -99,6 +108,15 @@ def _lib():
     L.asdr_tuner_read_slots.argtypes = [vp, C.POINTER(C.c_int32)]; L.asdr_tuner_read_slots.restype = i
     L.asdr_tuner_set_channel_gain.argtypes = [vp, i, C.c_float]; L.asdr_tuner_set_channel_gain.restype = i
     L.asdr_tuner_read_gains.argtypes = [vp, fp]; L.asdr_tuner_read_gains.restype = i
+    L.asdr_tuner_set_iq_correction.argtypes = [vp, i, vp]; L.asdr_tuner_set_iq_correction.restype = i
+    L.asdr_tuner_get_iq_correction.argtypes = [vp, i, vp]; L.asdr_tuner_get_iq_correction.restype = i
+    L.asdr_tuner_iq_stats_enable.argtypes = [vp, i]; L.asdr_tuner_iq_stats_enable.restype = i
+    L.asdr_tuner_iq_stats_enabled.argtypes = [vp]; L.asdr_tuner_iq_stats_enabled.restype = i
+    L.asdr_tuner_iq_stats_read.argtypes = [vp, vp, i]; L.asdr_tuner_iq_stats_read.restype = i
+    L.asdr_tuner_iq_stats_clear.argtypes = [vp]; L.asdr_tuner_iq_stats_clear.restype = i
+    L.asdr_tuner_iq_estimate.argtypes = [vp, vp]; L.asdr_tuner_iq_estimate.restype = i
+    L.asdr_tuner_iq_track.argtypes = [vp, i]; L.asdr_tuner_iq_track.restype = i
+    L.asdr_tuner_condition_launches.argtypes = [vp]; L.asdr_tuner_condition_launches.restype = ll
     _typed = True
     return L
 
@@ -183,6 +201,23 @@ def design_channel_filter(fs_mid, lo_hz, hi_hz):
     if lo == -hi:
         return proto.astype(np.float32)
     return (proto * np.exp(2j * np.pi * (0.5 * (lo + hi) / fs_mid) * x)).astype(np.complex64)
+
+
+def estimate_iq_correction(stats):
+    """asdr_tuner_iq_estimate on one source's statistics: an element of TunerBank.iq_stats(), or the seven values (n, sum_re, sum_im,
+    sum_re2, sum_im2, sum_reim, clipped) in that order.  Returns the words (dc_re, dc_im, cross_q16, gain_q16); raises AsdrError
+    where the estimator fails (include/asdr_tuner.h, "Source conditioning").  Host arithmetic only: no bank, no device."""
+    L = _lib()
+    st = np.zeros(1, dtype=IQ_STATS_DTYPE)
+    vals = [stats[k] for k in IQ_STATS_DTYPE.names] if getattr(stats, "dtype", None) is not None and stats.dtype.names else list(stats)
+    if len(vals) != len(IQ_STATS_DTYPE.names):
+        raise AsdrError("estimate_iq_correction: needs the seven values of asdr_tuner_iq_stats_t")
+    for k, v in zip(IQ_STATS_DTYPE.names, vals):
+        st[k] = int(v)
+    c = np.zeros(1, dtype=IQ_CORRECTION_DTYPE)
+    if L.asdr_tuner_iq_estimate(st.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)) != 0:
+        raise AsdrError(L.asdr_last_error().decode())
+    return tuple(int(c[k][0]) for k in IQ_CORRECTION_DTYPE.names)
 
 
 class _DeviceRows:
@@ -527,3 +562,49 @@ class TunerBank:
         if not p:
             raise AsdrError(self._L.asdr_last_error().decode())
         return torch.as_tensor(_DeviceRows(p, (self.n_channels,), self), device="cuda")
+
+    # source conditioning (include/asdr_tuner.h, "Source conditioning"): every bank kind
+    def set_iq_correction(self, dc=(0, 0), cross=0.0, gain=1.0, source=ALL, words=None):
+        """The source's (or every source's) DC and I/Q-imbalance correction, from the next update call: x' = (xr - dc[0],
+        cross (xr - dc[0]) + gain (xi - dc[1])), in the header's integer arithmetic.  dc in int16 units (rounded to integers),
+        cross in [-0.5, 0.5] and gain in [0.5, 2] rounded to Q16 -- or words = (dc_re, dc_im, cross_q16, gain_q16), the words
+        themselves (dc, cross and gain are then not looked at)."""
+        if words is None:
+            words = (int(np.rint(dc[0])), int(np.rint(dc[1])), int(np.rint(65536.0 * float(cross))), int(np.rint(65536.0 * float(gain))))
+        if len(words) != 4 or any(not -2**31 <= int(w) < 2**31 for w in words):
+            raise AsdrError("set_iq_correction: needs four words (dc_re, dc_im, cross_q16, gain_q16) that fit int32")
+        c = np.array([tuple(int(w) for w in words)], dtype=IQ_CORRECTION_DTYPE)
+        self._chk(self._L.asdr_tuner_set_iq_correction(self._h, int(source), c.ctypes.data_as(C.c_void_p)))
+
+    def iq_correction(self, source):
+        """The source's words (dc_re, dc_im, cross_q16, gain_q16); the identity is (0, 0, 0, 65536)."""
+        c = np.zeros(1, dtype=IQ_CORRECTION_DTYPE)
+        self._chk(self._L.asdr_tuner_get_iq_correction(self._h, int(source), c.ctypes.data_as(C.c_void_p)))
+        return tuple(int(c[k][0]) for k in IQ_CORRECTION_DTYPE.names)
+
+    def enable_iq_stats(self, on=True):
+        """Accumulate every source's exact moments and clip count of the uncorrected samples from the next update call on;
+        enabling and disabling both clear them."""
+        self._chk(self._L.asdr_tuner_iq_stats_enable(self._h, int(bool(on))))
+
+    def iq_stats_enabled(self):
+        return bool(self._L.asdr_tuner_iq_stats_enabled(self._h))
+
+    def iq_stats(self, clear=True):
+        """Structured array [n_sources] of IQ_STATS_DTYPE (n, sum_re, sum_im, sum_re2, sum_im2, sum_reim, clipped; int64, exact);
+        waits for the bank's work."""
+        st = np.zeros(self.n_sources, dtype=IQ_STATS_DTYPE)
+        self._chk(self._L.asdr_tuner_iq_stats_read(self._h, st.ctypes.data_as(C.c_void_p), int(bool(clear))))
+        return st
+
+    def clear_iq_stats(self):
+        self._chk(self._L.asdr_tuner_iq_stats_clear(self._h))
+
+    def track_iq(self, source=ALL):
+        """Read the statistics, set the estimated correction of `source` (or of every source), clear the statistics.  A source
+        whose estimate fails keeps its correction; returns the number of sources set."""
+        return self._chk(self._L.asdr_tuner_iq_track(self._h, int(source)))
+
+    def condition_launches(self):
+        """Pre-pass launches since creation: 0 for a bank that never had a correction off the identity or the statistics on."""
+        return int(self._L.asdr_tuner_condition_launches(self._h))

@@ -141,6 +141,43 @@
  *   cost      a bank whose channels are all on slot 0 at gain 1 launches and allocates exactly as before; any other bank runs
  *             one other channel kernel in the old one's place.  A channel on slot 0 at gain 1 of such a bank
  *             is written bit for bit as before.
+ *
+ * Source conditioning (every bank kind; everything not named here is unchanged).  Zero-IF radios add a DC offset and an I/Q gain
+ * and phase imbalance to what they deliver; a bank holds one correction per source, applied to x before anything else reads it, and
+ * can measure x to find that correction.  All integer; >> is an arithmetic shift.
+ *   correction per source s: (d_r, d_i, p, g) = (dc_re, dc_im, cross_q16, gain_q16), d_r, d_i in [-32768, 32767], p in [-32768,
+ *             32768], g in [32768, 131072]; the identity (0, 0, 0, 65536) at creation.  With x = (xr, xi) the int16 pair of the
+ *             "Input formats" table:
+ *                 a = xr - d_r,  b = xi - d_i                       (not clamped: 18-bit values)
+ *                 xr' = sat16(a)
+ *                 xi' = sat16((p a + g b + 32768) >> 16)            (in int64: |g b| reaches 2^33)
+ *             x' takes the place of x in every statement above, for all three bank kinds.  The identity gives x' = x exactly.  For
+ *             RS16 only d_r acts: xr' = sat16(xr - d_r), xi' = 0.
+ *   timing    a correction applies to the rows of the next update call; the history rows and overlap-save windows kept across
+ *             calls hold x', so a change between two calls is well defined by the above and flushes nothing.  asdr_tuner_reset
+ *             keeps the corrections, as it keeps the format.
+ *   statistics  off at creation, bank-wide.  Per source, over every sample the bank consumes while they are on, taken of x
+ *             (converted, before the correction): n, sum xr, sum xi, sum xr^2, sum xi^2, sum xr xi, and `clipped`, the number of
+ *             stored samples with a part at the format's rail: CU8 a in {0, 255}, CS8 {-128, 127}, CS16 / RS16 {-32768, 32767}, CF32
+ *             |a| >= 1 or not finite.  All seven are int64 and exact; they wrap modulo 2^64, sum xr^2 first: past 2^63 after 2^33
+ *             samples at -32768 (7 minutes at 20 MS/s), so the caller reads or clears before then.  Being taken of x they make the
+ *             estimate below absolute: tracking twice converges and does not compound.  For RS16 the three sums with xi are 0.
+ *             Enabling, disabling and asdr_tuner_reset clear the statistics; retunes, filter, format and correction changes do not.
+ *   estimator a pure host function in float64, every sum converted to double first, each operation rounded once (no contraction):
+ *                 m_r = sum xr / n,  m_i = sum xi / n
+ *                 v_rr = sum xr^2 / n - m_r m_r,  v_ii = sum xi^2 / n - m_i m_i,  v_ri = sum xr xi / n - m_r m_i
+ *                 det = v_rr v_ii - v_ri v_ri,  gh = v_rr / sqrt(det),  ph = (-gh v_ri) / v_rr
+ *                 d_r = rint(m_r),  d_i = rint(m_i),  p = rint(65536 ph),  g = rint(65536 gh)          (round half to even)
+ *             the blind estimate that leaves the corrected Q uncorrelated with I and equal to it in power: right for signals that
+ *             are circular about DC, which a band full of independent stations is.  It fails (output untouched) when n < 2, when
+ *             v_rr <= 0, when det <= 0, or when a word falls outside its range.  Statistics whose three sums with xi are all zero
+ *             (RS16) give d_r, d_i = 0 and the identity for p and g, and need only n >= 2 and d_r in range.
+ *   cost      a bank with every correction at the identity and the statistics off launches and allocates exactly as before.  With
+ *             the statistics on and every correction at the identity one more kernel reads the caller's rows and sums; the bank's
+ *             kernels read the caller's rows as before.  With any correction off the identity that kernel also writes x' of every
+ *             source (the identity ones: a converted copy) as CS16 (RS16 for an RS16 bank) to a scratch of the bank's, and the
+ *             bank's unchanged kernels read the scratch.  An ASDR_NO_DEVICE bank takes the setters, enable and
+ *             the estimator and fails the reads, the clear and track.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
@@ -299,6 +336,25 @@ int asdr_tuner_set_channel_slot(asdr_tuner_t *t, int ch, int slot);
 int asdr_tuner_read_slots(const asdr_tuner_t *t, int32_t *dst /* [n_channels] */);
 int asdr_tuner_set_channel_gain(asdr_tuner_t *t, int ch, float gain);
 int asdr_tuner_read_gains(const asdr_tuner_t *t, float *dst /* [n_channels] */);
+
+/* Source conditioning (the section above; every bank kind).  Setters return 0 / -1; a rejected call keeps the old state. */
+typedef struct { int32_t dc_re, dc_im, cross_q16, gain_q16; } asdr_tuner_iq_t;
+typedef struct { int64_t n, sum_re, sum_im, sum_re2, sum_im2, sum_reim, clipped; } asdr_tuner_iq_stats_t;
+/* source: a source index, or ASDR_ALL for set.  Rejected: a word outside its range, a bad source. */
+int asdr_tuner_set_iq_correction(asdr_tuner_t *t, int source, const asdr_tuner_iq_t *c);
+int asdr_tuner_get_iq_correction(const asdr_tuner_t *t, int source, asdr_tuner_iq_t *c);
+/* on != 0: the statistics run from the next update call; either value clears them.  Synchronises with the bank's work. */
+int asdr_tuner_iq_stats_enable(asdr_tuner_t *t, int on);
+int asdr_tuner_iq_stats_enabled(const asdr_tuner_t *t);   /* 1 / 0 (0 for a NULL bank) */
+/* Waits for the bank's work, copies the statistics to dst [n_sources]; clear != 0 then clears them.  Fails when they are off. */
+int asdr_tuner_iq_stats_read(asdr_tuner_t *t, asdr_tuner_iq_stats_t *dst /* [n_sources] */, int clear);
+int asdr_tuner_iq_stats_clear(asdr_tuner_t *t);
+/* The estimator: no bank, no device.  0, or -1 (asdr_last_error) with *c untouched. */
+int asdr_tuner_iq_estimate(const asdr_tuner_iq_stats_t *s, asdr_tuner_iq_t *c);
+/* Reads the statistics, estimates and sets the correction of `source` (or of every source, ASDR_ALL), clears the statistics.  A
+ * source whose estimate fails keeps its correction.  Returns the number of sources it set, -1 when the read fails. */
+int asdr_tuner_iq_track(asdr_tuner_t *t, int source);
+long long asdr_tuner_condition_launches(const asdr_tuner_t *t);   /* pre-pass launches since creation */
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */

@@ -23,6 +23,10 @@
   F4p       F4 with a palette in use (include/asdr_tuner.h, "Filter palette and gain"): channel c on slot c mod 4 -- the default
             filter, +-5 kHz, 300 .. 3000 Hz, -3000 .. -300 Hz (design_channel_filter at Fs_mid = 150 kHz) -- at gain 1, 0.5, 2, -1,
             4 by c mod 5; F4's inputs.  Run beside F4 in one process: F4 is the code path without the palette
+  F4c       F4 with source conditioning (include/asdr_tuner.h, "Source conditioning"): every source carries a correction off the
+            identity (CONDITION_WORDS by source) and the statistics are on; F4's inputs.  Run beside F4 in one process: F4 is the
+            code path without the pre-pass
+  F20c      F20 with source conditioning, likewise
 
 Call time is from device events around the timed calls (warmed; at least 1 s of timed work).  Model counts per call: integer
 multiply-adds 4 D + 2 L per output sample and channel (mixer + filter) and the bytes the call must move (CS16 input once per
@@ -32,7 +36,7 @@ time per call over call time.  The first call of each config is checked against 
 channels.  Fast-convolution banks (F*) have no operation model here (DESIGN.md 3.8.2 counts them); their first call is checked
 against tests/tuner_fastconv_ref.py, a float64 statement, so "parity" there means every sample within +-2.  Inputs are seeded.
 
-  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z F4m F20m F4p]
+  python tools/bench_tuner.py [T1 T2 T3 T3+chain T4 T4+chain S48 F4 F4+chain F20 F61 F4u8 F20s8 R64 R64z F4m F20m F4p F4c F20c]
 """
 import json
 import os
@@ -46,6 +50,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import audiosdr_amd as A  # noqa: E402
+import tuner_condition_ref as CR  # noqa: E402
 import tuner_fastconv_ref as FR  # noqa: E402
 import tuner_formats_ref as FM  # noqa: E402
 import tuner_palette_ref as PR  # noqa: E402
@@ -74,22 +79,34 @@ CONFIGS = {
     "F4m": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, monitors=True, seed=sum(map(ord, "F4"))),
     "F20m": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, monitors=True, seed=sum(map(ord, "F20"))),
     "F4p": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, palette=True, seed=sum(map(ord, "F4"))),
+    "F4c": dict(n_src=16, D=16, n_ch=65536, L=None, nb=16, fs_in=2400000, fastconv=True, condition=True, seed=sum(map(ord, "F4"))),
+    "F20c": dict(n_src=16, D=128, n_ch=65536, L=None, nb=16, fs_in=20000000, fastconv=True, condition=True, seed=sum(map(ord, "F20"))),
 }
 PALETTE_BANDS = [None, (-5000.0, 5000.0), (300.0, 3000.0), (-3000.0, -300.0)]   # slot 0 is the default filter
 PALETTE_GAINS = [1.0, 0.5, 2.0, -1.0, 4.0]
 
 
+def condition_words(s):
+    """Source s's correction (dc_re, dc_im, cross_q16, gain_q16) of the F*c configs: a few hundred LSB of DC, up to +-4 degrees of
+    phase and +-6 % of gain, none the identity."""
+    return (310 - 40 * s, -777 + 90 * s, -4583 + 600 * s, 61977 + 450 * s)
+
+
 def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fmt="cs16", real=False, seed=None, monitors=False,
-        palette=False):
+        palette=False, condition=False):
     """nb = blocks per call of a plain bank, frames per call of a rate bank (fs_in given); D is R for a fast-convolution bank.
     fmt: the bank's input format (rows go through update_samples_device); real: CS16 rows with zero Q; monitors: the spectrum
     (4,096 bins, hann, sum) and the levels of a fast-convolution bank are on; palette: channel c is on slot c mod 4 of
-    PALETTE_BANDS at gain PALETTE_GAINS[c mod 5]."""
+    PALETTE_BANDS at gain PALETTE_GAINS[c mod 5]; condition: source s carries condition_words(s) and the I/Q statistics are on."""
     rng = np.random.default_rng(sum(map(ord, name)) if seed is None else seed)
     bank = A.TunerBank.fastconv(n_ch, n_src, fs_in, D) if fastconv else A.TunerBank(n_ch, n_src, D, fs_in=fs_in)
     bank.set_input_format(fmt)
     if monitors:
         bank.enable_spectrum(4096, "hann", "sum"); bank.enable_levels()
+    if condition:
+        for s in range(n_src):
+            bank.set_iq_correction(words=condition_words(s), source=s)
+        bank.enable_iq_stats()
     rate = fs_in is not None
     cap = nb + 1 if rate else nb
     if L is not None:
@@ -120,6 +137,8 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
     else:
         raw = rng.integers(-12000, 12000, size=(calls, n_src, N, 2), endpoint=True).astype(np.int16)
     iq = [FM.to_cs16(raw[0], fmt)]                            # the first call's rows as the restatements take them
+    if condition:
+        iq = [np.stack([CR.condition(iq[0][s], condition_words(s)) for s in range(n_src)])]
     dIQ = torch.from_numpy(raw).cuda()
     dI = torch.empty((n_ch, cap, 128), dtype=torch.int16, device="cuda")
     dQ = torch.empty_like(dI)
@@ -222,6 +241,11 @@ def run(name, n_src, D, n_ch, L, nb, chain=False, fs_in=None, fastconv=False, fm
     if palette:
         out.update({"palette": {"slots_in_use": sorted(set(int(v) for v in bank.slots())), "bands_hz": PALETTE_BANDS,
                                 "gains": PALETTE_GAINS}})
+    if condition:
+        st = bank.iq_stats()
+        out.update({"condition": {"words": [list(condition_words(s)) for s in range(n_src)], "launches": bank.condition_launches(),
+                                  "launches_expected": len(out_blocks) + 9, "stats_samples_per_source": [int(v) for v in st["n"]],
+                                  "stats_clipped": [int(v) for v in st["clipped"]]}})
     if monitors:
         spec, frames = bank.spectrum()
         lev, lframes = bank.levels()
