@@ -60,7 +60,7 @@ EXPORTS = (["asdr_create", "asdr_destroy", "asdr_last_error", "asdr_n_channels",
             "asdr_capture_device_ptr", "asdr_capture_update_device", "asdr_capture_read",
             "asdr_create_sharded", "asdr_n_shards", "asdr_shard", "asdr_shard_first_channel", "asdr_shard_device",
             "asdr_host_alloc", "asdr_host_free", "asdr_host_register", "asdr_host_unregister", "asdr_set_host_chunks",
-            "asdr_host_path_info", "asdr_stream_pipeline_alloc_failures", "asdr_set_launch_split", "asdr_order_after", "asdr_order_before", "asdr_lane_calls", "asdr_sam_role_calls", "asdr_sam_chunk_calls", "asdr_als_role_calls", "asdr_set_lanes"] +
+            "asdr_host_path_info", "asdr_stream_pipeline_alloc_failures", "asdr_set_launch_split", "asdr_order_after", "asdr_order_before", "asdr_lane_calls", "asdr_sam_role_calls", "asdr_sam_chunk_calls", "asdr_als_role_calls", "asdr_set_lanes", "asdr_set_alternate_order", "asdr_reversed_launches"] +
            ["asdr_" + n for n in _SETTERS_VOID + _SETTERS_F + _SETTERS_I + _GETTERS_F + _GETTERS_I])
 
 _lib = None
@@ -205,6 +205,9 @@ def load_library(path=None):
         L.asdr_lanes_overlap_probe.argtypes = [vp]; L.asdr_lanes_overlap_probe.restype = _i
         L.asdr_lanes_enabled.argtypes = [vp]; L.asdr_lanes_enabled.restype = _i
         L.asdr_stream_pipeline_headroom_refusals.argtypes = [vp]; L.asdr_stream_pipeline_headroom_refusals.restype = C.c_long
+    if path is None or hasattr(L, "asdr_set_alternate_order"):
+        L.asdr_set_alternate_order.argtypes = [vp, _i]; L.asdr_set_alternate_order.restype = _i
+        L.asdr_reversed_launches.argtypes = [vp]; L.asdr_reversed_launches.restype = C.c_long
     if path is None:
         _lib = L
     return L
@@ -284,6 +287,14 @@ class AudioSDRBatch:
 
     def stream_pipeline_headroom_refusals(self):
         return int(self._L.asdr_stream_pipeline_headroom_refusals(self._h))
+
+    def set_alternate_order(self, on=True):
+        """Alternating channel order of the plain kind's one-block direct launches (include/asdr.h): off by default."""
+        self._chk(self._L.asdr_set_alternate_order(self._h, 1 if on else 0))
+
+    def reversed_launches(self):
+        """Launches that walked their channels in the reversed order so far (include/asdr.h)."""
+        return int(self._L.asdr_reversed_launches(self._h))
 
     def set_lanes(self, on=True, min_waves=0):
         self._chk(self._L.asdr_set_lanes(self._h, 1 if on else 0, int(min_waves)))

@@ -199,7 +199,11 @@ typedef struct {
   ChanParams uni;         /* uni_valid: the parameter row of EVERY channel of the direct launch's settings group (asdr_host.cpp params_uniform: the
                              rows are equal in every field the kernels read) -- launch constants instead of a row of `params` per lane */
   uint32_t uni_valid;     /* 1: `uni` is filled and the launcher may take the instantiation that reads it (asdr_update_kernel_mw_u) */
-  uint32_t pad_uni_;
+  uint32_t wg_reverse;    /* 1: the workgroup with hardware index blockIdx.x works on LOGICAL workgroup gridDim.x - 1 - blockIdx.x (its channels, its schedule
+                             slots); the duty rotation keeps the hardware index.  Honoured by the plain kind's one-block direct instantiations only
+                             (asdr_update_kernel_mw_u / _mw / _one); with asdr_set_alternate_order(b, 1) the host alternates it launch by launch, so that the
+                             state rows a launch wrote LAST are the ones the next launch reads FIRST.  Off by default: measured, the step time and the
+                             waves' wait cycles do not move with it (profiles/README.md) */
 } UpdateArgs;
 #define ASDR_ALS_STAGE_SLOTS 32  /* ALS role streams: slots of UpdateArgs.als_stage per channel (16 KB) */
 #define ASDR_ALS_CHUNK 8         /* ... and blocks per chain / filter launch: the chain launches run up to STAGE_SLOTS / CHUNK - 2 chunks ahead */

@@ -61,6 +61,7 @@ extern "C" int asdr_launch_stream_ack(uint32_t *err, hipStream_t stream);
 extern "C" int asdr_kernels_upload_tables(void);
 namespace { void autopin_batch_created(); void autopin_batch_gone(); }   // (the auto-pinned caller ranges live as long as the process has a device batch: host path, below)
 extern "C" int asdr_launch_update(const UpdateArgs *a, int variant, int uniform, hipStream_t stream);
+extern "C" int asdr_launch_update_ordered(const UpdateArgs *a, int variant, int uniform, hipStream_t stream, int *reversed);
 extern "C" int asdr_launch_sam_role(const UpdateArgs *a, int variant, int uniform, int role, hipStream_t stream);
 extern "C" int asdr_launch_als_role(const UpdateArgs *a, int role, hipStream_t stream);
 extern "C" int asdr_launch_als_stage_seed(const UpdateArgs *a, int ch0, int n, hipStream_t stream);
@@ -350,6 +351,13 @@ struct asdr_batch {
   long stat_stream_headroom_refusals = 0;   // pipeline calls sent to the other launch forms because pipeline + side sub-ranges would not be co-resident (asdr_stream_pipeline_headroom_refusals)
   long stat_stream_alloc_failures = 0;   // the pipeline's buffers could not be allocated: the batch opted itself out (asdr_stream_pipeline_alloc_failures)
   uint32_t lo_parity = 0;
+  // Alternating channel order (asdr_set_alternate_order): the one-block direct launches of the plain kind walk their sub-range forwards in one
+  // launched block and backwards in the next, so that the state rows a launch wrote last are the first the next launch reads -- built for the
+  // last-level cache to serve those reads; measured, it buys nothing (profiles/README.md).  The parity advances per launched block like
+  // lo_parity, whether the order is on or off; a lane reverses within its own half.
+  uint32_t wg_parity = 0;
+  bool alternate_order = false;     // off by default: measured, no gain (profiles/README.md); ASDR_ALTERNATE_ORDER=1 / asdr_set_alternate_order
+  long stat_reversed_launches = 0;  // launches that ran in the reversed order (asdr_reversed_launches)
   uint32_t nb_phase = 0;         // blocks processed so far, mod 3 (position of every channel's blanker ring)
   uint32_t als_phase = 0;        // blocks processed so far, mod 2 (position of every channel's ALS input ring)
   ChainConsts k{};
@@ -968,6 +976,7 @@ asdr_batch_t *asdr_create(int n_channels, int device) {
   b->sam_split_min = getenv("ASDR_SAM_SPLIT_MIN") ? atoi(getenv("ASDR_SAM_SPLIT_MIN")) : ASDR_SAM_SPLIT_MIN_CHANNELS;
   b->stream_pipeline = getenv("ASDR_NO_STREAM_PIPELINE") == nullptr;
   b->uniform_params = getenv("ASDR_NO_UNIFORM_PARAMS") == nullptr;
+  b->alternate_order = getenv("ASDR_ALTERNATE_ORDER") != nullptr && getenv("ASDR_NO_ALTERNATE_ORDER") == nullptr;
   b->als_split_min = getenv("ASDR_ALS_SPLIT_MIN") ? atoi(getenv("ASDR_ALS_SPLIT_MIN")) : 0x7fffffff;
   if (getenv("ASDR_LAUNCH_SPLIT")) b->launch_split = std::max(1, std::min(atoi(getenv("ASDR_LAUNCH_SPLIT")), 8));
   if (getenv("ASDR_LAUNCH_SPLIT_MIN_WAVES")) b->launch_split_min_waves = std::max(8, atoi(getenv("ASDR_LAUNCH_SPLIT_MIN_WAVES")));
@@ -1362,12 +1371,19 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
     b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
     b->lo_parity ^= 1u;
+    b->wg_parity ^= (uint32_t)(n_blocks & 1);
     return 0;
   }
   // The largest sub-range runs on the caller's stream: back-to-back calls then follow each other there without a gap, the helper
   // streams' joins (shorter kernels) are already satisfied when it ends, and only their starts pay the fork event's latency
   // (C4: 28 us per call with the remainders' launch on the caller's stream).
   const int n_launch = per_block ? n_blocks : 1;
+  // the order of launched block lb of this call, for a sub-range that may take it: a direct group of the plain kind, one block per launch
+  // (the launcher has the last word: asdr_launch_update_ordered reports whether the kernel it chose honours the field)
+  auto order_bit = [&](int kind, int uniform, int direct_ch0, int lb) -> uint32_t {
+    if (!b->alternate_order || kind != ASDR_KERNEL_PLAIN || !uniform || direct_ch0 < 0 || !(per_block || n_blocks == 1)) return 0u;
+    return (b->wg_parity ^ (uint32_t)lb) & 1u;
+  };
   float *const taps = a.taps;
   if (e0 && part == 0) HIPCHK(hipEventRecord(e0, stream));   // timing marker: right before the first launch
   if (use_lanes) {
@@ -1399,6 +1415,7 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
           if (su.uniform && b->kind_direct[su.kind]) { const SlotInfo &s0 = b->sched[su.first]; al.direct_ch0 = s0.ch + lo; al.direct_mode = s0.mode; al.direct_flags = s0.flags; al.direct_lo = s0.lo; set_uni(b, al, s0.ch); }
           al.lo_cache = b->d_lo + (size_t)(1 + (l % ASDR_LANES)) * 2 * ASDR_LO_ENTRIES;   // this lane's own set: its writers fill it, its waves read it (general-kernel waves have no entry)
           al.lo_write = 1u;
+          al.wg_reverse = order_bit(su.kind, su.uniform, al.direct_ch0, 0);
           al.lo_writer_bit = ASDR_LO_WRITER_LANE(l % ASDR_LANES);   // (lane 0: ASDR_LO_WRITER; a direct launch: its wave 0, under any name)
           if (sam_split && (su.kind == ASDR_KERNEL_SAM || su.kind == ASDR_KERNEL_SAM_ALS)) set_sam_rows(al, su.kind, first, 0);
           const int form = (als_split && su.kind == ASDR_KERNEL_ALS_SMALL && su.uniform) ? 2 : su.uniform;
@@ -1407,8 +1424,11 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
             al.nb_phase = (b->nb_phase + (uint32_t)(lb % 3)) % 3u;
             al.als_phase = (b->als_phase + (uint32_t)lb) & 1u;
             al.lo_parity = b->lo_parity ^ (uint32_t)(lb & 1);
+            al.wg_reverse = order_bit(su.kind, su.uniform, al.direct_ch0, lb);
           }
-          if (asdr_launch_update(&al, su.kind, form, ls) != 0) return fail("update kernel launch failed");
+          int rev = 0;
+          if (asdr_launch_update_ordered(&al, su.kind, form, ls, &rev) != 0) return fail("update kernel launch failed");
+          b->stat_reversed_launches += rev;
         }
       }
     }
@@ -1419,6 +1439,7 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
     b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
     b->lo_parity ^= (uint32_t)(n_launch & 1);
+    b->wg_parity ^= (uint32_t)(n_launch & 1);
     return 0;
   }
   // This part's waves of every sub-range, as launch items.  A large item is cut into `launch_split` pieces on as many streams
@@ -1592,6 +1613,7 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
         a.direct_ch0 = s0.ch + (first - subs[i].first); a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch);
         if (first != subs[i].first) a.lo_write = 0u;   // (a direct launch's wave 0 is the writer: only the piece that holds the group's first wave)
       }
+      a.wg_reverse = order_bit(subs[i].kind, subs[i].uniform, a.direct_ch0, per_block ? lb : 0);   // (a piece of a split launch reverses within itself)
       const bool sam3 = sam_split && (subs[i].kind == ASDR_KERNEL_SAM || subs[i].kind == ASDR_KERNEL_SAM_ALS);
       if (sam3) set_sam_rows(a, subs[i].kind, first, sam_roles ? (lb & 1) : 0);   // this sub-range's tiles (1 KB per slot, 8 slots per tile) and lock words
       const int form = (als_split && subs[i].kind == ASDR_KERNEL_ALS_SMALL && subs[i].uniform) ? 2 : subs[i].uniform;
@@ -1610,7 +1632,9 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
         HIPCHK(hipEventRecord(b->ev_role[4 + pa], stream));
         continue;
       }
-      if (asdr_launch_update(&a, subs[i].kind, form, s) != 0) return fail("update kernel launch failed");
+      int rev = 0;
+      if (asdr_launch_update_ordered(&a, subs[i].kind, form, s, &rev) != 0) return fail("update kernel launch failed");
+      b->stat_reversed_launches += rev;
       if (it != main_item) HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
     }
     for (int j = 0; j < n_aux; j++) HIPCHK(hipStreamWaitEvent(stream, b->ev_join[j], 0));   // behind the caller's stream's own launch
@@ -1624,6 +1648,7 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
   b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
   b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
   b->lo_parity ^= (uint32_t)(parity_launches & 1);
+  b->wg_parity ^= (uint32_t)(n_launch & 1);
   return 0;
 }
 
@@ -2130,6 +2155,18 @@ int asdr_order_after(asdr_batch_t *b, void *stream_) {   // the batch's calls on
   HIPCHK(hipStreamWaitEvent(b->stream, b->ev_fork, 0));
   return 0;
 }
+int asdr_set_alternate_order(asdr_batch_t *b, int on) {
+  if (!b) return fail("null batch");
+  if (is_sharded(b)) { for (asdr_batch *sh : b->shards) sh->alternate_order = on != 0; return 0; }
+  b->alternate_order = on != 0;
+  return 0;
+}
+
+long asdr_reversed_launches(asdr_batch_t *b) {
+  if (is_sharded(b)) { long t = 0; for (asdr_batch *sh : b->shards) t += sh->stat_reversed_launches; return t; }
+  return b ? b->stat_reversed_launches : -1;
+}
+
 long asdr_lane_calls(asdr_batch_t *b) {
   if (is_sharded(b)) { long t = 0; for (asdr_batch *sh : b->shards) t += sh->stat_lane_calls; return t; }
   return b ? b->stat_lane_calls : -1;

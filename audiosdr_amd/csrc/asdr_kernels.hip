@@ -546,6 +546,16 @@ __device__ __forceinline__ void store_int4_nt(int4 *p, int4 v) {
   const i4v tv = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(tv, reinterpret_cast<i4v *>(p));
 }
+#ifndef ASDR_STATE_POLICY
+#define ASDR_STATE_POLICY 1   /* cache policy of the state rows that come back a launch later (newest blanker slot, hil_i / hil_q slots) in the plain kind's one-block
+                                 instantiations (asdr_update_kernel_mw_u / _mw / _one: EVERY launch of them, direct group or not, whatever order it walks):
+                                 0 = as everywhere else: non-temporal stores, the blanker ring's oldest block by non-temporal loads (ASDR_NT_LOADS);
+                                 1 (shipped) = those rows as plain stores: -2.5 % on the C2 step, with or without the alternating order;
+                                 2 = plain stores, and the oldest block by plain loads (gives a part of that back).  Measured: profiles/README.md */
+#endif
+// a state row's 16 bytes: plain (PLAIN) or streaming
+template <bool PLAIN> __device__ __forceinline__ void store4_state(float *p, const float *v) { if constexpr (PLAIN) store4(p, v); else store4_nt(p, v); }
+template <bool PLAIN> __device__ __forceinline__ void store_int4_state(int4 *p, int4 v) { if constexpr (PLAIN) *p = v; else store_int4_nt(p, v); }
 // the even entries of eight (the 16-waves-per-CU form keeps the mixer's phases of even samples only)
 __device__ __forceinline__ void store4e(float *p, const float *v) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[2], v[4], v[6]); }
 __device__ __forceinline__ void store8(float *p, const float *v) {
@@ -1239,6 +1249,14 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #ifndef ASDR_MW_ROT
 #define ASDR_MW_ROT 0
 #endif
+  // The LOGICAL workgroup index: which channels / schedule slots this workgroup works on.  A launch with a.wg_reverse walks the sub-range from
+  // its end (the plain kind's one-block instantiations only: everywhere else the field is not read), so that consecutive launches can
+  // alternate and the state rows written last are read first (off by default: measured, no gain -- profiles/README.md).  Placement (XCD = workgroup mod 8, the SIMD patterns) and with it the duty
+  // rotation below belong to the HARDWARE index.  Nothing in a launch depends on WHEN logical wave 0 runs: the oscillator cache's writer
+  // fills the entry the NEXT launch reads, and stream order separates the two.
+  constexpr bool ORDERED = (ROLE == 0) && !HAS_ALS && !HAS_SAM && UNIFORM && ONEBLK_ && (STRIDE == ASDR_STRIDE);
+  constexpr bool ST_PLAIN = ORDERED && (ASDR_STATE_POLICY >= 1), LD_PLAIN = ORDERED && (ASDR_STATE_POLICY >= 2);   // (state rows: see ASDR_STATE_POLICY; the same three instantiations, independent of a.wg_reverse)
+  const int wg_l = (ORDERED && a.wg_reverse != 0u) ? (int)(gridDim.x - 1u - blockIdx.x) : (int)blockIdx.x;
   const uint32_t mw_b = blockIdx.x;
   const uint32_t mw_rot = (ASDR_MW_ROT == 0) ? mw_b : (ASDR_MW_ROT == 1) ? (mw_b >> 3) : (ASDR_MW_ROT == 2) ? ((mw_b >> 3) + (mw_b >> 8)) :
                           (ASDR_MW_ROT == 3) ? ((mw_b * 0x9E3779B1u) >> 30) : (ASDR_MW_ROT == 4) ? ((mw_b >> 3) % 3u) : (mw_b >> 5);
@@ -1265,9 +1283,9 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   constexpr int MWX = 16;   // per channel: 0 blanker average in / out, 1 mixer phase in / "a phase sequence was computed" out, 2 increment, 3 flags, 4 phase after the block,
                             // 5 AGC quiet flag, 6 AM level, 7 gain after the block, 8 envelope in / out, 9 hang counter in / out, 10 gain in, 11..14 attack / release alpha, beta, 15 hang count
   // schedule slot / channel index of the workgroup's channel q (0 .. 8 * WAVES - 1), for the lanes that work on other waves' channels
-  auto mw_channel = [&](int q) -> int { const int sidx = (int)blockIdx.x * (8 * WAVES) + q; return (sidx < a.n_sched) ? a.direct_ch0 + sidx : a.n_channels; };
+  auto mw_channel = [&](int q) -> int { const int sidx = wg_l * (8 * WAVES) + q; return (sidx < a.n_sched) ? a.direct_ch0 + sidx : a.n_channels; };
   // this wave's index in the launched schedule sub-range (the streaming pipeline launches its three roles one after the other)
-  const int wave_g = STREAM ? (int)blockIdx.x % a.stream_waves : (int)blockIdx.x * WAVES + wave;
+  const int wave_g = STREAM ? wg_l % a.stream_waves : wg_l * WAVES + wave;
   float *const lds = lds_wg + wave * 8 * STRIDE;            // this wave's 8 channel rows
   const int lane = threadIdx.x & 63, c8 = lane >> 3, s8_ = lane & 7;
 #ifndef ASDR_MW_SINE_LDS
@@ -1434,7 +1452,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     // profiling build (tools/timeline.py): lane 0 of a few waves timestamps the phase boundaries into the taps buffer
     // (the four-wave form: all four waves of workgroups 0, 683, 1365, 2047 -> slots 4 i + wave; entries 17..28 = arrival at / departure from the
     // six workgroup barriers, see TL(17) ff.)
-    const int tl_wg = ((int)blockIdx.x == 0) ? 0 : (((int)blockIdx.x == 683) ? 1 : (((int)blockIdx.x == 1365) ? 2 : (((int)blockIdx.x == 2047) ? 3 : -1)));
+    const int tl_wg = (wg_l == 0) ? 0 : ((wg_l == 683) ? 1 : ((wg_l == 1365) ? 2 : ((wg_l == 2047) ? 3 : -1)));
     const int tl_slot = STREAM ? ((wave_g == 0) ? 2 * (3 + ROLE) + (blk & 1) : -1)
                                : (MW ? ((tl_wg < 0) ? -1 : 4 * tl_wg + wave)
                                      : ((wave_g == 0) ? 0 : ((wave_g == 2731) ? 1 : ((wave_g == 5461) ? 2 : ((wave_g == 8191) ? 3 : -1)))));
@@ -1540,7 +1558,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       const int4 *old4 = reinterpret_cast<const int4 *>(hist + ns * 256 + kA), *mid4 = reinterpret_cast<const int4 *>(hist + ns_mid * 256 + kA);
 #if ASDR_NT_LOADS >= 2
       rmi[0].v = mid4[0]; rmi[1].v = mid4[8]; rmq[0].v = mid4[16]; rmq[1].v = mid4[24];   // (the middle block comes back once more: temporal)
-      roi[0].v = load_int4_nt(old4); roi[1].v = load_int4_nt(old4 + 8); roq[0].v = load_int4_nt(old4 + 16); roq[1].v = load_int4_nt(old4 + 24);
+      if constexpr (LD_PLAIN) { roi[0].v = old4[0]; roi[1].v = old4[8]; roq[0].v = old4[16]; roq[1].v = old4[24]; }
+      else { roi[0].v = load_int4_nt(old4); roi[1].v = load_int4_nt(old4 + 8); roq[0].v = load_int4_nt(old4 + 16); roq[1].v = load_int4_nt(old4 + 24); }
 #else
       rmi[0].v = mid4[0]; rmi[1].v = mid4[8]; rmq[0].v = mid4[16]; rmq[1].v = mid4[24];   // Q row starts 128 samples = 16 int4 later
       roi[0].v = old4[0]; roi[1].v = old4[8]; roq[0].v = old4[16]; roq[1].v = old4[24];
@@ -1628,7 +1647,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       const bool own_tail = (s8 >= 1);
       if (C16 && nb_en) {   // the 16-waves-per-CU form sends the newest block to its ring slot FIRST: 16 registers less across the envelope pass
         int4 *ni = reinterpret_cast<int4 *>(hist + ns_new * 256 + kA);
-        store_int4_nt(ni, ri[0].v); store_int4_nt(ni + 8, ri[1].v); store_int4_nt(ni + 16, rq[0].v); store_int4_nt(ni + 24, rq[1].v);
+        store_int4_state<ST_PLAIN>(ni, ri[0].v); store_int4_state<ST_PLAIN>(ni + 8, ri[1].v); store_int4_state<ST_PLAIN>(ni + 16, rq[0].v); store_int4_state<ST_PLAIN>(ni + 24, rq[1].v);
         if (lead) { S->nb_gain[ns_new][0] = gain_i; S->nb_gain[ns_new][1] = gain_q; }
       }
       // (every gain the wave's ring slots arrived with is 1.0: the two-operation binary32 scale, see scale8)
@@ -1705,7 +1724,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       if (nb_en && !C16) {   // newest block -> third ring slot, with its gains (blanker-off channels pass their own input: see above)
         int4 *ni = reinterpret_cast<int4 *>(hist + ns_new * 256 + kA);
 #ifndef ASDR_TEMPORAL_RINGS
-        store_int4_nt(ni, ri[0].v); store_int4_nt(ni + 8, ri[1].v); store_int4_nt(ni + 16, rq[0].v); store_int4_nt(ni + 24, rq[1].v);
+        store_int4_state<ST_PLAIN>(ni, ri[0].v); store_int4_state<ST_PLAIN>(ni + 8, ri[1].v); store_int4_state<ST_PLAIN>(ni + 16, rq[0].v); store_int4_state<ST_PLAIN>(ni + 24, rq[1].v);
 #else
         ni[0] = ri[0].v; ni[8] = ri[1].v; ni[16] = rq[0].v; ni[24] = rq[1].v;
 #endif
@@ -2275,7 +2294,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       // Every wave of the workgroup has its IF output in LDS; wave 0 runs the PLL of all 8 * WAVES channels, one per lane.
       __syncthreads();
       if (ABL_ON(ABL_SAM) && wave == 0 && lane_i < 8 * WAVES) {
-        const int sj = (int)blockIdx.x * WAVES * 8 + lane_i;       // schedule slot of workgroup channel lane_i
+        const int sj = wg_l * WAVES * 8 + lane_i;       // schedule slot of workgroup channel lane_i
         int chj = a.n_channels; uint32_t modej = a.params[a.n_channels].mode;
         if (sj < a.n_sched) { const int4 sl = *reinterpret_cast<const int4 *>(a.sched + sj); chj = sl.x; modej = (uint32_t)sl.y; }
         if (modej == ASDR_SAMmode) {
@@ -2415,7 +2434,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
               _Pragma("unroll")                                                                                                               \
               for (int j = 0; j < 4; ++j) qn[4 * m + j] = mq[j];                                                                              \
             } else { store4(L + W0 + kF + 32 * m, mi); store4(L + W1 + kF + 32 * m, mq); }                                                    \
-            store4_nt(hi_ring + hs * 128 + 32 * m, mi);                                                                                       \
+            store4_state<ST_PLAIN>(hi_ring + hs * 128 + 32 * m, mi);                                                                                       \
           }
         if (lo_hit || mix_uni) { C16_MIX_LOOP(true) }
         else {
@@ -2462,7 +2481,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           for (int j = 0; j < 4; ++j) qn[4 * m + j] = mq[j];
         } else { store4(L + W0 + kF + 32 * m, mi); store4(L + W1 + kF + 32 * m, mq); }
 #ifndef ASDR_TEMPORAL_RINGS
-        if (is_ssb) store4_nt(hi_ring + hs * 128 + 32 * m, mi);
+        if (is_ssb) store4_state<ST_PLAIN>(hi_ring + hs * 128 + 32 * m, mi);
 #else
         if (is_ssb) store4(hi_ring + hs * 128 + 32 * m, mi);
 #endif
@@ -2528,7 +2547,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             L[XP + 127 + k] = hq_m[4 * m + j];
             if (k < 63) L[XP + 255 + k] = qn[4 * m + j];   // x[256 + k], k < 63: what pass 1 reads of this block
           }
-          store4_nt(hq_ring + hs * 128 + 32 * m, qn + 4 * m);   // newest replaces oldest in the HBM ring
+          store4_state<ST_PLAIN>(hq_ring + hs * 128 + 32 * m, qn + 4 * m);   // newest replaces oldest in the HBM ring
         }
         if (lead) S->hil_slot = hs ^ 1u;
         WAVE_SYNC();
@@ -2600,7 +2619,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           for (int j = 0; j < 4; ++j) L[XP + 255 + kF + 32 * m + j] = qn[4 * m + j];
           }
 #ifndef ASDR_TEMPORAL_RINGS
-          store4_nt(hq_ring + hs * 128 + 32 * m, qn + 4 * m);
+          store4_state<ST_PLAIN>(hq_ring + hs * 128 + 32 * m, qn + 4 * m);
 #else
           store4(hq_ring + hs * 128 + 32 * m, qn + 4 * m);   // newest replaces oldest (loaded before the IF pipeline)
 #endif
@@ -4011,8 +4030,11 @@ extern "C" __global__ void asdr_reset_kernel(UpdateArgs a, const uint32_t *reset
 }
 
 // `variant`: ASDR_KERNEL_PLAIN / _SAM / _ALS / _ALS_SMALL / _SAM_ALS; `uniform`: every wave of the sub-range holds 8 real channels with one schedule key
-extern "C" int asdr_launch_update(const UpdateArgs *a, int variant, int uniform, hipStream_t stream) {
+// `reversed` (may be null): set to 1 when the launch asked for the reversed workgroup order (a->wg_reverse) AND went to one of the three instantiations
+// that honour it; every other kernel ignores the field
+extern "C" int asdr_launch_update_ordered(const UpdateArgs *a, int variant, int uniform, hipStream_t stream, int *reversed) {
   const int n_waves = a->n_sched / 8;
+  if (reversed) *reversed = 0;
   if (n_waves <= 0) return 0;
   if (variant == ASDR_KERNEL_ALS || (variant == ASDR_KERNEL_SAM_ALS && a->xch_sam == nullptr)) { if (uniform) ASDR_LAUNCH(asdr_update_kernel_als, dim3(n_waves), dim3(64), 0, stream, *a); else ASDR_LAUNCH(asdr_update_kernel_als_mixed, dim3(n_waves), dim3(64), 0, stream, *a); }
   else if (variant == ASDR_KERNEL_ALS_SMALL && uniform == 2) {   // chain up to the AGC | the filter + output, two launches (one block per call: the host loops)
@@ -4047,17 +4069,21 @@ extern "C" int asdr_launch_update(const UpdateArgs *a, int variant, int uniform,
       ASDR_LAUNCH(asdr_update_kernel_c16, dim3(n_waves), dim3(64), (size_t)c16_pad, stream, *a);   // (c16_pad: dynamic LDS that takes the occupancy back, measurements)
     else
     if (uniform && mw_on && a->n_blocks == 1 && a->run_if == nullptr && a->direct_ch0 >= 0 && n_waves >= mw_min && a->uni_valid)
-      ASDR_LAUNCH(asdr_update_kernel_mw_u, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a);
+    { if (reversed) *reversed = (int)a->wg_reverse;
+      ASDR_LAUNCH(asdr_update_kernel_mw_u, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a); }
     else
     if (uniform && mw_on && a->n_blocks == 1 && a->run_if == nullptr && a->direct_ch0 >= 0 && n_waves >= mw_min)
-      ASDR_LAUNCH(asdr_update_kernel_mw, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a);
+    { if (reversed) *reversed = (int)a->wg_reverse;
+      ASDR_LAUNCH(asdr_update_kernel_mw, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a); }
     else
-    if (uniform && ASDR_ONEBLK && a->n_blocks == 1 && a->run_if == nullptr) ASDR_LAUNCH(asdr_update_kernel_one, dim3(n_waves), dim3(64), 0, stream, *a);
+    if (uniform && ASDR_ONEBLK && a->n_blocks == 1 && a->run_if == nullptr) { if (reversed) *reversed = (int)a->wg_reverse; ASDR_LAUNCH(asdr_update_kernel_one, dim3(n_waves), dim3(64), 0, stream, *a); }
     else if (uniform) ASDR_LAUNCH(asdr_update_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_update_kernel_mixed, dim3(n_waves), dim3(64), 0, stream, *a);
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+extern "C" int asdr_launch_update(const UpdateArgs *a, int variant, int uniform, hipStream_t stream) { return asdr_launch_update_ordered(a, variant, uniform, stream, nullptr); }
 
 // ALS role streams: the two launches of the chain | filter form on their own (role 0 = the chain up to the AGC, 1 = the filter + output),
 // and the kernel that seeds the stage's "previous block" slot from the als_x ring in front of a call's first block.

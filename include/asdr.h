@@ -180,6 +180,19 @@ int asdr_lanes_enabled(asdr_batch_t *b);
 int asdr_order_after(asdr_batch_t *b, void *stream);
 int asdr_order_before(asdr_batch_t *b, void *stream);
 long asdr_lane_calls(asdr_batch_t *b);
+/* Alternating channel order.  A caller that feeds one block per call makes every launch re-read the state rows the previous launch wrote
+ * (about 3.2 KB per channel).  Walked in the same ascending order every time, a bank whose per-step footprint exceeds the last-level cache
+ * (65,536 channels: ~358 MB against 256 MiB) finds none of them there.  The one-block direct launches of the plain kind (a settings group of
+ * consecutive channels: asdr_update_kernel_mw_u, asdr_update_kernel_mw, asdr_update_kernel_one) can therefore walk their channels forwards in
+ * one launched block and backwards in the next -- the rows written last are read first -- on the batch's streams (each lane within its own
+ * half), on a caller's stream, and block by block inside a multi-block call issued as one launch per block.  Results are bit-identical:
+ * only which workgroup takes which channels changes.  asdr_set_alternate_order(b, 0 / 1) switches it per batch; asdr_reversed_launches() =
+ * launches that ran in the reversed order so far.  Sharded batches forward both to their shards.  Every other launch form keeps the ascending
+ * order.  DEFAULT 0: measured on MI355X (profiles/README.md), neither the step time nor the waves' wait cycles move with the order: if the
+ * re-reads are served from the last-level cache, that buys nothing here (the counters at hand cannot tell).  Environment ASDR_ALTERNATE_ORDER=1 at
+ * asdr_create time = default 1 (ASDR_NO_ALTERNATE_ORDER=1 outranks it). */
+int asdr_set_alternate_order(asdr_batch_t *b, int on);
+long asdr_reversed_launches(asdr_batch_t *b);
 /* SAM role streams: a multi-block call (n_blocks >= 2) of a batch whose schedule is ONE sub-range of SAM channels run as three launches
  * per block (pre | PLL | post: 512 or more SAM channels configured alike) puts the three roles on three streams chained by events, so
  * that pre(k + 1) and PLL(k + 1) run beside post(k): the PLL's 128-step dependent chain per block (about 32 us for any bank size) then
