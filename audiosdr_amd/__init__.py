@@ -9,7 +9,7 @@ missing, construction raises.
 from .binding import (STREAM_BATCH, AGCfast, AGCmedium, AGCoff, AGCslow, ALL, AMmode, BLOCK, CW_LSBmode, CW_USBmode, LSBmode, SAMmode,
                       TAPS, USBmode, WSPRmode, AudioSDRBatch, AsdrError, audio2100, audio2300, audio2500, audio2700,
                       audio2900, audio3100, audio3300, audioAM, audioBypass, audioCW, audioWSPR, library_path,
-                      library_sha256, load_library, host_alloc, host_free)
+                      library_sha256, load_library, host_alloc, host_free, state_field, state_record_bytes, state_record_fields)
 from .front import (NO_DEVICE, AudioGrabberComplex256Batch, AudioIQgeneratorBatch, AudioSDRpreProcessorBatch,  # noqa: E402
                     FRONT_EXPORTS)
 from .tuner import (IQ_CORRECTION_DTYPE, IQ_IDENTITY, IQ_STATS_DTYPE, TUNER_EXPORTS, TUNER_STATE_DTYPE, TunerBank,  # noqa: E402

@@ -60,7 +60,9 @@ EXPORTS = (["asdr_create", "asdr_destroy", "asdr_last_error", "asdr_n_channels",
             "asdr_capture_device_ptr", "asdr_capture_update_device", "asdr_capture_read",
             "asdr_create_sharded", "asdr_n_shards", "asdr_shard", "asdr_shard_first_channel", "asdr_shard_device",
             "asdr_host_alloc", "asdr_host_free", "asdr_host_register", "asdr_host_unregister", "asdr_set_host_chunks",
-            "asdr_host_path_info", "asdr_stream_pipeline_alloc_failures", "asdr_set_launch_split", "asdr_order_after", "asdr_order_before", "asdr_lane_calls", "asdr_sam_role_calls", "asdr_sam_chunk_calls", "asdr_als_role_calls", "asdr_set_lanes", "asdr_set_alternate_order", "asdr_reversed_launches"] +
+            "asdr_host_path_info", "asdr_stream_pipeline_alloc_failures", "asdr_set_launch_split", "asdr_order_after", "asdr_order_before", "asdr_lane_calls", "asdr_sam_role_calls", "asdr_sam_chunk_calls", "asdr_als_role_calls", "asdr_set_lanes", "asdr_set_alternate_order", "asdr_reversed_launches",
+            "asdr_state_record_bytes", "asdr_export_state", "asdr_import_state", "asdr_export_state_device", "asdr_import_state_device",
+            "asdr_state_record_field"] +
            ["asdr_" + n for n in _SETTERS_VOID + _SETTERS_F + _SETTERS_I + _GETTERS_F + _GETTERS_I])
 
 _lib = None
@@ -208,9 +210,50 @@ def load_library(path=None):
     if path is None or hasattr(L, "asdr_set_alternate_order"):
         L.asdr_set_alternate_order.argtypes = [vp, _i]; L.asdr_set_alternate_order.restype = _i
         L.asdr_reversed_launches.argtypes = [vp]; L.asdr_reversed_launches.restype = C.c_long
+    if path is None or hasattr(L, "asdr_state_record_bytes"):   # receiver state records (include/asdr.h)
+        ip = C.POINTER(C.c_int)
+        L.asdr_state_record_bytes.argtypes = []; L.asdr_state_record_bytes.restype = C.c_size_t
+        L.asdr_export_state.argtypes = [vp, ip, _i, vp]; L.asdr_export_state.restype = _i
+        L.asdr_import_state.argtypes = [vp, ip, _i, vp]; L.asdr_import_state.restype = _i
+        L.asdr_export_state_device.argtypes = [vp, ip, _i, vp, vp]; L.asdr_export_state_device.restype = _i
+        L.asdr_import_state_device.argtypes = [vp, ip, _i, vp, vp]; L.asdr_import_state_device.restype = _i
+        L.asdr_state_record_field.argtypes = [_i, ip, ip]; L.asdr_state_record_field.restype = C.c_char_p
     if path is None:
         _lib = L
     return L
+
+
+_STATE_DTYPES = {"u8": np.uint8, "i16": np.int16, "u32": np.uint32, "i32": np.int32, "f32": np.float32}
+
+
+def state_record_bytes():
+    """Size of one receiver state record (asdr_state_record_bytes(): constant for a version, a multiple of 256)."""
+    return int(load_library().asdr_state_record_bytes())
+
+
+def state_record_fields():
+    """The record's field table as the library has it (asdr_state_record_field, include/asdr.h): a list of (name, byte offset, numpy
+    dtype, shape).  Every byte of a record outside these fields is zero."""
+    L = load_library()
+    out, i = [], 0
+    while True:
+        off, cnt = C.c_int(0), C.c_int(0)
+        s = L.asdr_state_record_field(i, C.byref(off), C.byref(cnt))
+        if s is None:
+            return out
+        name, typ = s.decode().split(":")
+        out.append((name, int(off.value), np.dtype(_STATE_DTYPES[typ]), (int(cnt.value),) if cnt.value > 1 else ()))
+        i += 1
+
+
+def state_field(records, name):
+    """A writable view of field `name` in a uint8 [n, RECORD] array of records: shape [n] or [n, count]."""
+    for n_, off, dt, shape in state_record_fields():
+        if n_ == name:
+            cnt = shape[0] if shape else 1
+            v = records[:, off:off + cnt * dt.itemsize].view(dt)
+            return v[:, 0] if not shape else v
+    raise KeyError(name)
 
 
 class AudioSDRBatch:
@@ -479,6 +522,46 @@ class AudioSDRBatch:
         if n < 0:
             raise AsdrError(self._L.asdr_last_error().decode())
         return ms[:n]
+
+    # ---- receiver state records: save, restore and move receivers (include/asdr.h) ----
+    STATE_RECORD_BYTES = 6400   # ASDR_STATE_RECORD_BYTES == asdr_state_record_bytes() (checked by the suite)
+
+    @staticmethod
+    def state_record_fields():
+        return state_record_fields()
+
+    def _state_channels(self, channels, n=None):
+        if channels is None:
+            return None, (self.n_channels if n is None else n)
+        ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+        return ch, ch.size
+
+    def export_state(self, channels=None):
+        """uint8 [n, STATE_RECORD_BYTES]: the records of `channels` (global indices; None = every channel), in that order."""
+        ch, n = self._state_channels(channels)
+        out = np.zeros((n, state_record_bytes()), dtype=np.uint8)
+        self._chk(self._L.asdr_export_state(self._h, None if ch is None else ch.ctypes.data_as(C.POINTER(C.c_int)), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def import_state(self, records, channels=None):
+        """Load records (uint8 [n, STATE_RECORD_BYTES]) into `channels` (None = channels 0 .. n-1).  All or nothing."""
+        rec = np.ascontiguousarray(records, dtype=np.uint8)
+        if rec.ndim != 2 or rec.shape[1] != state_record_bytes():
+            raise AsdrError("records must be uint8 [n, %d]" % state_record_bytes())
+        ch, n = self._state_channels(channels, rec.shape[0])
+        if n != rec.shape[0]:
+            raise AsdrError("one record per channel")
+        self._chk(self._L.asdr_import_state(self._h, None if ch is None else ch.ctypes.data_as(C.POINTER(C.c_int)), n, rec.ctypes.data_as(C.c_void_p)))
+
+    def export_state_device(self, ptr, channels=None, stream=0, n=None):
+        """Records of `channels` into device memory at `ptr` (n x STATE_RECORD_BYTES bytes, 16-byte aligned), asynchronously on `stream`."""
+        ch, n = self._state_channels(channels, n)
+        self._chk(self._L.asdr_export_state_device(self._h, None if ch is None else ch.ctypes.data_as(C.POINTER(C.c_int)), n, C.c_void_p(ptr), C.c_void_p(stream)))
+
+    def import_state_device(self, ptr, channels=None, stream=0, n=None):
+        """Records in device memory at `ptr` into `channels` (the headers are checked on the host first; the state moves asynchronously)."""
+        ch, n = self._state_channels(channels, n)
+        self._chk(self._L.asdr_import_state_device(self._h, None if ch is None else ch.ctypes.data_as(C.POINTER(C.c_int)), n, C.c_void_p(ptr), C.c_void_p(stream)))
 
     # ---- batch-only helpers ----
     def read_status(self):

@@ -358,6 +358,12 @@ struct asdr_batch {
   uint32_t wg_parity = 0;
   bool alternate_order = false;     // off by default: measured, no gain (profiles/README.md); ASDR_ALTERNATE_ORDER=1 / asdr_set_alternate_order
   long stat_reversed_launches = 0;  // launches that ran in the reversed order (asdr_reversed_launches)
+  // receiver state records (asdr_export_state* / asdr_import_state*, the end of this file): pinned and device staging, allocated at first use;
+  // st_ev is recorded behind the last asynchronous use of the pinned half
+  uint8_t *st_h = nullptr, *st_d = nullptr;
+  size_t st_h_cap = 0, st_d_cap = 0;
+  hipEvent_t st_ev = nullptr;
+  bool st_ev_pending = false;
   uint32_t nb_phase = 0;         // blocks processed so far, mod 3 (position of every channel's blanker ring)
   uint32_t als_phase = 0;        // blocks processed so far, mod 2 (position of every channel's ALS input ring)
   ChainConsts k{};
@@ -1127,6 +1133,9 @@ void asdr_destroy(asdr_batch_t *b) {
   for (void *p : ptrs) if (p) hipFree(p);
   b->copy_pool.reset();
   for (int i = 0; i < 3; i++) if (b->h_io[i]) hipHostFree(b->h_io[i]);
+  if (b->st_d) hipFree(b->st_d);
+  if (b->st_h) hipHostFree(b->st_h);
+  if (b->st_ev) hipEventDestroy(b->st_ev);
   for (hipEvent_t e : b->ev_host) hipEventDestroy(e);
   for (hipEvent_t e : b->tev) hipEventDestroy(e);
   if (b->ev0) hipEventDestroy(b->ev0);
@@ -2714,6 +2723,406 @@ int asdr_read_taps(asdr_batch_t *b, float *dst) {
   if (!b || !b->d_taps || !dst) return fail("taps not enabled");
   if (asdr_synchronize(b) != 0) return -1;
   HIPCHK(hipMemcpy(dst, b->d_taps, (size_t)ASDR_N_TAPS * b->n * ASDR_N * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- receiver state records (include/asdr.h "receiver state records"; kernels: asdr_state.hip) ------------------------------------------
+// A record = header | control part (every member of struct Chan, the gain table as its (threshold, slope, knee) triple) | signal part (the nine
+// state rows in canonical order).  The host writes and reads the first ASDR_STATE_OFF_SMALL bytes; the two kernels move the rest.
+extern "C" int asdr_launch_state_gather(const UpdateArgs *a, const int *list, int n, int ch0, int rec0, void *records, const void *ctl, hipStream_t stream);
+extern "C" int asdr_launch_state_scatter(const UpdateArgs *a, const int *list, int n, int ch0, int rec0, const void *records, hipStream_t stream);
+
+namespace {
+
+constexpr size_t kRec = ASDR_STATE_RECORD_BYTES, kCtl = ASDR_STATE_OFF_SMALL;
+constexpr int kStateChunk = 4096;   // records per staging round of the host forms (26 MB pinned + 26 MB of HBM)
+// control words, in record order (word i lives at byte ASDR_STATE_OFF_CONTROL + 4 i)
+enum { CW_IN_GAIN, CW_IN_GAIN_I, CW_IN_GAIN_Q, CW_GAIN_BALANCE, CW_OUTPUT_GAIN, CW_OUT_GAIN, CW_CURRENT_OUT_GAIN, CW_FREQ_SHIFT, CW_MODE, CW_MUTED,
+       CW_CURRENT_FILTER, CW_AF_EN, CW_IF_TABLE, CW_AUDIO_TABLE, CW_ALS_M, CW_ALS_DELAY, CW_ALS_LAMBDA, CW_ALS_EN, CW_ALS_NOTCH, CW_ALS_ADAPTIVE,
+       CW_ALPHA_ATT, CW_BETA_ATT, CW_ALPHA_REL, CW_BETA_REL, CW_ATTACK_MS, CW_RELEASE_MS, CW_KNEE, CW_SLOPE, CW_THRESHOLD, CW_STATIC_GAIN,
+       CW_SLOT129, CW_HANG_COUNT, CW_AGC_EN, CW_NB_THRESHOLD, CW_NB_EN, CW_ZERO, CW_COUNT };
+static_assert(ASDR_STATE_OFF_CONTROL + 4 * CW_COUNT == ASDR_STATE_OFF_SMALL, "control part");
+
+struct StateField { const char *name; int offset, count; };
+#define SF_CW(name, type, w) {name ":" type, ASDR_STATE_OFF_CONTROL + 4 * (w), 1}
+#define SF_SM(name, type, word, count) {name ":" type, ASDR_STATE_OFF_SMALL + 4 * (word), count}
+const StateField kStateFields[] = {
+  {"magic:u32", 0, 1}, {"version:u32", 4, 1}, {"bytes:u32", 8, 1}, {"content:u32", 12, 1},
+  SF_CW("in_gain", "f32", CW_IN_GAIN), SF_CW("in_gain_i", "f32", CW_IN_GAIN_I), SF_CW("in_gain_q", "f32", CW_IN_GAIN_Q), SF_CW("gain_balance", "f32", CW_GAIN_BALANCE),
+  SF_CW("output_gain", "f32", CW_OUTPUT_GAIN), SF_CW("out_gain", "f32", CW_OUT_GAIN), SF_CW("current_out_gain", "f32", CW_CURRENT_OUT_GAIN),
+  SF_CW("freq_shift", "f32", CW_FREQ_SHIFT), SF_CW("mode", "u32", CW_MODE), SF_CW("muted", "u32", CW_MUTED), SF_CW("current_filter", "i32", CW_CURRENT_FILTER),
+  SF_CW("af_en", "u32", CW_AF_EN), SF_CW("if_table", "i32", CW_IF_TABLE), SF_CW("audio_table", "i32", CW_AUDIO_TABLE), SF_CW("als_m", "i32", CW_ALS_M),
+  SF_CW("als_delay", "i32", CW_ALS_DELAY), SF_CW("als_lambda", "f32", CW_ALS_LAMBDA), SF_CW("als_en", "u32", CW_ALS_EN), SF_CW("als_notch", "u32", CW_ALS_NOTCH),
+  SF_CW("als_adaptive", "u32", CW_ALS_ADAPTIVE), SF_CW("agc_alpha_att", "f32", CW_ALPHA_ATT), SF_CW("agc_beta_att", "f32", CW_BETA_ATT),
+  SF_CW("agc_alpha_rel", "f32", CW_ALPHA_REL), SF_CW("agc_beta_rel", "f32", CW_BETA_REL), SF_CW("agc_attack_ms", "f32", CW_ATTACK_MS),
+  SF_CW("agc_release_ms", "f32", CW_RELEASE_MS), SF_CW("agc_knee", "f32", CW_KNEE), SF_CW("agc_slope", "f32", CW_SLOPE), SF_CW("agc_threshold", "f32", CW_THRESHOLD),
+  SF_CW("agc_static_gain", "f32", CW_STATIC_GAIN), SF_CW("agc_slot129", "f32", CW_SLOT129), SF_CW("agc_hang_count", "u32", CW_HANG_COUNT),
+  SF_CW("agc_en", "u32", CW_AGC_EN), SF_CW("nb_threshold", "f32", CW_NB_THRESHOLD), SF_CW("nb_en", "u32", CW_NB_EN),
+  SF_SM("if_state", "f32", 0, 32), SF_SM("img_state", "f32", 32, 32), SF_SM("af_state", "f32", 64, 16), SF_SM("phase_ssb", "f32", 80, 1), SF_SM("phase_am", "f32", 81, 1),
+  SF_SM("nb_avg", "f32", 82, 1), SF_SM("am_carrier", "f32", 83, 1), SF_SM("agc_gain", "f32", 84, 1), SF_SM("agc_old_abs", "f32", 85, 1), SF_SM("agc_hang_counter", "u32", 86, 1),
+  SF_SM("pll_y_re", "f32", 87, 1), SF_SM("pll_y_im", "f32", 88, 1), SF_SM("pll_prev_filt", "f32", 89, 1), SF_SM("pll_d0", "f32", 90, 1), SF_SM("pll_d1", "f32", 91, 1),
+  SF_SM("pll_phase_est", "f32", 92, 1), SF_SM("pll_freq", "f32", 93, 1), SF_SM("hil_slot", "u32", 95, 1), SF_SM("status", "u32", 96, 1), SF_SM("nb_gain", "f32", 97, 6),
+  {"nb_hist:i16", ASDR_STATE_OFF_NB_HIST, 768}, {"nb_mask:u8", ASDR_STATE_OFF_NB_MASK, ASDR_NB_MASK_ROW}, {"hil_q:f32", ASDR_STATE_OFF_HIL_Q, 256},
+  {"hil_i:f32", ASDR_STATE_OFF_HIL_I, 256}, {"als_x:f32", ASDR_STATE_OFF_ALS_X, 256}, {"als_w:f32", ASDR_STATE_OFF_ALS_W, 128},
+  {"audio_prev:f32", ASDR_STATE_OFF_AUDIO_PREV, 128},
+};
+#undef SF_CW
+#undef SF_SM
+static_assert(offsetof(ChanSmall, hil_slot) == 4 * 95 && offsetof(ChanSmall, status) == 4 * 96 && offsetof(ChanSmall, nb_gain) == 4 * 97 &&
+              offsetof(ChanSmall, pll_freq) == 4 * 93 && offsetof(ChanSmall, phase_ssb) == 4 * 80, "field table");
+
+// header + control part of a record from the host half of a channel
+void control_to_record(const Chan &c, uint32_t content, uint8_t *dst) {
+  uint32_t w[kCtl / 4] = {};
+  w[0] = ASDR_STATE_MAGIC; w[1] = ASDR_STATE_VERSION; w[2] = (uint32_t)kRec; w[3] = content;
+  uint32_t *cw = w + ASDR_STATE_OFF_CONTROL / 4;
+  auto F = [&](int i, float v) { memcpy(&cw[i], &v, 4); };
+  auto I = [&](int i, int32_t v) { memcpy(&cw[i], &v, 4); };
+  F(CW_IN_GAIN, c.in_gain); F(CW_IN_GAIN_I, c.in_gain_i); F(CW_IN_GAIN_Q, c.in_gain_q); F(CW_GAIN_BALANCE, c.gain_balance);
+  F(CW_OUTPUT_GAIN, c.output_gain); F(CW_OUT_GAIN, c.out_gain); F(CW_CURRENT_OUT_GAIN, c.current_out_gain); F(CW_FREQ_SHIFT, c.freq_shift);
+  cw[CW_MODE] = c.mode; cw[CW_MUTED] = c.muted; I(CW_CURRENT_FILTER, c.current_filter); cw[CW_AF_EN] = c.af_en;
+  I(CW_IF_TABLE, c.if_table); I(CW_AUDIO_TABLE, c.audio_table); I(CW_ALS_M, c.als_m); I(CW_ALS_DELAY, c.als_delay); F(CW_ALS_LAMBDA, c.als_lambda);
+  cw[CW_ALS_EN] = c.als_en; cw[CW_ALS_NOTCH] = c.als_notch; cw[CW_ALS_ADAPTIVE] = c.als_adaptive;
+  F(CW_ALPHA_ATT, c.agc_alpha_att); F(CW_BETA_ATT, c.agc_beta_att); F(CW_ALPHA_REL, c.agc_alpha_rel); F(CW_BETA_REL, c.agc_beta_rel);
+  F(CW_ATTACK_MS, c.agc_attack_ms); F(CW_RELEASE_MS, c.agc_release_ms);
+  // the gain table as its triple: the members ARE the key of the channel's row of the pool (every setter that changes one rebuilds the table)
+  F(CW_KNEE, c.agc_knee); F(CW_SLOPE, c.agc_slope); F(CW_THRESHOLD, c.agc_threshold);
+  F(CW_STATIC_GAIN, c.agc_static_gain); F(CW_SLOT129, c.agc_slot129); cw[CW_HANG_COUNT] = c.agc_hang_count; cw[CW_AGC_EN] = c.agc_en;
+  F(CW_NB_THRESHOLD, c.nb_threshold); cw[CW_NB_EN] = c.nb_en; cw[CW_ZERO] = 0u;
+  memcpy(dst, w, kCtl);
+}
+
+// what is wrong with a record's first kCtl bytes, or nullptr
+const char *check_record(const uint8_t *p) {
+  uint32_t w[kCtl / 4];
+  memcpy(w, p, kCtl);
+  if (w[0] != ASDR_STATE_MAGIC) return "bad magic";
+  if (w[1] != ASDR_STATE_VERSION) return "version mismatch (records are not portable across versions)";
+  if (w[2] != (uint32_t)kRec) return "wrong size in the `bytes` word";
+  if ((w[3] & ~(ASDR_STATE_HAS_SIGNAL | ASDR_STATE_HAS_AUDIO_PREV)) != 0u) return "unknown content bits";
+  if ((w[3] & ASDR_STATE_HAS_AUDIO_PREV) && !(w[3] & ASDR_STATE_HAS_SIGNAL)) return "content: audio_prev flag without the signal part";
+  const uint32_t *cw = w + ASDR_STATE_OFF_CONTROL / 4;
+  const int32_t if_t = (int32_t)cw[CW_IF_TABLE], au_t = (int32_t)cw[CW_AUDIO_TABLE], m = (int32_t)cw[CW_ALS_M], d = (int32_t)cw[CW_ALS_DELAY], cf = (int32_t)cw[CW_CURRENT_FILTER];
+  if (if_t < ASDR_TBL_IF_SSB || if_t > ASDR_TBL_IF_AM) return "IF table id out of range";
+  if (au_t < ASDR_TBL_AUDIO_BASE + ASDR_audioAM || au_t > ASDR_TBL_AUDIO_BASE + ASDR_audio3300) return "audio table id out of range";
+  if (m < -32768 || m > ASDR_N || d < -32768 || d > 32767 || cf < -32768 || cf > 32767) return "ALS length / delay / filter id out of range";
+  if (cw[CW_MODE] > 0xFFFFu) return "mode out of range";
+  for (int i : {CW_MUTED, CW_AF_EN, CW_ALS_EN, CW_ALS_NOTCH, CW_ALS_ADAPTIVE, CW_AGC_EN, CW_NB_EN}) if (cw[i] > 1u) return "a boolean word is neither 0 nor 1";
+  if (cw[CW_ZERO] != 0u) return "pad word not zero";
+  return nullptr;
+}
+
+// the host half of channel `ch` from a checked record: every member, the gain table found or built in THIS batch's pool (reference counts kept)
+void record_to_chan(asdr_batch *b, int ch, const uint8_t *p) {
+  uint32_t w[kCtl / 4];
+  memcpy(w, p, kCtl);
+  const uint32_t *cw = w + ASDR_STATE_OFF_CONTROL / 4;
+  auto F = [&](int i) { float v; memcpy(&v, &cw[i], 4); return v; };
+  Chan &c = b->ch[ch];
+  c.in_gain = F(CW_IN_GAIN); c.in_gain_i = F(CW_IN_GAIN_I); c.in_gain_q = F(CW_IN_GAIN_Q); c.gain_balance = F(CW_GAIN_BALANCE);
+  c.output_gain = F(CW_OUTPUT_GAIN); c.out_gain = F(CW_OUT_GAIN); c.current_out_gain = F(CW_CURRENT_OUT_GAIN); c.freq_shift = F(CW_FREQ_SHIFT);
+  c.mode = (uint16_t)cw[CW_MODE]; c.muted = cw[CW_MUTED] != 0u; c.current_filter = (int16_t)(int32_t)cw[CW_CURRENT_FILTER]; c.af_en = cw[CW_AF_EN] != 0u;
+  c.if_table = (int32_t)cw[CW_IF_TABLE]; c.audio_table = (int32_t)cw[CW_AUDIO_TABLE];
+  c.als_m = (int16_t)(int32_t)cw[CW_ALS_M]; c.als_delay = (int16_t)(int32_t)cw[CW_ALS_DELAY]; c.als_lambda = F(CW_ALS_LAMBDA);
+  c.als_en = cw[CW_ALS_EN] != 0u; c.als_notch = cw[CW_ALS_NOTCH] != 0u; c.als_adaptive = cw[CW_ALS_ADAPTIVE] != 0u;
+  c.agc_alpha_att = F(CW_ALPHA_ATT); c.agc_beta_att = F(CW_BETA_ATT); c.agc_alpha_rel = F(CW_ALPHA_REL); c.agc_beta_rel = F(CW_BETA_REL);
+  c.agc_attack_ms = F(CW_ATTACK_MS); c.agc_release_ms = F(CW_RELEASE_MS);
+  c.agc_knee = F(CW_KNEE); c.agc_slope = F(CW_SLOPE); c.agc_threshold = F(CW_THRESHOLD);
+  rebuild_agc(b, c);   // the setters' own find-or-create: moves the reference from the channel's old table to the triple's (and clobbers slot 129 ...)
+  c.agc_slot129 = F(CW_SLOT129);   // ... which the record carries as the exporting channel had it)
+  c.agc_static_gain = F(CW_STATIC_GAIN); c.agc_hang_count = cw[CW_HANG_COUNT]; c.agc_en = cw[CW_AGC_EN] != 0u;
+  c.nb_threshold = F(CW_NB_THRESHOLD); c.nb_en = cw[CW_NB_EN] != 0u;
+}
+
+// the entries of one call that one (unsharded) batch owns: local channel and index into the caller's record array; a NULL channel list gives
+// ranges (entry e = channel ch0 + e, record rec0 + e) and no lists
+struct StateEntries {
+  asdr_batch *b = nullptr;
+  std::vector<int> pairs;   // (channel, record) x n, or empty: the range
+  int n = 0, ch0 = 0, rec0 = 0;
+  int ch(int e) const { return pairs.empty() ? ch0 + e : pairs[2 * (size_t)e]; }
+  int rec(int e) const { return pairs.empty() ? rec0 + e : pairs[2 * (size_t)e + 1]; }
+};
+
+int state_stage_reserve(asdr_batch *b, size_t h_bytes, size_t d_bytes) {
+  if (!b->st_ev) HIPCHK(hipEventCreateWithFlags(&b->st_ev, hipEventDisableTiming));
+  if (b->st_ev_pending) { HIPCHK(hipEventSynchronize(b->st_ev)); b->st_ev_pending = false; }   // the pinned half is free again
+  if (h_bytes > b->st_h_cap) {
+    if (b->st_h) { HIPCHK(hipHostFree(b->st_h)); b->st_h = nullptr; b->st_h_cap = 0; }
+    HIPCHK(hipHostMalloc((void **)&b->st_h, h_bytes, hipHostMallocDefault));
+    b->st_h_cap = h_bytes;
+  }
+  if (d_bytes > b->st_d_cap) {
+    if (b->st_d) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(b->st_d)); b->st_d = nullptr; b->st_d_cap = 0; }
+    HIPCHK(hipMalloc((void **)&b->st_d, d_bytes));
+    b->st_d_cap = d_bytes;
+  }
+  return 0;
+}
+
+// `stream` joins the batch's stream order: behind every launch the batch has been given, and the next call on another stream waits for it
+// (the rule of update_device_part)
+int state_order_in(asdr_batch *b, hipStream_t stream) {
+  if (b->lanes_pending) { if (lanes_join_into(b, stream) != 0) return -1; b->lanes_pending = false; b->last_stream = stream; b->last_was_lanes = false; }
+  if (b->ev_last_valid && stream != b->last_stream) {
+    HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
+    HIPCHK(hipStreamWaitEvent(stream, b->ev_last, 0));
+  }
+  return 0;
+}
+void state_order_out(asdr_batch *b, hipStream_t stream) { b->last_stream = stream; b->ev_last_valid = true; b->last_was_lanes = false; }
+
+uint32_t state_content(const asdr_batch *b) {
+  return b->device == ASDR_NO_DEVICE ? 0u : (ASDR_STATE_HAS_SIGNAL | (b->exact_unknown_mode ? ASDR_STATE_HAS_AUDIO_PREV : 0u));
+}
+
+// resets that setters left pending: applied as the next update would apply them first (asdr_read_status does the same)
+int state_apply_resets(asdr_batch *b) {
+  if (!b->reset_pending) return 0;
+  if (sync_all(b) != 0) return -1;
+  return apply_resets(b, b->stream);
+}
+
+int export_host(const StateEntries &en, uint8_t *out) {
+  asdr_batch *b = en.b;
+  const uint32_t content = state_content(b);
+  if (b->device == ASDR_NO_DEVICE) {
+    for (int e = 0; e < en.n; e++) {
+      uint8_t *r = out + (size_t)en.rec(e) * kRec;
+      const Chan &c = b->ch[en.ch(e)];
+      control_to_record(c, content, r);
+      memset(r + kCtl, 0, kRec - kCtl);
+    }
+    return 0;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  if (sync_all(b) != 0) return -1;
+  if (check_stream_error(b) != 0) return -1;
+  if (apply_resets(b, b->stream) != 0) return -1;
+  UpdateArgs a;
+  fill_args(b, a);
+  for (int e0 = 0; e0 < en.n; e0 += kStateChunk) {
+    const int m = std::min(kStateChunk, en.n - e0);
+    const size_t rec_bytes = (size_t)m * kRec, list_bytes = (size_t)m * 2 * sizeof(int);
+    if (state_stage_reserve(b, rec_bytes + list_bytes, rec_bytes + list_bytes) != 0) return -1;
+    int *list = reinterpret_cast<int *>(b->st_h + rec_bytes);
+    for (int i = 0; i < m; i++) { list[2 * i] = en.ch(e0 + i); list[2 * i + 1] = i; }
+    HIPCHK(hipMemcpyAsync(b->st_d + rec_bytes, list, list_bytes, hipMemcpyHostToDevice, b->stream));
+    if (asdr_launch_state_gather(&a, reinterpret_cast<const int *>(b->st_d + rec_bytes), m, 0, 0, b->st_d, nullptr, b->stream) != 0) return fail("state gather kernel launch failed");
+    HIPCHK(hipMemcpyAsync(b->st_h, b->st_d, rec_bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < m; i++) {
+      uint8_t *r = out + (size_t)en.rec(e0 + i) * kRec;
+      const Chan &c = b->ch[en.ch(e0 + i)];
+      memcpy(r + kCtl, b->st_h + (size_t)i * kRec + kCtl, kRec - kCtl);
+      control_to_record(c, content, r);
+    }
+  }
+  return 0;
+}
+
+int export_device(const StateEntries &en, void *d_records, void *stream_) {
+  asdr_batch *b = en.b;
+  if (b->device == ASDR_NO_DEVICE) return fail("control-plane-only batch (ASDR_NO_DEVICE) has no device: use asdr_export_state");
+  hipStream_t stream = (stream_ == ASDR_STREAM_BATCH) ? b->stream : (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(b->device));
+  if (state_apply_resets(b) != 0) return -1;
+  const uint32_t content = state_content(b);
+  const size_t ctl_bytes = (size_t)en.n * kCtl, list_bytes = en.pairs.empty() ? 0 : (size_t)en.n * 2 * sizeof(int);
+  if (state_stage_reserve(b, ctl_bytes + list_bytes, ctl_bytes + list_bytes) != 0) return -1;
+  for (int e = 0; e < en.n; e++) { const Chan &c = b->ch[en.ch(e)]; control_to_record(c, content, b->st_h + (size_t)e * kCtl); }
+  if (list_bytes) memcpy(b->st_h + ctl_bytes, en.pairs.data(), list_bytes);
+  if (state_order_in(b, stream) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(b->st_d, b->st_h, ctl_bytes + list_bytes, hipMemcpyHostToDevice, stream));
+  UpdateArgs a;
+  fill_args(b, a);
+  if (asdr_launch_state_gather(&a, list_bytes ? reinterpret_cast<const int *>(b->st_d + ctl_bytes) : nullptr, en.n, en.ch0, en.rec0, d_records, b->st_d, stream) != 0)
+    return fail("state gather kernel launch failed");
+  HIPCHK(hipEventRecord(b->st_ev, stream)); b->st_ev_pending = true;
+  state_order_out(b, stream);
+  return 0;
+}
+
+// host half of an import (every record has been checked): members, dirty marks, reset bits
+void import_host_half(const StateEntries &en, const uint8_t *ctl, size_t ctl_stride) {
+  asdr_batch *b = en.b;
+  for (int e = 0; e < en.n; e++) {
+    const int ch = en.ch(e);
+    const uint8_t *p = ctl + (size_t)en.rec(e) * ctl_stride;
+    uint32_t content; memcpy(&content, p + 12, 4);
+    record_to_chan(b, ch, p);
+    mark_dirty(b, ch);
+    b->reset[ch] = 0u;   // the next update's reset pass must not wipe what this call loads
+    if (!(content & ASDR_STATE_HAS_SIGNAL)) mark_reset(b, ch, ASDR_R_ALL);   // a control-only record: the signal state at power-on
+  }
+}
+
+bool any_signal(const StateEntries &en, const uint8_t *ctl, size_t ctl_stride) {
+  for (int e = 0; e < en.n; e++) { uint32_t content; memcpy(&content, ctl + (size_t)en.rec(e) * ctl_stride + 12, 4); if (content & ASDR_STATE_HAS_SIGNAL) return true; }
+  return false;
+}
+
+int import_host(const StateEntries &en, const uint8_t *in) {
+  asdr_batch *b = en.b;
+  if (b->device != ASDR_NO_DEVICE && any_signal(en, in, kRec)) {
+    HIPCHK(hipSetDevice(b->device));
+    if (sync_all(b) != 0) return -1;
+    if (check_stream_error(b) != 0) return -1;
+    UpdateArgs a;
+    fill_args(b, a);
+    for (int e0 = 0; e0 < en.n; e0 += kStateChunk) {
+      const int m = std::min(kStateChunk, en.n - e0);
+      const size_t rec_bytes = (size_t)m * kRec, list_bytes = (size_t)m * 2 * sizeof(int);
+      if (state_stage_reserve(b, rec_bytes + list_bytes, rec_bytes + list_bytes) != 0) return -1;
+      int *list = reinterpret_cast<int *>(b->st_h + rec_bytes);
+      for (int i = 0; i < m; i++) { memcpy(b->st_h + (size_t)i * kRec, in + (size_t)en.rec(e0 + i) * kRec, kRec); list[2 * i] = en.ch(e0 + i); list[2 * i + 1] = i; }
+      HIPCHK(hipMemcpyAsync(b->st_d, b->st_h, rec_bytes + list_bytes, hipMemcpyHostToDevice, b->stream));
+      if (asdr_launch_state_scatter(&a, reinterpret_cast<const int *>(b->st_d + rec_bytes), m, 0, 0, b->st_d, b->stream) != 0) return fail("state scatter kernel launch failed");
+      HIPCHK(hipStreamSynchronize(b->stream));
+    }
+  }
+  import_host_half(en, in, kRec);
+  return 0;
+}
+
+// `ctl`: the records' first kCtl bytes as the caller's array has them, already on the host ([record index][kCtl])
+int import_device(const StateEntries &en, const void *d_records, const uint8_t *ctl, hipStream_t stream) {
+  asdr_batch *b = en.b;
+  if (any_signal(en, ctl, kCtl)) {
+    HIPCHK(hipSetDevice(b->device));
+    const size_t list_bytes = en.pairs.empty() ? 0 : (size_t)en.n * 2 * sizeof(int);
+    if (list_bytes) {
+      if (state_stage_reserve(b, list_bytes, list_bytes) != 0) return -1;
+      memcpy(b->st_h, en.pairs.data(), list_bytes);
+    }
+    if (state_order_in(b, stream) != 0) return -1;
+    if (list_bytes) HIPCHK(hipMemcpyAsync(b->st_d, b->st_h, list_bytes, hipMemcpyHostToDevice, stream));
+    UpdateArgs a;
+    fill_args(b, a);
+    if (asdr_launch_state_scatter(&a, list_bytes ? reinterpret_cast<const int *>(b->st_d) : nullptr, en.n, en.ch0, en.rec0, d_records, stream) != 0)
+      return fail("state scatter kernel launch failed");
+    if (list_bytes) { HIPCHK(hipEventRecord(b->st_ev, stream)); b->st_ev_pending = true; }
+    state_order_out(b, stream);
+  }
+  import_host_half(en, ctl, kCtl);
+  return 0;
+}
+
+// index checks of a call, and its entries by owner
+int state_route(asdr_batch *b, const int *channels, int n, bool no_duplicates, std::vector<StateEntries> &out) {
+  if (n > b->n && no_duplicates) return fail("more records than channels: a destination would be named twice");
+  if (channels) {
+    std::vector<uint8_t> seen(no_duplicates ? (size_t)b->n : 0, 0);
+    for (int i = 0; i < n; i++) {
+      const int c = channels[i];
+      if (c < 0 || c >= b->n) return fail("record " + std::to_string(i) + ": channel " + std::to_string(c) + " out of range (0.." + std::to_string(b->n - 1) + ")");
+      if (no_duplicates) { if (seen[c]) return fail("record " + std::to_string(i) + ": channel " + std::to_string(c) + " named twice"); seen[c] = 1; }
+    }
+  } else if (n > b->n) return fail("n exceeds the batch's channel count (channels == NULL names channels 0 .. n-1)");
+  out.clear();
+  if (!is_sharded(b)) {
+    StateEntries en; en.b = b; en.n = n;
+    if (channels) { en.pairs.resize(2 * (size_t)n); for (int i = 0; i < n; i++) { en.pairs[2 * (size_t)i] = channels[i]; en.pairs[2 * (size_t)i + 1] = i; } }
+    out.push_back(std::move(en));
+    return 0;
+  }
+  out.resize(b->shards.size());
+  for (size_t g = 0; g < b->shards.size(); g++) {
+    StateEntries &en = out[g];
+    en.b = b->shards[g];
+    if (!channels) { const int lo = b->shard_first[g], hi = std::min(b->shard_first[g + 1], n); en.n = std::max(0, hi - lo); en.ch0 = 0; en.rec0 = lo; }
+  }
+  if (channels) for (int i = 0; i < n; i++) {
+    int local = channels[i];
+    const std::vector<int> &f = b->shard_first;
+    const int g = (int)(std::upper_bound(f.begin(), f.end(), local) - f.begin()) - 1;
+    local -= f[g];
+    out[g].pairs.push_back(local); out[g].pairs.push_back(i); out[g].n++;
+  }
+  return 0;
+}
+
+int state_one_device(asdr_batch *b) {   // the rule of asdr_update_device_strided: device pointers belong to ONE device
+  if (!is_sharded(b)) return b->device == ASDR_NO_DEVICE ? fail("control-plane-only batch (ASDR_NO_DEVICE) has no device: use the host form") : 0;
+  for (asdr_batch *sh : b->shards) if (sh->device != b->shards[0]->device || sh->device == ASDR_NO_DEVICE)
+    return fail("sharded batch over several devices: device-resident records go to the shards (asdr_shard), host records to asdr_export_state / asdr_import_state");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t asdr_state_record_bytes(void) { return kRec; }
+
+const char *asdr_state_record_field(int i, int *offset, int *count) {
+  if (i < 0 || i >= (int)(sizeof kStateFields / sizeof kStateFields[0])) return nullptr;
+  if (offset) *offset = kStateFields[i].offset;
+  if (count) *count = kStateFields[i].count;
+  return kStateFields[i].name;
+}
+
+int asdr_export_state(asdr_batch_t *b, const int *channels, int n, void *host_records) {
+  if (!b) return fail("null batch");
+  if (n < 0) return fail("n < 0");
+  if (n == 0) return 0;
+  if (!host_records) return fail("null records");
+  std::vector<StateEntries> parts;
+  if (state_route(b, channels, n, false, parts) != 0) return -1;
+  for (const StateEntries &en : parts) if (en.n > 0 && export_host(en, static_cast<uint8_t *>(host_records)) != 0) return -1;
+  return 0;
+}
+
+int asdr_export_state_device(asdr_batch_t *b, const int *channels, int n, void *d_records, void *stream) {
+  if (!b) return fail("null batch");
+  if (n < 0) return fail("n < 0");
+  if (n == 0) return 0;
+  if (!d_records || ((uintptr_t)d_records & 15u) != 0) return fail("device records: null or not 16-byte aligned");
+  if (state_one_device(b) != 0) return -1;
+  std::vector<StateEntries> parts;
+  if (state_route(b, channels, n, false, parts) != 0) return -1;
+  for (const StateEntries &en : parts) if (en.n > 0 && export_device(en, d_records, stream) != 0) return -1;
+  return 0;
+}
+
+int asdr_import_state(asdr_batch_t *b, const int *channels, int n, const void *host_records) {
+  if (!b) return fail("null batch");
+  if (n < 0) return fail("n < 0");
+  if (n == 0) return 0;
+  if (!host_records) return fail("null records");
+  std::vector<StateEntries> parts;
+  if (state_route(b, channels, n, true, parts) != 0) return -1;
+  const uint8_t *in = static_cast<const uint8_t *>(host_records);
+  for (int i = 0; i < n; i++) {   // every record, before anything is written
+    const char *why = check_record(in + (size_t)i * kRec);
+    if (why) return fail("record " + std::to_string(i) + " (channel " + std::to_string(channels ? channels[i] : i) + "): " + why);
+  }
+  for (const StateEntries &en : parts) if (en.n > 0 && import_host(en, in) != 0) return -1;
+  return 0;
+}
+
+int asdr_import_state_device(asdr_batch_t *b, const int *channels, int n, const void *d_records, void *stream_) {
+  if (!b) return fail("null batch");
+  if (n < 0) return fail("n < 0");
+  if (n == 0) return 0;
+  if (!d_records || ((uintptr_t)d_records & 15u) != 0) return fail("device records: null or not 16-byte aligned");
+  if (state_one_device(b) != 0) return -1;
+  std::vector<StateEntries> parts;
+  if (state_route(b, channels, n, true, parts) != 0) return -1;
+  asdr_batch *b0 = is_sharded(b) ? b->shards[0] : b;
+  hipStream_t stream = (stream_ == ASDR_STREAM_BATCH) ? b0->stream : (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(b0->device));
+  // header + control part of every record to the host: validated before any launch (this waits for the work in front of it on `stream`)
+  std::vector<uint8_t> ctl((size_t)n * kCtl);
+  HIPCHK(hipMemcpy2DAsync(ctl.data(), kCtl, d_records, kRec, kCtl, (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (int i = 0; i < n; i++) {
+    const char *why = check_record(ctl.data() + (size_t)i * kCtl);
+    if (why) return fail("record " + std::to_string(i) + " (channel " + std::to_string(channels ? channels[i] : i) + "): " + why);
+  }
+  for (const StateEntries &en : parts) if (en.n > 0 && import_device(en, d_records, ctl.data(), stream) != 0) return -1;
   return 0;
 }
 

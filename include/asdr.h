@@ -444,6 +444,100 @@ const char *asdr_kernels_name(int i);
 unsigned long long asdr_kernels_launches(int i);
 void asdr_kernels_launches_reset(void);
 
+/* ---- receiver state records: save, restore and move receivers.  The reference has no counterpart: an `AudioSDR` object
+ * IS its state (the members of AudioSDR.h:158-246 and the function statics of AudioSDR.cpp:41-44, 690-692), and copying the object copies
+ * the receiver.  Here a receiver's state is spread over a host row (the setters' members) and nine device rows whose ring positions depend
+ * on the batch; a RECORD is that state in one fixed-size, self-contained, position-independent POD blob per channel.
+ *
+ * A record is ASDR_STATE_RECORD_BYTES (= asdr_state_record_bytes(), a multiple of 256) bytes, little-endian, every section 16-byte
+ * aligned, every pad word zero.  Fields (offset: type name -- the member it stands for):
+ *   header
+ *      0: u32 magic            ASDR_STATE_MAGIC ("ASDR")
+ *      4: u32 version          ASDR_STATE_VERSION; any other value is refused (records are not portable across versions)
+ *      8: u32 bytes            ASDR_STATE_RECORD_BYTES
+ *     12: u32 content          ASDR_STATE_HAS_SIGNAL: the signal part below is present (clear: a CONTROL-ONLY record, signal part all zero);
+ *                              ASDR_STATE_HAS_AUDIO_PREV: the audio_prev row was kept by the exporting batch (needs HAS_SIGNAL)
+ *   control part (ASDR_STATE_OFF_CONTROL = 16; one 32-bit word each, booleans as 0 / 1)
+ *     16: f32 in_gain          _inputGain as setInputGain left it (AudioSDR.cpp:232-238): setInputGain multiplies it with gain_balance
+ *     20: f32 in_gain_i        _inputGainI       24: f32 in_gain_q   _inputGainQ
+ *     28: f32 gain_balance     the MEMBER _gainBalance, which setIQgainBalance never writes (its local shadows it, .cpp:240-244)
+ *     32: f32 output_gain      _outputGain       36: f32 out_gain / 40: f32 current_out_gain   setMute's pair (.cpp:249-253)
+ *     44: f32 freq_shift       _freqShift (getTuningOffset)
+ *     48: u32 mode             _mode             52: u32 muted       _isMuted
+ *     56: i32 current_filter   _currentFilter (getAudioFilter)       60: u32 af_en   _audioFilterEnabled
+ *     64: i32 if_table         the IF band-pass as its GLOBAL biquad table id (0 SSB, 1 WSPR, 2 CW, 3 AM: what setDemodMode selected)
+ *     68: i32 audio_table      the audio filter as its global table id (5 + audio filter id 0..9: what setAudioFilter selected)
+ *     72: i32 als_m            _ALS_M            76: i32 als_delay   _ALS_delay          80: f32 als_lambda   _ALS_lambda
+ *     84: u32 als_en           88: u32 als_notch         92: u32 als_adaptive      (_ALSfilterEnabled, _ALSnotch, _ALSadaptive)
+ *     96: f32 agc_alpha_att   100: f32 agc_beta_att     104: f32 agc_alpha_rel    108: f32 agc_beta_rel
+ *    112: f32 agc_attack_ms   116: f32 agc_release_ms   (_agc_attackTime, _agc_releaseTime)
+ *    120: f32 agc_knee        124: f32 agc_slope        128: f32 agc_threshold -- the gain table goes in as THIS TRIPLE, not as an index into the
+ *                              exporting batch's table pool; the importing batch finds or builds its own row (the code the AGC setters use)
+ *    132: f32 agc_static_gain
+ *    136: f32 agc_slot129      _agc_hangTime, which is also _agc_gainLookup[129] (AudioSDR.h:219-220): rebuilt tables overwrite it, setAGChangTime too
+ *    140: u32 agc_hang_count   _agc_hangCount   144: u32 agc_en     _agc_enabled
+ *    148: f32 nb_threshold     _nb_threshold    152: u32 nb_en      _nb_enabled         156: u32 zero
+ *   signal part, in CANONICAL order: independent of the exporting batch's block count, launch form, shard and channel index
+ *    160: ChanSmall (448 B, audiosdr_amd/csrc/asdr_device.h: the biquad states, phases, AGC / PLL / blanker scalars, status bits) with
+ *         hil_slot = 0, nb_gain as [oldest, middle, newest][I, Q], its unused and pad words zero
+ *    608: i16 nb_hist[3][2][128]  the blanker's raw-sample ring as oldest, middle, newest: the two blocks the next update works on and the
+ *                              slot its input goes to (whose content is dead: the block consumed last)
+ *   2144: u8  nb_mask[160]     mask codes (138 used)
+ *   2304: f32 hil_q[2][128]    Hilbert Q history, older -> newer (two blocks back, previous block)
+ *   3328: f32 hil_i[2][128]    mixed I blocks, older -> newer ([1] = the previous block = the 128-sample delay; [0] is the slot the next block goes to)
+ *   4352: f32 als_x[2][128]    ALS input ring as previous, current (current = the slot the next block goes to)
+ *   5376: f32 als_w[128]       ALS coefficients
+ *   5888: f32 audio_prev[128]  _audioOut as the last block left it; zeros (flag clear) when the exporting batch does not keep the row
+ *                              (asdr_set_exact_unknown_mode(b, 0))
+ * Two receivers in the same state give byte-identical records wherever they live.
+ *
+ * NOT in a record, because it is not receiver state: the local-oscillator cache and the pipeline's exchange rows (recomputed), the stage-tap
+ * buffers, the capture sink and its position, timing switches and launch-form switches (properties of a batch), and everything of a tuner
+ * bank (asdr_tuner.h).  A record says nothing about where a receiver's input comes from.
+ *
+ * asdr_export_state / asdr_import_state move `n` records between the batch and HOST memory and return when done; the _device forms move
+ * them between the batch and DEVICE memory of the batch's device, asynchronously on `stream` (ASDR_STREAM_BATCH: the batch's stream).
+ * `channels`: a host array of n GLOBAL channel indices (record i belongs to channels[i]), or NULL for channels 0 .. n-1.
+ *  - Ordering: every call is ordered after every update the batch has been given so far, on whatever stream (as asdr_read_status is), and
+ *    an asdr_update_device on any stream that follows is ordered after it by the rule of asdr_update_device (event on the previous
+ *    call's stream).  asdr_import_state_device reads the records' first 160 bytes (header + control part) on the host before anything
+ *    is written: it returns once the work in front of it on `stream` has completed; the signal parts then move asynchronously.
+ *  - Sharded batches: the host forms route by owner and give the records back in the caller's order; the _device forms are accepted while
+ *    all shards live on one device (the rule of asdr_update_device), otherwise they go through asdr_shard().
+ *  - Export reads only.  Resets that setters left pending (setDemodMode zeroes the IF state, enableALSfilter the ALS rows, ...) are
+ *    APPLIED before the rows are gathered, exactly as the next update would have applied them first (asdr_read_status does the same):
+ *    a record never carries pending resets, and a setter called before the export acts on the imported receiver as on the original.
+ *  - Import is a transaction: n, every index (range, no destination named twice) and every record (magic, version, bytes, content bits,
+ *    table ids) are checked before anything is written; on failure the return code is < 0, asdr_last_error() names the failing record,
+ *    and neither the host half nor the device half of the batch has changed.  On success the channels' parameter rows are marked dirty
+ *    as by a setter (the next update re-sorts the schedule and re-derives the uniform-parameter groups), and their pending reset bits are
+ *    cleared: the next update's reset pass must not wipe what was just loaded.
+ *  - A control-only record (exported by an ASDR_NO_DEVICE batch) sets the settings and puts the signal state at power-on.  An
+ *    ASDR_NO_DEVICE batch imports any record and ignores the signal part.
+ *  - audio_prev: a record with the flag clear zeroes the row of a batch that keeps it; a batch that does not keep the row ignores it.
+ * asdr_state_record_field(i, &offset, &count) names field i of the table above as "name:type" (type one of u8 i16 u32 i32 f32; `count`
+ * elements at `offset`), NULL behind the last one: for tools that read or edit records on the host. */
+#define ASDR_STATE_MAGIC 0x52445341u
+#define ASDR_STATE_VERSION 1u
+#define ASDR_STATE_RECORD_BYTES 6400
+#define ASDR_STATE_HAS_SIGNAL 1u
+#define ASDR_STATE_HAS_AUDIO_PREV 2u
+#define ASDR_STATE_OFF_CONTROL 16
+#define ASDR_STATE_OFF_SMALL 160
+#define ASDR_STATE_OFF_NB_HIST 608
+#define ASDR_STATE_OFF_NB_MASK 2144
+#define ASDR_STATE_OFF_HIL_Q 2304
+#define ASDR_STATE_OFF_HIL_I 3328
+#define ASDR_STATE_OFF_ALS_X 4352
+#define ASDR_STATE_OFF_ALS_W 5376
+#define ASDR_STATE_OFF_AUDIO_PREV 5888
+size_t asdr_state_record_bytes(void);
+int asdr_export_state(asdr_batch_t *b, const int *channels, int n, void *host_records);
+int asdr_import_state(asdr_batch_t *b, const int *channels, int n, const void *host_records);
+int asdr_export_state_device(asdr_batch_t *b, const int *channels, int n, void *d_records, void *stream);
+int asdr_import_state_device(asdr_batch_t *b, const int *channels, int n, const void *d_records, void *stream);
+const char *asdr_state_record_field(int i, int *offset, int *count);
+
 #ifdef __cplusplus
 }
 #endif
