@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "asdr_tuner_device.h"
+#include "asdr_tuner_state.h"
 
 int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
 
@@ -218,6 +219,12 @@ struct asdr_tuner_bank {
   int kp = 8;
   int16_t *d_mid = nullptr;           // [2][n][n_frames * 128]
   size_t mid_cap = 0;
+  // state records (include/asdr_tuner.h, "State records"; the end of this file): pinned and device staging, allocated at first use;
+  // st_ev is recorded behind the last asynchronous use of the pinned half
+  uint8_t *st_h = nullptr, *st_d = nullptr;
+  size_t st_h_cap = 0, st_d_cap = 0;
+  hipEvent_t st_ev = nullptr;
+  bool st_ev_pending = false;
 };
 
 namespace {
@@ -661,6 +668,9 @@ void asdr_tuner_destroy(asdr_tuner_t *t) {
     hipFree(t->d_fc_tab); hipFree(t->d_fc_x); hipFree(t->d_spec); hipFree(t->d_lev); hipFree(t->d_lev_part);
     hipFree(t->d_pal_tab); hipFree(t->d_slot); hipFree(t->d_gain);
     hipFree(t->d_corr); hipFree(t->d_cond); hipFree(t->d_iq_stats);
+    hipFree(t->st_d);
+    if (t->st_h) hipHostFree(t->st_h);
+    if (t->st_ev) hipEventDestroy(t->st_ev);
     if (t->ev0) hipEventDestroy(t->ev0);
     if (t->ev1) hipEventDestroy(t->ev1);
     if (t->stream) hipStreamDestroy(t->stream);
@@ -1350,5 +1360,548 @@ int asdr_tuner_iq_track(asdr_tuner_t *t, int source) {
 }
 
 long long asdr_tuner_condition_launches(const asdr_tuner_t *t) { return t ? t->cond_launches : -1; }
+
+}  // extern "C"
+
+// ---- state records (include/asdr_tuner.h, "State records"; kernels: asdr_tuner_state.hip) -----------------------------------------
+// A channel record = a 256-byte head (written and checked by the host) | the carry row (moved by the two kernels, which also move the
+// level accumulator into / out of the head).  A bank-state blob is host work throughout: plain copies of the sources' rows.
+namespace {
+
+constexpr size_t kRec = ASDR_TUNER_CHANNEL_RECORD_BYTES, kHead = ASDR_TUNER_CHANNEL_OFF_CARRY;
+constexpr int kRecChunk = 8192;   // records per staging round of the host forms (20 MB pinned + 20 MB of HBM)
+static_assert(kRec == kHead + ASDR_TUNER_CARRY * sizeof(int32_t), "record layout");
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// a channel record's head, as the record has it
+struct RecHead {
+  uint32_t magic, version, bytes, content;
+  int32_t kind, dr; int64_t fs_in; int32_t up, down; int64_t pos, out_pos; uint32_t pad0[2];
+  int32_t src; uint32_t fw; int64_t pos_a; uint32_t ph_a; int32_t slot; float gain; uint32_t pad1;
+  double level;
+  uint32_t zero[38];
+};
+static_assert(sizeof(RecHead) == kHead && offsetof(RecHead, kind) == ASDR_TUNER_CHANNEL_OFF_ORIGIN &&
+              offsetof(RecHead, src) == ASDR_TUNER_CHANNEL_OFF_CONTROL && offsetof(RecHead, level) == ASDR_TUNER_CHANNEL_OFF_LEVEL, "record head");
+
+struct RecField { const char *name; int offset, count; };
+const RecField kRecFields[] = {
+  {"magic:u32", 0, 1}, {"version:u32", 4, 1}, {"bytes:u32", 8, 1}, {"content:u32", 12, 1},
+  {"kind:i32", 16, 1}, {"decimation:i32", 20, 1}, {"fs_in:i64", 24, 1}, {"up:i32", 32, 1}, {"down:i32", 36, 1}, {"position:i64", 40, 1},
+  {"output_position:i64", 48, 1}, {"pad0:u32", 56, 2},
+  {"src:i32", 64, 1}, {"fw:u32", 68, 1}, {"pos_a:i64", 72, 1}, {"ph_a:u32", 80, 1}, {"slot:i32", 84, 1}, {"gain:f32", 88, 1}, {"pad1:u32", 92, 1},
+  {"level:f64", 96, 1}, {"pad2:u32", 104, 38},
+};
+
+uint32_t rec_content(const asdr_tuner_t *t) {
+  if (t->device == ASDR_NO_DEVICE) return 0u;
+  return ASDR_TUNER_REC_HAS_SIGNAL | (pass_through(t) ? 0u : ASDR_TUNER_REC_HAS_CARRY) | (t->lev_on ? ASDR_TUNER_REC_HAS_LEVEL : 0u);
+}
+
+void head_of(const asdr_tuner_t *t, int ch, uint8_t *dst) {
+  RecHead h;
+  memset(&h, 0, sizeof h);
+  h.magic = ASDR_TUNER_CHANNEL_MAGIC; h.version = ASDR_TUNER_STATE_VERSION; h.bytes = (uint32_t)kRec; h.content = rec_content(t);
+  h.kind = t->fc ? 1 : 0; h.dr = t->D; h.fs_in = t->fs_in; h.up = t->up; h.down = t->down; h.pos = t->pos; h.out_pos = t->out_pos;
+  const asdr_tuner_state_t &s = t->chan[ch];
+  h.src = s.src; h.fw = s.fw; h.pos_a = s.pos_a; h.ph_a = s.ph_a;
+  h.slot = t->fc ? t->slot[ch] : 0; h.gain = t->fc ? t->gain[ch] : 1.0f;
+  memcpy(dst, &h, sizeof h);
+}
+
+// what keeps the record at p out of bank t, or ""
+std::string head_error(const asdr_tuner_t *t, const uint8_t *p) {
+  RecHead h;
+  memcpy(&h, p, sizeof h);
+  if (h.magic != ASDR_TUNER_CHANNEL_MAGIC) return "bad magic";
+  if (h.version != ASDR_TUNER_STATE_VERSION) return "version mismatch (records are not portable across versions)";
+  if (h.bytes != (uint32_t)kRec) return "wrong size in the `bytes` word";
+  if (h.content & ~(ASDR_TUNER_REC_HAS_SIGNAL | ASDR_TUNER_REC_HAS_CARRY | ASDR_TUNER_REC_HAS_LEVEL)) return "unknown content bits";
+  if ((h.content & (ASDR_TUNER_REC_HAS_CARRY | ASDR_TUNER_REC_HAS_LEVEL)) && !(h.content & ASDR_TUNER_REC_HAS_SIGNAL))
+    return "content: carry or level flag without the signal part";
+  if (h.kind != (t->fc ? 1 : 0)) return "taken from a bank of another kind (direct / rate against fast-convolution)";
+  if (h.dr != t->D) return std::string("taken at another ") + (t->fc ? "R" : "decimation D");
+  if (h.fs_in != t->fs_in) return "taken at another input rate Fs_in";
+  if (h.up != t->up || h.down != t->down) return "taken at another resampling ratio U / M";
+  if (h.pos != t->pos)
+    return "taken at position P = " + std::to_string(h.pos) + ", the bank is at " + std::to_string(t->pos) + " (records move between banks at equal positions only)";
+  if (h.out_pos != t->out_pos)
+    return "taken at output position " + std::to_string(h.out_pos) + ", the bank is at " + std::to_string(t->out_pos);
+  if (h.src < 0 || h.src >= t->n_src) return "source " + std::to_string(h.src) + " out of range (the bank has " + std::to_string(t->n_src) + ")";
+  if (h.pos_a < 0 || h.pos_a > t->pos) return "anchor position outside 0 .. P";
+  if (!std::isfinite(h.gain) || std::fabs(h.gain) > ASDR_TUNER_FC_MAX_GAIN) return "gain must be finite with |gain| <= 32768";
+  if (t->fc) {
+    if (h.slot < 0 || h.slot >= ASDR_TUNER_FC_MAX_FILTERS) return "palette slot must be in 0..63";
+    if (h.slot != 0 && t->pal[h.slot].n == 0) return "palette slot " + std::to_string(h.slot) + " is undefined in this bank";
+  } else {
+    if (h.slot != 0) return "palette slot must be 0 on a bank without a palette";
+    if (h.gain != 1.0f) return "gain must be 1 on a bank without channel gains";
+  }
+  return "";
+}
+
+// index checks of a call
+int rec_indices(const asdr_tuner_t *t, const int *channels, int n, bool no_duplicates) {
+  if (n < 1) return fail("n must be at least 1");
+  if (!channels) return n > t->n ? fail("n exceeds the bank's channel count (channels == NULL names channels 0 .. n-1)") : 0;
+  if (no_duplicates && n > t->n) return fail("more records than channels: a destination would be named twice");
+  std::vector<uint8_t> seen(no_duplicates ? (size_t)t->n : 0, 0);
+  for (int i = 0; i < n; i++) {
+    const int c = channels[i];
+    if (c < 0 || c >= t->n)
+      return fail("record " + std::to_string(i) + ": channel " + std::to_string(c) + " out of range (0.." + std::to_string(t->n - 1) + ")");
+    if (no_duplicates) {
+      if (seen[c]) return fail("record " + std::to_string(i) + ": channel " + std::to_string(c) + " named twice");
+      seen[c] = 1;
+    }
+  }
+  return 0;
+}
+
+// every head of a call ([record i] at heads + i * stride) against the bank
+int rec_check_all(const asdr_tuner_t *t, const int *channels, int n, const uint8_t *heads, size_t stride) {
+  for (int i = 0; i < n; i++) {
+    const std::string why = head_error(t, heads + (size_t)i * stride);
+    if (!why.empty()) return fail("record " + std::to_string(i) + " (channel " + std::to_string(channels ? channels[i] : i) + "): " + why);
+  }
+  return 0;
+}
+
+// the host half of an import (every record has been checked): rows, slots, gains, dirty marks
+void rec_host_half(asdr_tuner_t *t, const int *channels, int n, const uint8_t *heads, size_t stride) {
+  for (int i = 0; i < n; i++) {
+    RecHead h;
+    memcpy(&h, heads + (size_t)i * stride, sizeof h);
+    const int c = channels ? channels[i] : i;
+    asdr_tuner_state_t s = fresh_state();
+    s.src = h.src; s.fw = h.fw; s.pos_a = h.pos_a; s.ph_a = h.ph_a;
+    t->chan[c] = s;
+    if (t->fc) { t->slot[c] = h.slot; t->gain[c] = h.gain; }
+  }
+  t->chan_dirty = t->order_dirty = true;
+  if (t->fc) {
+    t->sg_dirty = true;
+    t->n_off = 0;
+    for (int c = 0; c < t->n; c++) t->n_off += (t->slot[c] != 0 || t->gain[c] != 1.0f);
+  }
+}
+
+int rec_stage_reserve(asdr_tuner_t *t, size_t h_bytes, size_t d_bytes) {
+  if (!t->st_ev) HIPCHK(hipEventCreateWithFlags(&t->st_ev, hipEventDisableTiming));
+  if (t->st_ev_pending) { HIPCHK(hipEventSynchronize(t->st_ev)); t->st_ev_pending = false; }   // the pinned half is free again
+  if (h_bytes > t->st_h_cap) {
+    if (t->st_h) { HIPCHK(hipHostFree(t->st_h)); t->st_h = nullptr; t->st_h_cap = 0; }
+    HIPCHK(hipHostMalloc((void **)&t->st_h, h_bytes, hipHostMallocDefault));
+    t->st_h_cap = h_bytes;
+  }
+  if (d_bytes > t->st_d_cap) {
+    if (t->st_d) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(t->st_d)); t->st_d = nullptr; t->st_d_cap = 0; }
+    HIPCHK(hipMalloc((void **)&t->st_d, d_bytes));
+    t->st_d_cap = d_bytes;
+  }
+  return 0;
+}
+
+// `stream` joins the bank's stream order (the rule of pass_device / rate_device) ...
+int rec_order_in(asdr_tuner_t *t, hipStream_t stream) {
+  if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
+  return 0;
+}
+// ... and the next call on any stream is ordered after what it was given
+int rec_order_out(asdr_tuner_t *t, hipStream_t stream) {
+  if (!t->ev_valid) HIPCHK(hipEventRecord(t->ev0, stream));   // (asdr_tuner_last_kernel_ms reads both)
+  HIPCHK(hipEventRecord(t->ev1, stream));
+  t->ev_valid = true; t->last_stream = stream;
+  return 0;
+}
+
+// the carry the gather reads: the current rows, or none while they are logically zero or do not exist
+int32_t *live_carry(const asdr_tuner_t *t) { return (!pass_through(t) && !t->carry_stale) ? t->d_carry[t->ccur] : nullptr; }
+
+// entries e0 .. e0 + m - 1 of an export into records rec0 .. of d_records, on `stream` (which is in the bank's order)
+int rec_gather(asdr_tuner_t *t, const int *channels, int e0, int m, int rec0, void *d_records, hipStream_t stream) {
+  const size_t head_bytes = (size_t)m * kHead, list_bytes = channels ? (size_t)m * 2 * sizeof(int) : 0;
+  if (rec_stage_reserve(t, head_bytes + list_bytes, head_bytes + list_bytes) != 0) return -1;
+  for (int i = 0; i < m; i++) head_of(t, channels ? channels[e0 + i] : e0 + i, t->st_h + (size_t)i * kHead);
+  int *list = reinterpret_cast<int *>(t->st_h + head_bytes);
+  if (channels) for (int i = 0; i < m; i++) { list[2 * i] = channels[e0 + i]; list[2 * i + 1] = rec0 + i; }
+  HIPCHK(hipMemcpyAsync(t->st_d, t->st_h, head_bytes + list_bytes, hipMemcpyHostToDevice, stream));
+  TunerStateArgs a;
+  a.carry = live_carry(t); a.level = t->lev_on ? t->d_lev : nullptr;
+  if (asdr_launch_tuner_state_gather(&a, channels ? reinterpret_cast<const int *>(t->st_d + head_bytes) : nullptr, m, e0, rec0, d_records, t->st_d, stream) != 0)
+    return fail("tuner state gather kernel launch failed");
+  HIPCHK(hipEventRecord(t->st_ev, stream)); t->st_ev_pending = true;
+  return 0;
+}
+
+// Before the scatter of an import into a bank with a real stage 2: the carry exists and holds what it logically holds.
+int rec_carry_ready(asdr_tuner_t *t, hipStream_t stream) {
+  const size_t cb = (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t);
+  if (!t->d_carry[0] || !t->d_carry[1]) {   // as rate_device allocates it: nothing of ours may be in flight
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (!t->d_carry[0]) HIPCHK(hipMalloc(&t->d_carry[0], cb));
+    if (!t->d_carry[1]) HIPCHK(hipMalloc(&t->d_carry[1], cb));
+    HIPCHK(hipMemset(t->d_carry[t->ccur], 0, cb));
+    HIPCHK(hipDeviceSynchronize());
+    t->carry_stale = false;
+  } else if (t->carry_stale) {
+    HIPCHK(hipMemsetAsync(t->d_carry[t->ccur], 0, cb, stream));
+    t->carry_stale = false;
+  }
+  return 0;
+}
+
+// entries e0 .. e0 + m - 1 of an import from records rec0 .. of d_records, on `stream`; the list (if any) goes through the staging
+// area past `keep` bytes of it
+int rec_scatter(asdr_tuner_t *t, const int *channels, int e0, int m, int rec0, const void *d_records, size_t keep, hipStream_t stream) {
+  const size_t list_bytes = channels ? (size_t)m * 2 * sizeof(int) : 0;
+  if (list_bytes) {
+    int *list = reinterpret_cast<int *>(t->st_h + keep);
+    for (int i = 0; i < m; i++) { list[2 * i] = channels[e0 + i]; list[2 * i + 1] = rec0 + i; }
+    HIPCHK(hipMemcpyAsync(t->st_d + keep, list, list_bytes, hipMemcpyHostToDevice, stream));
+  }
+  TunerStateArgs a;
+  a.carry = pass_through(t) ? nullptr : t->d_carry[t->ccur]; a.level = t->lev_on ? t->d_lev : nullptr;
+  if (!a.carry && !a.level) return 0;   // nothing of the channel lives on the device
+  if (asdr_launch_tuner_state_scatter(&a, list_bytes ? reinterpret_cast<const int *>(t->st_d + keep) : nullptr, m, e0, rec0, d_records, stream) != 0)
+    return fail("tuner state scatter kernel launch failed");
+  if (list_bytes) { HIPCHK(hipEventRecord(t->st_ev, stream)); t->st_ev_pending = true; }
+  return 0;
+}
+
+// ---- the bank-state blob
+constexpr size_t kBlobHead = ASDR_TUNER_BLOB_HEADER_BYTES, kPalEntry = 16 + 2 * ASDR_TUNER_FC_MAX_TAPS * sizeof(float) + 8;   // 1056
+enum { BS_FILTER, BS_RESAMPLER, BS_PALETTE, BS_CORR, BS_STATS, BS_SPECTRUM, BS_HISTORY, BS_UNUSED, BS_COUNT };
+struct BlobHead {
+  uint32_t magic, version; uint64_t bytes;
+  uint32_t content; int32_t kind, dr, n_src;
+  int64_t fs_in; int32_t up, down; int64_t pos, out_pos;
+  int32_t fmt, hist_slots, g, n_taps, g2, k2;
+  int32_t spec_bins, spec_win, spec_mode, lev_on;
+  int64_t spec_frames, lev_frames; int32_t iq_stats_on; uint32_t pad;
+  struct { uint64_t offset, bytes; } dir[BS_COUNT];
+};
+static_assert(sizeof(BlobHead) == kBlobHead && offsetof(BlobHead, dir) == 128 && offsetof(BlobHead, fmt) == 64 &&
+              offsetof(BlobHead, spec_frames) == 104, "blob header");
+static_assert(kPalEntry % 16 == 0, "palette entry");
+
+// the directory that the header's own fields ask for (offsets back to back from kBlobHead); returns the total size
+uint64_t blob_layout(BlobHead &h) {
+  const bool fc = h.kind == 1, sig = (h.content & ASDR_TUNER_BLOB_HAS_SIGNAL) != 0u;
+  uint64_t sz[BS_COUNT];
+  sz[BS_FILTER] = fc ? up16(ASDR_TUNER_FC_MAX_TAPS * sizeof(float)) : ASDR_TUNER_MAX_TAPS * sizeof(int16_t);
+  sz[BS_RESAMPLER] = (uint64_t)h.up * ASDR_TUNER_MAX_RESAMPLER_TAPS * sizeof(int16_t);
+  sz[BS_PALETTE] = fc ? (ASDR_TUNER_FC_MAX_FILTERS - 1) * kPalEntry : 0;
+  sz[BS_CORR] = (uint64_t)h.n_src * sizeof(asdr_tuner_iq_t);
+  sz[BS_STATS] = sig && h.iq_stats_on ? up16((uint64_t)h.n_src * sizeof(asdr_tuner_iq_stats_t)) : 0;
+  sz[BS_SPECTRUM] = sig ? (uint64_t)h.n_src * (uint64_t)h.spec_bins * sizeof(double) : 0;
+  sz[BS_HISTORY] = sig ? (uint64_t)h.n_src * (uint64_t)h.hist_slots * sizeof(int32_t) : 0;
+  sz[BS_UNUSED] = 0;
+  uint64_t off = kBlobHead;
+  for (int k = 0; k < BS_COUNT; k++) {
+    h.dir[k].offset = sz[k] ? off : 0; h.dir[k].bytes = sz[k];
+    off += up16(sz[k]);
+  }
+  return off;
+}
+
+void blob_header(const asdr_tuner_t *t, BlobHead &h) {
+  memset(&h, 0, sizeof h);
+  h.magic = ASDR_TUNER_BANK_MAGIC; h.version = ASDR_TUNER_STATE_VERSION;
+  h.content = (t->device != ASDR_NO_DEVICE ? ASDR_TUNER_BLOB_HAS_SIGNAL : 0u) | (t->carry_stale ? ASDR_TUNER_BLOB_CARRY_STALE : 0u);
+  h.kind = t->fc ? 1 : 0; h.dr = t->D; h.n_src = t->n_src;
+  h.fs_in = t->fs_in; h.up = t->up; h.down = t->down; h.pos = t->pos; h.out_pos = t->out_pos;
+  h.fmt = t->fmt; h.hist_slots = t->hist_slots; h.g = t->fc ? 0 : t->g; h.n_taps = (int32_t)(t->fc ? t->gch.size() : t->h.size());
+  h.g2 = t->g2; h.k2 = t->k2;
+  h.spec_bins = t->spec_bins; h.spec_win = t->spec_bins ? t->spec_win : 0; h.spec_mode = t->spec_bins ? t->spec_mode : 0;
+  h.lev_on = t->lev_on ? 1 : 0;
+  h.spec_frames = t->spec_bins ? t->spec_frames : 0; h.lev_frames = t->lev_on ? t->lev_frames : 0; h.iq_stats_on = t->iq_stats_on ? 1 : 0;
+  h.bytes = blob_layout(h);
+}
+
+// what is wrong with the blob (for a bank of this geometry: t may be NULL, create_from_bank_state checks the geometry by creating), or ""
+std::string blob_error(const asdr_tuner_t *t, const uint8_t *p, size_t bytes) {
+  if (bytes < kBlobHead) return "truncated: shorter than the header";
+  BlobHead h;
+  memcpy(&h, p, sizeof h);
+  if (h.magic != ASDR_TUNER_BANK_MAGIC) return "bad magic";
+  if (h.version != ASDR_TUNER_STATE_VERSION) return "version mismatch (blobs are not portable across versions)";
+  if (h.content & ~(ASDR_TUNER_BLOB_HAS_SIGNAL | ASDR_TUNER_BLOB_CARRY_STALE)) return "unknown content bits";
+  if (h.kind != 0 && h.kind != 1) return "unknown bank kind";
+  if (h.n_src < 1 || h.n_src > 65535) return "n_sources out of range";
+  if (h.up < 1 || h.up > ASDR_TUNER_MAX_UP || h.down < 1) return "resampling ratio out of range";
+  if (h.dr < 1 || h.dr > ASDR_TUNER_FC_MAX_R) return "decimation out of range";
+  if (t) {
+    if (h.kind != (t->fc ? 1 : 0)) return "taken from a bank of another kind (direct / rate against fast-convolution)";
+    if (h.dr != t->D) return std::string("taken at another ") + (t->fc ? "R" : "decimation D");
+    if (h.fs_in != t->fs_in) return "taken at another input rate Fs_in";
+    if (h.up != t->up || h.down != t->down) return "taken at another resampling ratio U / M";
+    if (h.n_src != t->n_src) return "taken from a bank of " + std::to_string(h.n_src) + " sources, this one has " + std::to_string(t->n_src);
+  }
+  const bool fc = h.kind == 1;
+  if (h.hist_slots != (fc ? 128 * h.dr : ASDR_TUNER_HIST_SLOTS)) return "history length does not follow the geometry";
+  if (h.spec_bins < 0 || h.spec_bins > 256 * ASDR_TUNER_FC_MAX_R) return "spectrum bins out of range";
+  BlobHead want = h;
+  const uint64_t total = blob_layout(want);
+  if (h.bytes != total) return "the `bytes` word does not follow the header's fields";
+  if (bytes < total) return "truncated: " + std::to_string(bytes) + " bytes of " + std::to_string(total);
+  if (memcmp(want.dir, h.dir, sizeof h.dir) != 0) return "the section directory does not follow the header's fields";
+  if (h.fmt < ASDR_TUNER_IN_CS16 || h.fmt > ASDR_TUNER_IN_RS16) return "unknown input format";
+  const long long frame = 128LL * h.dr;
+  if (h.pos < 0 || h.pos % frame != 0) return "position P is not a frame boundary";
+  if (h.out_pos < 0 || h.out_pos % 128 != 0) return "output position is not a block boundary";
+  if (h.pad != 0) return "pad word not zero";
+  if (fc) {
+    if (h.n_taps < 1 || h.n_taps > ASDR_TUNER_FC_MAX_TAPS) return "channel filter length must be in 1..129";
+    if (h.g != 0) return "a fast-convolution bank has no stage-1 gain shift";
+    const float *g = reinterpret_cast<const float *>(p + h.dir[BS_FILTER].offset);
+    for (int k = 0; k < h.n_taps; k++) if (!std::isfinite(g[k])) return "channel filter taps must be finite";
+    for (int k = 1; k < ASDR_TUNER_FC_MAX_FILTERS; k++) {
+      const uint8_t *e = p + h.dir[BS_PALETTE].offset + (size_t)(k - 1) * kPalEntry;
+      int32_t n, cx;
+      memcpy(&n, e, 4); memcpy(&cx, e + 4, 4);
+      if (n < 0 || n > ASDR_TUNER_FC_MAX_TAPS || (cx != 0 && cx != 1)) return "palette slot " + std::to_string(k) + ": tap count or complex flag out of range";
+      const float *taps = reinterpret_cast<const float *>(e + 16);
+      for (int i = 0; i < (cx ? 2 * n : n); i++) if (!std::isfinite(taps[i])) return "palette slot " + std::to_string(k) + ": taps must be finite";
+    }
+    if (h.spec_bins != 0) {
+      if (h.spec_bins < 256 || h.spec_bins > 256 * h.dr || (h.spec_bins & (h.spec_bins - 1)) != 0) return "spectrum bins must be 0 or a power of two in 256..N";
+      if (h.spec_win != ASDR_TUNER_WIN_RECT && h.spec_win != ASDR_TUNER_WIN_HANN) return "unknown spectrum window";
+      if (h.spec_mode != ASDR_TUNER_MON_SUM && h.spec_mode != ASDR_TUNER_MON_PEAK) return "unknown spectrum mode";
+    }
+  } else {
+    if (h.n_taps < 1 || h.n_taps > ASDR_TUNER_MAX_TAPS) return "filter length must be in 1..1024";
+    if (h.g < 0 || h.g > ASDR_TUNER_MAX_GAIN_SHIFT) return "gain shift must be in 0..15";
+    const int16_t *f = reinterpret_cast<const int16_t *>(p + h.dir[BS_FILTER].offset);
+    long sum = 0;
+    for (int k = 0; k < h.n_taps; k++) sum += std::labs((long)f[k]);
+    if (sum > 65535) return "sum of |h| exceeds 65535";
+    if (h.spec_bins != 0 || h.lev_on != 0) return "only a fast-convolution bank has monitors";
+  }
+  if (h.lev_on != 0 && h.lev_on != 1) return "the levels switch is neither 0 nor 1";
+  if (h.iq_stats_on != 0 && h.iq_stats_on != 1) return "the statistics switch is neither 0 nor 1";
+  if (h.spec_frames < 0 || h.lev_frames < 0) return "negative frame count";
+  if (h.k2 < 1 || h.k2 > ASDR_TUNER_MAX_RESAMPLER_TAPS) return "resampler taps per phase (K) must be in 1..64";
+  const std::string e2 = resampler_error(h.up, reinterpret_cast<const int16_t *>(p + h.dir[BS_RESAMPLER].offset), h.up * h.k2, h.g2);
+  if (!e2.empty()) return e2;
+  for (int s = 0; s < h.n_src; s++) {
+    asdr_tuner_iq_t c;
+    memcpy(&c, p + h.dir[BS_CORR].offset + (size_t)s * sizeof c, sizeof c);
+    const std::string ec = correction_error(c);
+    if (!ec.empty()) return "source " + std::to_string(s) + ": " + ec;
+  }
+  return "";
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t asdr_tuner_channel_record_bytes(void) { return kRec; }
+
+const char *asdr_tuner_channel_record_field(int i, int *offset, int *count) {
+  if (i < 0 || i >= (int)(sizeof kRecFields / sizeof kRecFields[0])) return nullptr;
+  if (offset) *offset = kRecFields[i].offset;
+  if (count) *count = kRecFields[i].count;
+  return kRecFields[i].name;
+}
+
+int asdr_tuner_export_channels(asdr_tuner_t *t, const int *channels, int n, void *host_records) {
+  if (!t) return fail("null tuner bank");
+  if (rec_indices(t, channels, n, false) != 0) return -1;
+  if (!host_records) return fail("null records");
+  uint8_t *out = static_cast<uint8_t *>(host_records);
+  if (t->device == ASDR_NO_DEVICE) {
+    for (int i = 0; i < n; i++) {
+      head_of(t, channels ? channels[i] : i, out + (size_t)i * kRec);
+      memset(out + (size_t)i * kRec + kHead, 0, kRec - kHead);
+    }
+    return 0;
+  }
+  HIPCHK(hipSetDevice(t->device));
+  if (asdr_tuner_synchronize(t) != 0) return -1;
+  for (int e0 = 0; e0 < n; e0 += kRecChunk) {
+    const int m = std::min(kRecChunk, n - e0);
+    const size_t rec_bytes = (size_t)m * kRec, extra = up16((size_t)m * (kHead + 2 * sizeof(int)));
+    if (rec_stage_reserve(t, rec_bytes + extra, rec_bytes + extra) != 0) return -1;
+    // heads and list behind the chunk's records in both staging halves: rec_gather stages at the front, so gather into the back
+    uint8_t *d_rec = t->st_d + extra;
+    if (rec_gather(t, channels, e0, m, 0, d_rec, t->stream) != 0) return -1;
+    HIPCHK(hipMemcpyAsync(t->st_h + extra, d_rec, rec_bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    memcpy(out + (size_t)e0 * kRec, t->st_h + extra, rec_bytes);
+  }
+  return 0;
+}
+
+int asdr_tuner_export_channels_device(asdr_tuner_t *t, const int *channels, int n, void *d_records, void *stream_) {
+  if (!t) return fail("null tuner bank");
+  if (rec_indices(t, channels, n, false) != 0) return -1;
+  if (t->device == ASDR_NO_DEVICE) return fail("control-plane-only tuner bank (ASDR_NO_DEVICE) has no device: use asdr_tuner_export_channels");
+  if (!d_records || ((uintptr_t)d_records & 15u) != 0) return fail("device records: null or not 16-byte aligned");
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(t->device));
+  if (rec_stage_reserve(t, (size_t)n * (kHead + 2 * sizeof(int)), (size_t)n * (kHead + 2 * sizeof(int))) != 0) return -1;
+  if (rec_order_in(t, stream) != 0) return -1;
+  if (rec_gather(t, channels, 0, n, 0, d_records, stream) != 0) return -1;
+  return rec_order_out(t, stream);
+}
+
+int asdr_tuner_import_channels(asdr_tuner_t *t, const int *channels, int n, const void *host_records) {
+  if (!t) return fail("null tuner bank");
+  if (rec_indices(t, channels, n, true) != 0) return -1;
+  if (!host_records) return fail("null records");
+  const uint8_t *in = static_cast<const uint8_t *>(host_records);
+  if (rec_check_all(t, channels, n, in, kRec) != 0) return -1;
+  if (t->device != ASDR_NO_DEVICE && (!pass_through(t) || t->lev_on)) {
+    HIPCHK(hipSetDevice(t->device));
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+    if (!pass_through(t) && rec_carry_ready(t, t->stream) != 0) return -1;
+    for (int e0 = 0; e0 < n; e0 += kRecChunk) {
+      const int m = std::min(kRecChunk, n - e0);
+      const size_t rec_bytes = (size_t)m * kRec, list_bytes = (size_t)m * 2 * sizeof(int);
+      if (rec_stage_reserve(t, rec_bytes + list_bytes, rec_bytes + list_bytes) != 0) return -1;
+      memcpy(t->st_h, in + (size_t)e0 * kRec, rec_bytes);
+      HIPCHK(hipMemcpyAsync(t->st_d, t->st_h, rec_bytes, hipMemcpyHostToDevice, t->stream));
+      if (rec_scatter(t, channels, e0, m, 0, t->st_d, rec_bytes, t->stream) != 0) return -1;
+      HIPCHK(hipStreamSynchronize(t->stream));
+    }
+  }
+  rec_host_half(t, channels, n, in, kRec);
+  return 0;
+}
+
+int asdr_tuner_import_channels_device(asdr_tuner_t *t, const int *channels, int n, const void *d_records, void *stream_) {
+  if (!t) return fail("null tuner bank");
+  if (rec_indices(t, channels, n, true) != 0) return -1;
+  if (t->device == ASDR_NO_DEVICE) return fail("control-plane-only tuner bank (ASDR_NO_DEVICE) has no device: use asdr_tuner_import_channels");
+  if (!d_records || ((uintptr_t)d_records & 15u) != 0) return fail("device records: null or not 16-byte aligned");
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(t->device));
+  const size_t head_bytes = (size_t)n * kHead, list_bytes = (size_t)n * 2 * sizeof(int);
+  if (rec_stage_reserve(t, head_bytes + list_bytes, head_bytes + list_bytes) != 0) return -1;
+  // every record's head to the host: validated before any launch (this waits for the work in front of it on `stream`)
+  HIPCHK(hipMemcpy2DAsync(t->st_h, kHead, d_records, kRec, kHead, (size_t)n, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (rec_check_all(t, channels, n, t->st_h, kHead) != 0) return -1;
+  if (!pass_through(t) || t->lev_on) {
+    if (rec_order_in(t, stream) != 0) return -1;
+    if (!pass_through(t) && rec_carry_ready(t, stream) != 0) return -1;
+    if (rec_scatter(t, channels, 0, n, 0, d_records, head_bytes, stream) != 0) return -1;
+    if (rec_order_out(t, stream) != 0) return -1;
+  }
+  rec_host_half(t, channels, n, t->st_h, kHead);
+  return 0;
+}
+
+size_t asdr_tuner_bank_state_bytes(const asdr_tuner_t *t) {
+  if (!t) return 0;
+  BlobHead h;
+  blob_header(t, h);
+  return (size_t)h.bytes;
+}
+
+int asdr_tuner_export_bank_state(asdr_tuner_t *t, void *host, size_t capacity) {
+  if (!t) return fail("null tuner bank");
+  if (!host) return fail("null destination");
+  BlobHead h;
+  blob_header(t, h);
+  if (capacity < h.bytes) return fail("bank state: capacity of " + std::to_string(capacity) + " bytes, the blob has " + std::to_string(h.bytes));
+  uint8_t *p = static_cast<uint8_t *>(host);
+  if (t->device != ASDR_NO_DEVICE) {
+    HIPCHK(hipSetDevice(t->device));
+    if (asdr_tuner_synchronize(t) != 0) return -1;
+  }
+  memset(p, 0, (size_t)h.dir[BS_HISTORY].bytes ? (size_t)h.dir[BS_HISTORY].offset : (size_t)h.bytes);   // pads and unused taps (the history has none)
+  memcpy(p, &h, sizeof h);
+  if (t->fc) {
+    memcpy(p + h.dir[BS_FILTER].offset, t->gch.data(), t->gch.size() * sizeof(float));
+    for (int k = 1; k < ASDR_TUNER_FC_MAX_FILTERS; k++) {
+      const asdr_tuner_bank::PaletteSlot &s = t->pal[k];
+      uint8_t *e = p + h.dir[BS_PALETTE].offset + (size_t)(k - 1) * kPalEntry;
+      const int32_t n = s.n, cx = s.n && s.cx ? 1 : 0;
+      memcpy(e, &n, 4); memcpy(e + 4, &cx, 4);
+      if (n) memcpy(e + 16, s.taps.data(), (size_t)(cx ? 2 * n : n) * sizeof(float));
+    }
+  } else {
+    memcpy(p + h.dir[BS_FILTER].offset, t->h.data(), t->h.size() * sizeof(int16_t));
+  }
+  memcpy(p + h.dir[BS_RESAMPLER].offset, t->h2.data(), t->h2.size() * sizeof(int16_t));
+  memcpy(p + h.dir[BS_CORR].offset, t->corr.data(), (size_t)t->n_src * sizeof(asdr_tuner_iq_t));
+  if (h.dir[BS_STATS].bytes) HIPCHK(hipMemcpy(p + h.dir[BS_STATS].offset, t->d_iq_stats, (size_t)t->n_src * sizeof(asdr_tuner_iq_stats_t), hipMemcpyDeviceToHost));
+  if (h.dir[BS_SPECTRUM].bytes) HIPCHK(hipMemcpy(p + h.dir[BS_SPECTRUM].offset, t->d_spec, (size_t)h.dir[BS_SPECTRUM].bytes, hipMemcpyDeviceToHost));
+  if (h.dir[BS_HISTORY].bytes) HIPCHK(hipMemcpy(p + h.dir[BS_HISTORY].offset, t->d_hist[t->cur], (size_t)h.dir[BS_HISTORY].bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int asdr_tuner_import_bank_state(asdr_tuner_t *t, const void *host, size_t bytes) {
+  if (!t) return fail("null tuner bank");
+  if (!host) return fail("null bank state");
+  const uint8_t *p = static_cast<const uint8_t *>(host);
+  const std::string why = blob_error(t, p, bytes);
+  if (!why.empty()) return fail("bank state: " + why);
+  BlobHead h;
+  memcpy(&h, p, sizeof h);
+  const bool dev = t->device != ASDR_NO_DEVICE, sig = (h.content & ASDR_TUNER_BLOB_HAS_SIGNAL) != 0u;
+  if (asdr_tuner_reset(t) != 0) return -1;
+  // the monitors and the statistics first: what can fail here (an allocation) fails with the bank in its reset state
+  if (asdr_tuner_iq_stats_enable(t, h.iq_stats_on) != 0) return -1;
+  if (t->fc) {
+    if (asdr_tuner_spectrum_enable(t, h.spec_bins, h.spec_win, h.spec_mode) != 0) return -1;
+    if (asdr_tuner_levels_enable(t, h.lev_on) != 0) return -1;
+  }
+  t->pos = h.pos; t->out_pos = h.out_pos; t->fmt = h.fmt;
+  t->carry_stale = (h.content & ASDR_TUNER_BLOB_CARRY_STALE) != 0u;
+  if (t->fc) {
+    const float *g = reinterpret_cast<const float *>(p + h.dir[BS_FILTER].offset);
+    t->gch.assign(g, g + h.n_taps);
+    t->g_dirty = true;
+    for (int k = 1; k < ASDR_TUNER_FC_MAX_FILTERS; k++) {
+      const uint8_t *e = p + h.dir[BS_PALETTE].offset + (size_t)(k - 1) * kPalEntry;
+      int32_t n, cx;
+      memcpy(&n, e, 4); memcpy(&cx, e + 4, 4);
+      asdr_tuner_bank::PaletteSlot s;
+      if (n) { const float *taps = reinterpret_cast<const float *>(e + 16); s.taps.assign(taps, taps + (cx ? 2 * n : n)); s.cx = cx != 0; s.n = n; }
+      t->pal[k] = s;
+    }
+    t->pal_dirty = ~0ull;
+    t->spec_frames = h.spec_bins ? h.spec_frames : 0; t->lev_frames = h.lev_on ? h.lev_frames : 0;
+  } else {
+    const int16_t *f = reinterpret_cast<const int16_t *>(p + h.dir[BS_FILTER].offset);
+    t->h.assign(f, f + h.n_taps);
+    t->g = h.g;
+    t->taps_dirty = true;
+  }
+  const int16_t *h2 = reinterpret_cast<const int16_t *>(p + h.dir[BS_RESAMPLER].offset);
+  t->h2.assign(h2, h2 + (size_t)h.up * h.k2);
+  t->g2 = h.g2; t->k2 = h.k2; t->rs_dirty = true;
+  for (int s = 0; s < t->n_src; s++) {
+    asdr_tuner_iq_t c;
+    memcpy(&c, p + h.dir[BS_CORR].offset + (size_t)s * sizeof c, sizeof c);
+    set_correction(t, s, c);
+  }
+  if (dev && sig) {
+    HIPCHK(hipSetDevice(t->device));
+    if (h.dir[BS_STATS].bytes) HIPCHK(hipMemcpy(t->d_iq_stats, p + h.dir[BS_STATS].offset, (size_t)t->n_src * sizeof(asdr_tuner_iq_stats_t), hipMemcpyHostToDevice));
+    if (h.dir[BS_SPECTRUM].bytes) HIPCHK(hipMemcpy(t->d_spec, p + h.dir[BS_SPECTRUM].offset, (size_t)h.dir[BS_SPECTRUM].bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t->d_hist[t->cur], p + h.dir[BS_HISTORY].offset, (size_t)h.dir[BS_HISTORY].bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  return 0;
+}
+
+asdr_tuner_t *asdr_tuner_create_from_bank_state(const void *host, size_t bytes, int n_channels, int device) {
+  if (!host) { fail("null bank state"); return nullptr; }
+  const uint8_t *p = static_cast<const uint8_t *>(host);
+  const std::string why = blob_error(nullptr, p, bytes);
+  if (!why.empty()) { fail("bank state: " + why); return nullptr; }
+  BlobHead h;
+  memcpy(&h, p, sizeof h);
+  asdr_tuner_t *t = h.kind == 1 ? create_fastconv(n_channels, h.n_src, h.fs_in, h.dr, device) : create_bank(n_channels, h.n_src, h.fs_in, h.dr, device);
+  if (!t) return nullptr;
+  if (asdr_tuner_import_bank_state(t, host, bytes) != 0) { asdr_tuner_destroy(t); return nullptr; }   // (this checks U / M against the new bank's)
+  return t;
+}
 
 }  // extern "C"

@@ -23,7 +23,11 @@ TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", 
                  "asdr_tuner_palette_clear", "asdr_tuner_set_channel_slot", "asdr_tuner_read_slots", "asdr_tuner_set_channel_gain",
                  "asdr_tuner_read_gains", "asdr_tuner_set_iq_correction", "asdr_tuner_get_iq_correction",
                  "asdr_tuner_iq_stats_enable", "asdr_tuner_iq_stats_enabled", "asdr_tuner_iq_stats_read", "asdr_tuner_iq_stats_clear",
-                 "asdr_tuner_iq_estimate", "asdr_tuner_iq_track", "asdr_tuner_condition_launches"]
+                 "asdr_tuner_iq_estimate", "asdr_tuner_iq_track", "asdr_tuner_condition_launches",
+                 "asdr_tuner_channel_record_bytes", "asdr_tuner_channel_record_field", "asdr_tuner_export_channels",
+                 "asdr_tuner_import_channels", "asdr_tuner_export_channels_device", "asdr_tuner_import_channels_device",
+                 "asdr_tuner_bank_state_bytes", "asdr_tuner_export_bank_state", "asdr_tuner_import_bank_state",
+                 "asdr_tuner_create_from_bank_state"]
 
 MAX_UP = 2048
 MID_RANGE = (44100, 176400)
@@ -48,6 +52,10 @@ assert IQ_CORRECTION_DTYPE.itemsize == 16 and IQ_STATS_DTYPE.itemsize == 56
 
 TUNER_STATE_DTYPE = np.dtype([("src", "<i4"), ("fw", "<u4"), ("pos_a", "<i8"), ("ph_a", "<u4"), ("reserved", "<u4")])
 assert TUNER_STATE_DTYPE.itemsize == 24
+
+# state records (include/asdr_tuner.h, "State records")
+CHANNEL_RECORD_BYTES = 2560
+_FIELD_TYPES = {"u32": "<u4", "i32": "<i4", "i64": "<i8", "f32": "<f4", "f64": "<f8"}
 
 _typed = False
 
@@ -117,6 +125,16 @@ def _lib():
     L.asdr_tuner_iq_estimate.argtypes = [vp, vp]; L.asdr_tuner_iq_estimate.restype = i
     L.asdr_tuner_iq_track.argtypes = [vp, i]; L.asdr_tuner_iq_track.restype = i
     L.asdr_tuner_condition_launches.argtypes = [vp]; L.asdr_tuner_condition_launches.restype = ll
+    sz, ip = C.c_size_t, C.POINTER(C.c_int)
+    L.asdr_tuner_channel_record_bytes.argtypes = []; L.asdr_tuner_channel_record_bytes.restype = sz
+    L.asdr_tuner_channel_record_field.argtypes = [i, ip, ip]; L.asdr_tuner_channel_record_field.restype = C.c_char_p
+    for n in ("export_channels", "import_channels"):
+        getattr(L, "asdr_tuner_" + n).argtypes = [vp, ip, i, vp]; getattr(L, "asdr_tuner_" + n).restype = i
+        getattr(L, "asdr_tuner_%s_device" % n).argtypes = [vp, ip, i, vp, vp]; getattr(L, "asdr_tuner_%s_device" % n).restype = i
+    L.asdr_tuner_bank_state_bytes.argtypes = [vp]; L.asdr_tuner_bank_state_bytes.restype = sz
+    L.asdr_tuner_export_bank_state.argtypes = [vp, vp, sz]; L.asdr_tuner_export_bank_state.restype = i
+    L.asdr_tuner_import_bank_state.argtypes = [vp, vp, sz]; L.asdr_tuner_import_bank_state.restype = i
+    L.asdr_tuner_create_from_bank_state.argtypes = [vp, sz, i, i]; L.asdr_tuner_create_from_bank_state.restype = vp
     _typed = True
     return L
 
@@ -220,6 +238,46 @@ def estimate_iq_correction(stats):
     return tuple(int(c[k][0]) for k in IQ_CORRECTION_DTYPE.names)
 
 
+def tuner_channel_record_fields():
+    """{name: (numpy dtype string, byte offset, count)} of a channel record's head (asdr_tuner_channel_record_field)."""
+    L = _lib()
+    out, k = {}, 0
+    while True:
+        off, cnt = C.c_int(), C.c_int()
+        name = L.asdr_tuner_channel_record_field(k, C.byref(off), C.byref(cnt))
+        if name is None:
+            return out
+        n, ty = name.decode().split(":")
+        out[n] = (_FIELD_TYPES[ty], int(off.value), int(cnt.value))
+        k += 1
+
+
+def tuner_channel_field(records, name):
+    """A writable view of field `name` of uint8 records [n, 2560] (or one record [2560]): [n] or [n, count] of the field's type;
+    "carry" gives the carry section as uint32 [n, 576] (I low, Q high)."""
+    records = np.asarray(records)
+    if records.dtype != np.uint8 or records.shape[-1] != CHANNEL_RECORD_BYTES or not records.flags.c_contiguous:
+        raise AsdrError("tuner_channel_field: needs C-contiguous uint8 records [n, %d]" % CHANNEL_RECORD_BYTES)
+    r2 = records.reshape(-1, CHANNEL_RECORD_BYTES)
+    if name == "carry":
+        ty, off, cnt = "<u4", 256, 576
+    else:
+        fields = tuner_channel_record_fields()
+        if name not in fields:
+            raise AsdrError("tuner_channel_field: no field %r (one of %s, carry)" % (name, " ".join(fields)))
+        ty, off, cnt = fields[name]
+    v = r2[:, off:off + cnt * np.dtype(ty).itemsize].view(ty)
+    return v[:, 0] if cnt == 1 else v
+
+
+def _channel_list(channels, n_default):
+    """(ctypes int pointer or None, n, the array kept alive) of a channel list; None names channels 0 .. n_default - 1."""
+    if channels is None:
+        return None, int(n_default), None
+    ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+    return ch.ctypes.data_as(C.POINTER(C.c_int)), int(ch.size), ch
+
+
 class _DeviceRows:
     """A device allocation as a __cuda_array_interface__ object, so that torch.as_tensor wraps it without a copy."""
 
@@ -256,6 +314,62 @@ class TunerBank:
         self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(R)
         self.fs_in = int(self._L.asdr_tuner_rate(self._h))
         return self
+
+    # state records (include/asdr_tuner.h, "State records")
+    @classmethod
+    def from_bank_state(cls, blob, n_channels, device=0):
+        """A new bank of the blob's kind and geometry with n_channels channels, holding the blob's state: every channel in creation
+        state at the blob's position, to be filled by import_channels."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        self = cls.__new__(cls)
+        self._L = _lib()
+        self._h = self._L.asdr_tuner_create_from_bank_state(blob.ctypes.data_as(C.c_void_p), int(blob.size), int(n_channels), int(device))
+        if not self._h:
+            raise AsdrError("asdr_tuner_create_from_bank_state failed: %s" % self._L.asdr_last_error().decode())
+        self.n_channels, self.n_sources = int(n_channels), int(self._L.asdr_tuner_n_sources(self._h))
+        self.decimation = int(self._L.asdr_tuner_decimation(self._h))
+        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+        return self
+
+    def bank_state_bytes(self):
+        return int(self._L.asdr_tuner_bank_state_bytes(self._h))
+
+    def export_bank_state(self):
+        """uint8 [bank_state_bytes()]: everything bank-wide and per source; waits for the bank's work and changes nothing."""
+        blob = np.zeros(self.bank_state_bytes(), dtype=np.uint8)
+        self._chk(self._L.asdr_tuner_export_bank_state(self._h, blob.ctypes.data_as(C.c_void_p), int(blob.size)))
+        return blob
+
+    def import_bank_state(self, blob):
+        """Validates the whole blob, then resets the bank and installs it; the channels follow by import_channels."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        self._chk(self._L.asdr_tuner_import_bank_state(self._h, blob.ctypes.data_as(C.c_void_p), int(blob.size)))
+
+    def export_channels(self, channels=None):
+        """uint8 [n, 2560]: the records of `channels` (any order; None: every channel)."""
+        p, n, _keep = _channel_list(channels, self.n_channels)
+        rec = np.zeros((n, CHANNEL_RECORD_BYTES), dtype=np.uint8)
+        self._chk(self._L.asdr_tuner_export_channels(self._h, p, n, rec.ctypes.data_as(C.c_void_p)))
+        return rec
+
+    def import_channels(self, records, channels=None):
+        """records: uint8 [n, 2560]; record i goes to channels[i] (None: channel i).  All-or-nothing."""
+        records = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, CHANNEL_RECORD_BYTES)
+        p, n, _keep = _channel_list(channels, records.shape[0])
+        if n != records.shape[0]:
+            raise AsdrError("import_channels: %d records for %d channels" % (records.shape[0], n))
+        self._chk(self._L.asdr_tuner_import_channels(self._h, p, n, records.ctypes.data_as(C.c_void_p)))
+
+    def export_channels_device(self, ptr, channels=None, stream=0, n=None):
+        """Records of `channels` (None: channels 0 .. n - 1, n defaulting to all) to device memory at ptr (16-byte aligned, n x 2560
+        bytes), asynchronous on `stream` in the bank's stream order."""
+        p, n, _keep = _channel_list(channels, self.n_channels if n is None else n)
+        self._chk(self._L.asdr_tuner_export_channels_device(self._h, p, n, C.c_void_p(ptr), C.c_void_p(stream)))
+
+    def import_channels_device(self, ptr, channels=None, stream=0, n=None):
+        """Record i at ptr to channels[i]; the heads are validated on the host first (a wait on `stream`), the rest runs on `stream`."""
+        p, n, _keep = _channel_list(channels, self.n_channels if n is None else n)
+        self._chk(self._L.asdr_tuner_import_channels_device(self._h, p, n, C.c_void_p(ptr), C.c_void_p(stream)))
 
     def fft_size(self):
         """N of a fast-convolution bank, 0 for a direct-form bank."""

@@ -178,10 +178,77 @@
  *             source (the identity ones: a converted copy) as CS16 (RS16 for an RS16 bank) to a scratch of the bank's, and the
  *             bank's unchanged kernels read the scratch.  An ASDR_NO_DEVICE bank takes the setters, enable and
  *             the estimator and fails the reads, the clear and track.
+ *
+ * State records (every bank kind; everything not named here is unchanged): what asdr.h's receiver state records are to a receiver,
+ * for the tuner in front of it.  A bank's state leaves it in two parts: one variable-size BANK-STATE BLOB (everything that is
+ * bank-wide or per source) and one fixed-size CHANNEL RECORD per channel.  A channel restored from both writes as its next output
+ * the sample the uninterrupted bank would have written, bit for bit.  Both are little-endian, every pad byte is zero, every section
+ * starts 16-byte aligned, and no byte depends on the bank's internal double-buffer parities: two banks that were given the same
+ * samples in calls of different sizes export the same bytes.  An export changes nothing the bank computes; an import is a
+ * transaction: everything is checked on the host before a word of the bank is written, and a refused import (-1, asdr_last_error
+ * names the record or the section) leaves the bank computing exactly what it would have.
+ *   channel   ASDR_TUNER_CHANNEL_RECORD_BYTES = 2560 bytes:
+ *     0 ..   15  magic "ASTC" (u32 ASDR_TUNER_CHANNEL_MAGIC), version 1, bytes (2560), content bits
+ *    16 ..   63  where the record was taken: kind i32 (0 direct / rate, 1 fast-convolution), D or R i32, Fs_in i64, U i32, M i32,
+ *                P i64, output position i64, pad
+ *    64 ..   95  src i32, fw u32, pos_a i64, ph_a u32, palette slot i32, gain f32, pad
+ *    96 ..  103  level accumulator f64 (0 when the levels are off)
+ *   104 ..  255  zero
+ *   256 .. 2559  the stage-2 carry: 576 dwords, slot i = u sample N_u - 576 + i (I low, Q high); zeros when the carry is
+ *                logically zero (before the first stage-2 call, after pass-through calls) or absent (a pass-through stage 2)
+ *             content bits: ASDR_TUNER_REC_HAS_SIGNAL (1) the record came from a bank with a device; ASDR_TUNER_REC_HAS_CARRY (2)
+ *             the carry section is stage-2 history (the bank had a real stage 2); ASDR_TUNER_REC_HAS_LEVEL (4) the level is valid.
+ *             asdr_tuner_channel_record_field lists the head's fields.
+ *   import    checks, all before any write: n >= 1; every index in range; no destination named twice (one RECORD may be named
+ *             for many destinations: cloning); magic, version, bytes, content bits; kind, D / R, Fs_in, U, M equal to the
+ *             destination's; P and the output position equal to the destination's NOW; 0 <= pos_a <= P; src below the
+ *             destination's n_sources; slot a defined palette slot on a fast-convolution bank, 0 elsewhere; gain finite with
+ *             |gain| <= 32768 (exactly 1 elsewhere).  The position rule makes an anchor and a carry mean in the destination what
+ *             they meant in the origin; it holds between a bank and one restored from its blob, and between banks fed in lockstep
+ *             from the same sources (the shards of one deployment).  Moving a channel between banks at different positions is not
+ *             supported.  Then the channel's row (src, fw, anchor), slot and gain are replaced verbatim -- no re-anchoring and no
+ *             flush: a direct-form channel's flushed history is already in pos_a -- the level is written when the destination has
+ *             the levels on, and the carry row when it has a real stage 2 (allocated first if need be; if the pass-through calls
+ *             before had left it stale the whole carry is first made the zeros it logically is, so the other channels still see
+ *             zeros).  A pass-through destination ignores the carry section.  A record without HAS_SIGNAL configures the channel
+ *             and gives it a zero carry and a zero level; an ASDR_NO_DEVICE bank exports and imports the head only.
+ *   ordering  the host forms synchronise with the bank's work and return when done.  The device forms run on `stream` under the
+ *             update calls' rule: `stream` first waits for the previous call's work if that ran on another stream, and the next
+ *             call on any stream is ordered after them.  The device import first brings every record's head to the host (a
+ *             strided copy and a wait on `stream`), validates, and only then launches.  Device records: 16-byte aligned, on the
+ *             bank's device.
+ *   blob      asdr_tuner_bank_state_bytes() bytes; it holds no channel count and nothing per channel.  A 256-byte header:
+ *     0 ..   15  magic "ASTB" (u32 ASDR_TUNER_BANK_MAGIC), version 1, total bytes u64
+ *    16 ..   31  content bits (ASDR_TUNER_BLOB_HAS_SIGNAL 1: the per-source device state is present; ASDR_TUNER_BLOB_CARRY_STALE 2:
+ *                pass-through calls had left the stage-2 history stale), kind i32, D or R i32, n_sources i32
+ *    32 ..   63  Fs_in i64, U i32, M i32, P i64, output position i64
+ *    64 ..   87  input format i32, history dwords per source i32 (1024, or 128 R), stage-1 gain shift g i32 (0 for a
+ *                fast-convolution bank), stage-1 taps i32 (L, or Lg), g2 i32, K i32
+ *    88 ..  103  spectrum bins i32 (0: off), window i32, mode i32, levels on i32
+ *   104 ..  127  spectrum frames i64, level frames i64, I/Q statistics on i32, pad
+ *   128 ..  255  the directory: eight (offset u64, bytes u64) pairs, in this order and laid out back to back from byte 256, each
+ *                section's size rounded up to 16: [0] the stage-1 filter (1024 int16 h, or 129 float g; unused taps zero), [1]
+ *                the stage-2 prototype (U x 64 int16: h2[k U + phi] at word k U + phi, K taps per phase used), [2] the palette
+ *                (fast-convolution banks: slots 1 .. 63, each Lg i32 (0: undefined), complex i32, pad, 258 floats), [3] the
+ *                corrections (n_sources asdr_tuner_iq_t), [4] the statistics (n_sources asdr_tuner_iq_stats_t; only while on and
+ *                HAS_SIGNAL), [5] the spectrum accumulators (n_sources x B f64; likewise), [6] the history rows (n_sources x
+ *                history dwords, oldest sample first: converted, corrected samples, re low, im high; only with HAS_SIGNAL), [7]
+ *                unused (0, 0)
+ *             import: kind, D / R, Fs_in, U, M and n_sources must equal the destination's (n_channels is free); the whole blob is
+ *             validated first (sizes, directory, filter limits as the setters have them, tap counts, gain shifts, correction
+ *             words, monitor configuration, positions on a frame boundary); then it acts as asdr_tuner_reset followed by
+ *             installing the blob: P, the output position, the format, the filters and the palette, the corrections, the
+ *             statistics switch and sums, the monitors' configuration, accumulators and frame counts, the history rows.  Every
+ *             channel is then in creation state at the new P, to be filled by asdr_tuner_import_channels; the level accumulators
+ *             are per channel and travel in the channel records.  A blob whose stage 2 was stale or a pass-through restores that
+ *             condition.  A blob without HAS_SIGNAL (from an ASDR_NO_DEVICE bank) carries the settings only: the histories stay
+ *             the zeros of a reset.  Order of a whole restore: the bank's blob, then its channels, then the receivers' records
+ *             (asdr_import_state) behind them.
  */
 #ifndef ASDR_TUNER_H_
 #define ASDR_TUNER_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "asdr.h"
@@ -355,6 +422,36 @@ int asdr_tuner_iq_estimate(const asdr_tuner_iq_stats_t *s, asdr_tuner_iq_t *c);
  * source whose estimate fails keeps its correction.  Returns the number of sources it set, -1 when the read fails. */
 int asdr_tuner_iq_track(asdr_tuner_t *t, int source);
 long long asdr_tuner_condition_launches(const asdr_tuner_t *t);   /* pre-pass launches since creation */
+
+/* State records (the section above).  channels: a host array of n indices in any order, or NULL for channels 0 .. n - 1. */
+#define ASDR_TUNER_CHANNEL_RECORD_BYTES 2560
+#define ASDR_TUNER_CHANNEL_MAGIC 0x43545341u /* "ASTC" */
+#define ASDR_TUNER_BANK_MAGIC 0x42545341u    /* "ASTB" */
+#define ASDR_TUNER_STATE_VERSION 1u
+#define ASDR_TUNER_CHANNEL_OFF_ORIGIN 16
+#define ASDR_TUNER_CHANNEL_OFF_CONTROL 64
+#define ASDR_TUNER_CHANNEL_OFF_LEVEL 96
+#define ASDR_TUNER_CHANNEL_OFF_CARRY 256
+#define ASDR_TUNER_REC_HAS_SIGNAL 1u
+#define ASDR_TUNER_REC_HAS_CARRY 2u
+#define ASDR_TUNER_REC_HAS_LEVEL 4u
+#define ASDR_TUNER_BLOB_HEADER_BYTES 256
+#define ASDR_TUNER_BLOB_HAS_SIGNAL 1u
+#define ASDR_TUNER_BLOB_CARRY_STALE 2u
+size_t asdr_tuner_channel_record_bytes(void);   /* 2560 */
+/* Field i of a channel record's head as "name:type" (u32, i32, i64, f32, f64), its byte offset and element count; NULL past the
+ * last.  The fields cover bytes 0 .. 255 without gaps or overlaps (pads are fields named pad*). */
+const char *asdr_tuner_channel_record_field(int i, int *offset, int *count);
+int asdr_tuner_export_channels(asdr_tuner_t *t, const int *channels, int n, void *host_records);
+int asdr_tuner_import_channels(asdr_tuner_t *t, const int *channels, int n, const void *host_records);
+int asdr_tuner_export_channels_device(asdr_tuner_t *t, const int *channels, int n, void *d_records, void *stream);
+int asdr_tuner_import_channels_device(asdr_tuner_t *t, const int *channels, int n, const void *d_records, void *stream);
+size_t asdr_tuner_bank_state_bytes(const asdr_tuner_t *t);   /* of the blob an export would write now; 0 for a NULL bank */
+/* Synchronises with the bank's work and writes the blob; fails when capacity is short.  Returns 0 / -1. */
+int asdr_tuner_export_bank_state(asdr_tuner_t *t, void *host, size_t capacity);
+int asdr_tuner_import_bank_state(asdr_tuner_t *t, const void *host, size_t bytes);
+/* A new bank of the blob's kind and geometry with n_channels channels on `device` (or ASDR_NO_DEVICE), then the import. */
+asdr_tuner_t *asdr_tuner_create_from_bank_state(const void *host, size_t bytes, int n_channels, int device);
 
 int asdr_tuner_synchronize(asdr_tuner_t *t);
 float asdr_tuner_last_kernel_ms(asdr_tuner_t *t);  /* device time of the last update (events around its kernels); -1 if none */
