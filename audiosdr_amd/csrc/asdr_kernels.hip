@@ -28,6 +28,77 @@
 #include "asdr_tables.h"
 #include "../../include/asdr.h"
 
+// ---- build switches -------------------------------------------------------------------------------
+// Every compile-time switch of this file and of asdr_fir.h has its default here, once.  Bare flags without a value: -DASDR_TIMELINE (phase time
+// stamps, tools/timeline.py), -DASDR_NB_ALWAYS_SLOW (blanker always on its general path, tools/ablate.py), -DASDR_FENCE (scheduling fences, below).
+#ifndef ASDR_STRIDE
+#define ASDR_STRIDE 388   /* floats per channel row in LDS, plain and SAM kinds (388 = 97 sixteen-byte slots: the rows start on different slots); build flag, measurements */
+#endif
+#ifndef ASDR_ALS_STRIDE
+#define ASDR_ALS_STRIDE 392   /* row length of the short-ALS kinds (8 banks from channel to channel: the filter's operand windows never overlap); build flag, measurements */
+#endif
+#ifndef ASDR_PRE_STRIDE
+#define ASDR_PRE_STRIDE 260   /* row length of the SAM pre role, which needs rows W0 / W1 only; build flag, measurements */
+#endif
+#ifndef ASDR_MW
+#define ASDR_MW 1   /* large one-block direct launches of the plain kernel take the four-wave workgroup form (asdr_update_kernel_mw); 0: one wave per workgroup; environment ASDR_MW overrides (tests, tools) */
+#endif
+#ifndef ASDR_MW_MIN_WAVES
+#define ASDR_MW_MIN_WAVES 64   /* smallest launch, in waves, that takes the four-wave form; environment ASDR_MW_MIN_WAVES overrides (tests, tools/timeline.py) */
+#endif
+#ifndef ASDR_MW_SHARE
+#define ASDR_MW_SHARE 7   /* what the four waves of an MW workgroup share: 1 audio cascades (2 waves x 16 channels), 2 blanker / phase chains, 4 AGC chain (1 wave x 32 channels); build flag, measurements */
+#endif
+#ifndef ASDR_MW_PRIO
+#define ASDR_MW_PRIO 2   /* s_setprio <n> inside the duty sections of the four-wave form (three sibling waves wait for the duty wave); 0: none; build flag, measurements */
+#endif
+#ifndef ASDR_MW_FIR_RING
+#define ASDR_MW_FIR_RING 1   /* the four-wave kernels run the Hilbert FIR with sliding windows in a register ring (asdr_fir.h); 0: the chunked FIR of every other form; build flag, tests/test_four_wave_fir_resources.py reads its call line */
+#endif
+#ifndef ASDR_C16
+#define ASDR_C16 0   /* large direct one-block launches of SSB-class groups take the 16-waves-per-CU kernel (asdr_update_kernel_c16); environment ASDR_C16 overrides (tests, tools) */
+#endif
+#ifndef ASDR_C16_MIN_WAVES
+#define ASDR_C16_MIN_WAVES 64   /* smallest launch, in waves, that takes the 16-waves-per-CU kernel; environment ASDR_C16_MIN_WAVES overrides (tests) */
+#endif
+#ifndef ASDR_STATE_POLICY
+#define ASDR_STATE_POLICY 1   /* cache policy of the state rows that come back a launch later, one-block kernels of the plain kind: 0 streaming, 1 plain stores, 2 + plain loads (see store4_state); build flag, measurements */
+#endif
+#ifndef ASDR_NT_LOADS
+#define ASDR_NT_LOADS 2   /* non-temporal loads for rows read once: 1 input rows, 2 + the blanker ring's oldest block (-1.5 % on C2), 3 + the Hilbert ring's oldest block (no further gain); build flag, measurements */
+#endif
+#ifndef ASDR_PIPE_PK_MASK
+#define ASDR_PIPE_PK_MASK 8   /* kernel kinds whose biquad pipelines run their y-independent products packed: 1 ALS, 2 plain, 4 SAM roles, 8 block pipeline (see biquad_pipe); build flag, measurements */
+#endif
+#ifndef ASDR_PIPE_CHUNK
+#define ASDR_PIPE_CHUNK 8   /* samples per lane per pipeline step: 4 (35 steps) or 8 (19 steps, less per-step overhead); tools/ablate.py builds 4 */
+#endif
+#ifndef ASDR_WAVES_PER_EU
+#define ASDR_WAVES_PER_EU 3   /* register budget of the main instantiations: 3 -> <= 168 VGPRs (12 waves/CU with 13.4 KB of LDS per wave); tools/ablate.py builds 2 */
+#endif
+#ifndef ASDR_ALS_WAVES_PER_EU
+#define ASDR_ALS_WAVES_PER_EU 3   /* register budget of the 516-float ALS kinds (LDS allows 9 waves/CU: needs 3 on one SIMD); build flag, measurements */
+#endif
+#ifndef ASDR_ALS_K_WAVES_PER_EU
+#define ASDR_ALS_K_WAVES_PER_EU 3   /* register budget of the stand-alone ALS kernel (asdr_als_kernel); build flag, measurements */
+#endif
+#ifndef ASDR_POST_BOUNDS
+#define ASDR_POST_BOUNDS ASDR_WAVES_PER_EU   /* register budget of the SAM post role (4 = 128 VGPRs: spills 31); build flag, measurements */
+#endif
+#ifndef ASDR_PLL_LANES
+#define ASDR_PLL_LANES 64   /* channels per wave of the PLL kernel (32 = twice the waves, each half empty); build flag, measurements */
+#endif
+#ifndef ASDR_ABLATE
+#define ASDR_ABLATE 0   /* mask of chain phases compiled out (ABL_* below; outputs are wrong by construction, only the time matters); tools/ablate.py, tools/timeline.py */
+#endif
+#ifndef ASDR_STREAM_R1_CARRY
+#define ASDR_STREAM_R1_CARRY 0   /* role 1 of the block pipeline keeps its IF cascade's state, coefficients and input gains in registers from block to block (measured +1.5 %, off); kept: deleting it moves registers in the generated code; build flag */
+#endif
+#ifndef ASDR_PIPE_BANK_SELECT
+#define ASDR_PIPE_BANK_SELECT 0   /* the stage-0 select of the biquad pipelines as a bank-masked DPP move (measured slower, off; see the step); kept: deleting it moves registers in the generated code; build flag */
+#endif
+// ---- end of the build switches ----------------------------------------------------------------------
+
 // ---- per-channel LDS layout (floats) --------------------------------------------------------------
 // Two instantiations: STRIDE 388 (no channel of the batch uses the ALS filter; 11 waves/CU fit) and 516 (ALS).
 // 388 = 97 sixteen-byte slots == 1 (mod 16): the 8 channels' rows start on different LDS slots.
@@ -35,70 +106,9 @@
 #define W1 128     // working row B: Q
 #define PH 256     // mixer phase sequence [256,384)
 #define XP 0       // Hilbert history x[1..383] in natural order at [0,383), overlays W0/W1/PH once the mixer has consumed them
-#ifndef ASDR_STRIDE
-#define ASDR_STRIDE 388
-#endif
-// Rows of the instantiations whose channels run a SHORT ALS filter on the compact overlay (als_small kinds, SAM + ALS post role): 392 floats,
+// ASDR_ALS_STRIDE: rows of the instantiations whose channels run a SHORT ALS filter on the compact overlay (als_small kinds, SAM + ALS post role): 392 floats,
 // i.e. 8 banks from channel to channel -- the filter's 5-bank operand windows of neighbouring channels then never overlap (at 388, 4 banks
 // apart, they do: 2-way).  One process per build: C4 -2.3 %, all-USB + ALS -2.2 %; the plain kinds lose 1.5 % at 392 and keep 388.
-#ifndef ASDR_AGC_QUIET_PATH
-#define ASDR_AGC_QUIET_PATH 1   /* 0: every block through the chunk loop (measurements) */
-#endif
-#ifndef ASDR_MW_OWN_STORES
-#define ASDR_MW_OWN_STORES 1   /* the four-wave form: a chain's results go back to HBM from the channel's OWN wave (its lead lanes: stores beside its other state), not from the duty wave's 32 lanes */
-#endif
-#ifndef ASDR_AGC_LEAN
-#define ASDR_AGC_LEAN 1   /* the four-wave form's AGC duty: the envelope-only chain when no hang counter can run out inside the block (see the duty) */
-#endif
-#ifndef ASDR_MW_AGC_PIPELINED
-#define ASDR_MW_AGC_PIPELINED 0   /* ... and that chain BESIDE the audio duty, a chunk behind the cascades, while the bank attacks (see the audio duty).  Built, bit-exact, measured
-                                     (round 6): the workgroup's timeline gets 3.5 k cycles shorter in a fresh bank, the launch does not get faster (driver window +0...2.8 %,
-                                     steady state +2.3 %: the early decision, the progress words and the extra waves' instructions cost what the parking saved) -- off */
-#endif
-#ifndef ASDR_ONEBLK
-#define ASDR_ONEBLK 1   /* one-block launches of the plain / short-ALS uniform kernels take their loop-free twins (asdr_launch_update); 0: the looped kernels (measurements) */
-#endif
-#ifndef ASDR_MW
-#define ASDR_MW 1         /* large one-block direct launches of the plain kernel take the four-wave workgroup form (asdr_update_kernel_mw); 0: one wave per workgroup */
-#endif
-#ifndef ASDR_MW_SHARE
-#define ASDR_MW_SHARE 7   /* what the four waves of an MW workgroup share: 1 audio cascades (2 waves x 16 channels), 2 blanker / phase chains, 4 AGC chain (1 wave x 32 channels) */
-#endif
-#ifndef ASDR_MIX_KEEP_Q
-#define ASDR_MIX_KEEP_Q 1   /* uniform SSB waves keep the mixed Q in registers from the mixer to the Hilbert stage (no LDS round trip of the mixed rows); 0: through W0 / W1 */
-#endif
-#ifndef ASDR_UNIT_SCALE
-#define ASDR_UNIT_SCALE 1   /* waves whose input gains are all 1.0 scale their samples with two binary32 operations (scale8); 0: always the binary64 form */
-#endif
-#ifndef ASDR_C16
-#define ASDR_C16 0        /* large direct one-block launches of SSB-class groups take the 16-waves-per-CU kernel (asdr_update_kernel_c16); environment ASDR_C16 overrides */
-#endif
-#ifndef ASDR_C16_MIN_WAVES
-#define ASDR_C16_MIN_WAVES 64
-#endif
-#ifndef ASDR_MW_MIN_WAVES
-#define ASDR_MW_MIN_WAVES 64
-#endif
-#ifndef ASDR_MW_PRIO
-#define ASDR_MW_PRIO 2   /* experiments: s_setprio <n> inside the duty sections of the four-wave form (three sibling waves wait for the duty wave) */
-#endif
-#ifndef ASDR_CHAIN_PRIO
-#define ASDR_CHAIN_PRIO 0   /* experiments: s_setprio <n> around the dependent-chain phases of EVERY form (IF / audio pipelines, blanker / AGC chains) */
-#endif
-#define CHAIN_PRIO_ON() do { if (ASDR_CHAIN_PRIO) __builtin_amdgcn_s_setprio(ASDR_CHAIN_PRIO); } while (0)
-#define CHAIN_PRIO_OFF() do { if (ASDR_CHAIN_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-#ifndef ASDR_ONEBLK_ALS
-#define ASDR_ONEBLK_ALS 1   /* the loop-free form for the ALS instantiations too (short-filter uniform kernel, SAM post role with the filter); 0: measurements */
-#endif
-#ifndef ASDR_ONEBLK_ROLES
-#define ASDR_ONEBLK_ROLES 1   /* the SAM pre / post and the two-launch ALS pre roles (always one block per launch) compiled without the block loop */
-#endif
-#ifndef ASDR_ALS_WINDOW
-#define ASDR_ALS_WINDOW 1   /* the default-length ALS filter reads its operands once per FOUR tap sets (sliding windows in registers); 0: per tap set */
-#endif
-#ifndef ASDR_ALS_STRIDE
-#define ASDR_ALS_STRIDE 392
-#endif
 #define ASDR_COMPACT_ROWS(stride) ((stride) < 500)   /* 388 / 392 against the long filters' 516 */
 #define SCR0 387   // SAM lock flag (last, unused word of the AGC table row; never live together)
 // noise-blanker overlay (dead before the rows above are written)
@@ -118,10 +128,7 @@
 
 typedef float v4f __attribute__((ext_vector_type(4)));   // one aligned VGPR quad (operand of the exchange rings' inline-assembly accesses)   // one aligned VGPR pair: operand of v_pk_mul_f32 / v_pk_add_f32
 
-// Build-time ablation mask for profiling builds (DESIGN.md "ablation"); the shipped library uses 0.
-#ifndef ASDR_ABLATE
-#define ASDR_ABLATE 0
-#endif
+// Build-time ablation mask for profiling builds (ASDR_ABLATE; DESIGN.md "ablation"); the shipped library uses 0.
 #define ABL_NB 1
 #define ABL_IF 2
 #define ABL_SAM 4
@@ -132,11 +139,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));   // one aligned VGPR qua
 #define ABL_AGC 128
 #define ABL_ALS 256
 #define ABL_ON(x) (!(ASDR_ABLATE & (x)))
-
-// register budget of the main instantiation: 3 -> <=168 VGPRs (12 waves/CU with 13.4 KB LDS per wave)
-#ifndef ASDR_WAVES_PER_EU
-#define ASDR_WAVES_PER_EU 3
-#endif
 
 __constant__ float c_bq_pool[ASDR_N_BQ_TABLES][ASDR_BQ_COEFS];
 __constant__ float c_hilbert[ASDR_HILBERT_TAPS];
@@ -181,7 +183,7 @@ __device__ __forceinline__ double div_by_const(double x, double c, double r) {
 //     of q, so its truncation is trunc(q) as well.
 // (Round 2 formed the correctly rounded quotient with a multiply and two fmas: two binary64 operations more per lookup, all of
 // them on the PLL's dependent chain.)  Checked for every float32 phase in [0, 2 pi] by the CPU suite (oracle
-// ao_check_sin_index_one_multiply).  -DASDR_SIN_INDEX_DIV: the round-2 form (measurements).
+// ao_check_sin_index_one_multiply).
 // BELOW_TWO_PI: the caller guarantees phase < twoPI (the PLL: |phase_est| < pi after its wrap, so phase_est and
 // phase_est + pi/2 are below 4.72), which makes the first test dead -- three instructions less on the PLL's dependent chain.
 // NONNEG: the caller guarantees phase >= 0 (the mixer: its phase stays in [0, twoPI], AudioSDR.h:514-517, and so does phase + pi/2),
@@ -191,11 +193,7 @@ template <bool BELOW_TWO_PI = false, bool NONNEG = false>
 __device__ __forceinline__ uint32_t sin_index(float phase, float two_pi, SinIndexK k) {
   if (!BELOW_TWO_PI && phase >= two_pi) phase -= two_pi;
   if (!NONNEG && phase < 0.0f) phase += two_pi;
-#ifdef ASDR_SIN_INDEX_DIV
-  const double q = div_by_const((double)phase * 65535.0, (double)two_pi, k.inv_two_pi);
-#else
   const double q = (double)phase * k.scale;
-#endif
   return (uint32_t)(int)q & 0xFFFFu;
 }
 // AudioSDR.h:365-369: val1 + (((val2 - val1) * (float)delta) / 256.0).  The double divide-by-256 is exact and the
@@ -278,7 +276,6 @@ __device__ __forceinline__ float approx_atan(float z) {
 // selected first; -a - half_pi == -a + (-half_pi) and a - PI == a + (-PI) exactly), the other results are discarded.
 template <bool TWO_SUMS>
 __device__ __forceinline__ float approx_atan2(float y, float x, float half_pi) {
-  const bool xnz = (x != 0.0f);
   const bool big = fabsf(x) > fabsf(y);
   const float num = big ? y : x, den = big ? x : y;
   const float z = num / den;
@@ -298,20 +295,13 @@ __device__ __forceinline__ float approx_atan2(float y, float x, float half_pi) {
     a_pi = (float)((double)a + pis);
   }
   const float r_big = (x > 0.0f) ? a : a_pi;                               // |x| > |y|
-#ifdef ASDR_ATAN2_R4
-  const float r_small = -a + ((y > 0.0f) ? half_pi : -half_pi);            // |x| <= |y|, x != 0
-  const float r_x0 = (y > 0.0f) ? half_pi : ((y < 0.0f) ? -half_pi : 0.0f);   // x == 0
-  return xnz ? (big ? r_big : r_small) : r_x0;
-#else
   // |x| <= |y|, x != 0: y is not zero there, so its sign bit says which half_pi (one v_bfi instead of compare + select).  And the x == 0 branch
   // needs no arithmetic of its own (round 5): with y != 0 it is the value above -- z = 0 / y = +-0, a = +-0, -a + (+-half_pi) = +-half_pi --
   // and with y == 0 or NaN (x == 0 is num == 0 there; `!(|den| > 0)` is the reference's "neither y > 0 nor y < 0") it is 0.  Three vector
   // instructions less per PLL sample; equal bit for bit, NaNs included, on 4 x 10^8 random and special operand pairs (CPU, both forms in C).
-  (void)xnz;
   const float r_small = -a + __builtin_copysignf(half_pi, y);
   const float r = big ? r_big : r_small;
   return (num == 0.0f && !(fabsf(den) > 0.0f)) ? 0.0f : r;
-#endif
 }
 // AudioSDR.h:434-446, n_iter = 1
 __device__ __forceinline__ float fast_sqrt1(float x) {
@@ -364,23 +354,10 @@ __device__ __forceinline__ float dpp_row_shr1(float v) {
 // (ds_read_b128, prefetched a step ahead), stage k>0 takes the previous lane's four outputs of the previous step
 // through DPP row_shr:1, stage 3 writes back in place (ds_write_b128).  The y-independent part
 // p = (b0*x + b1*x1) + b2*x2 of all four samples is off the critical path; the recurrence is 3 dependent ops/sample.
-#ifndef ASDR_PIPE_PK_MASK
-#define ASDR_PIPE_PK_MASK 8   /* which kernel kinds run the pipelines' y-independent products packed (see PIPE_PK in the body): the block pipeline's role waves (alone on their
-                                  SIMDs, where a packed instruction costs an issue slot like any other: C5 share -1 %); everywhere else measured equal or slower */
-#endif
-#ifndef ASDR_PIPE_PREFETCH_FENCE
-#define ASDR_PIPE_PREFETCH_FENCE 0   /* measured: no gain (profiles/README.md, round 5) */
-#endif
-#ifndef ASDR_PIPE_CHUNK
-#define ASDR_PIPE_CHUNK 8   /* samples per lane per pipeline step: 4 (35 steps) or 8 (19 steps, less per-step overhead) */
-#endif
-#ifndef ASDR_PIPE_BANK_SELECT
-#define ASDR_PIPE_BANK_SELECT 0   /* the stage-0 select of the pipelines as a bank-masked DPP move (see the step); 0: round 5's v_cndmask_b32_dpp on VCC */
-#endif
-// SIGNAL (round 6, the four-wave form's audio duty): after every step that wrote a chunk back, the lane `sig` publishes the number of
-// chunks of the row that are final in *prog (release at workgroup scope) -- the AGC duty wave follows one chunk behind.
-template <bool PK = false, bool SIGNAL = false>
-__device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const float *cf, float *sv, int *prog = nullptr, bool sig = false) {
+// ASDR_PIPE_PK_MASK: which kernel kinds run the pipelines' y-independent products packed (see PIPE_PK in the body): the block pipeline's role waves (alone on their
+// SIMDs, where a packed instruction costs an issue slot like any other: C5 share -1 %); everywhere else measured equal or slower.
+template <bool PK = false>
+__device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const float *cf, float *sv) {
   constexpr int C = ASDR_PIPE_CHUNK, NSTEP = ASDR_N / C + 3;
   const float b0 = cf[0], b1 = cf[1], b2 = cf[2], a1 = cf[3], a2 = cf[4];
   float x1 = sv[0], x2 = sv[1], y1 = sv[2], y2 = sv[3];
@@ -391,8 +368,6 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
   for (int q = 0; q < C / 4; ++q) { const float4 t = reinterpret_cast<const float4 *>(row)[q]; xn[4 * q] = t.x; xn[4 * q + 1] = t.y; xn[4 * q + 2] = t.z; xn[4 * q + 3] = t.w; }
   const bool s0 = (st == 0);
   const unsigned long long s0m = __ballot(s0);   // EXEC is full here
-  uint32_t prog_lds = 0u;
-  if constexpr (SIGNAL) prog_lds = (uint32_t)(uintptr_t)(lds_int_ptr)prog;
   auto step = [&](auto edge_tag, const int c) {
     constexpr bool EDGE = decltype(edge_tag)::value;   // a step of the systolic fill / drain: some stages have no chunk
     const int cn = c - st;
@@ -405,7 +380,7 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
     // plain instruction each -- profiles/r05_op_cost.txt -- and under three resident waves that run was a third of a pipeline step.)
 #pragma unroll
     for (int j = 0; j < C; ++j) x[j] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(xn[j]), __float_as_int(yo[j]), 0x114, 0xF, 0xE, false));   // row_shr:4, banks 1..3
-#elif defined(ASDR_PIPE_PLAIN_SELECT) || ASDR_PIPE_CHUNK != 8
+#elif ASDR_PIPE_CHUNK != 8
 #pragma unroll
     for (int j = 0; j < C; ++j) { const float d = dpp_row_shr1(yo[j]); x[j] = s0 ? xn[j] : d; }
 #else
@@ -432,20 +407,6 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
 #pragma unroll
       for (int q = 0; q < C / 4; ++q) { const float4 t = reinterpret_cast<const float4 *>(row)[nc * (C / 4) + q]; xn[4 * q] = t.x; xn[4 * q + 1] = t.y; xn[4 * q + 2] = t.z; xn[4 * q + 3] = t.w; }
     }
-    const uint32_t prog_lds_ = prog_lds;   // (named outside the `if constexpr`: a generic lambda does not capture from inside it)
-    if constexpr (SIGNAL) {
-      // The chunks the PREVIOUS steps wrote back are final: c - 3 of them.  Published here, at the top of the step, so that the wait in front of the
-      // next step's select has a step's arithmetic between it and this write (at the end of the step it sat out the write: +60 cycles per step).  No
-      // release fence: the LDS executes a wave's operations in the order issued, and the "memory" clobber keeps the compiler from moving the row
-      // stores of the previous step below this one.
-      if (c >= 4 && sig) asm volatile("ds_write_b32 %0, %1" :: "v"(prog_lds_), "v"(c - 3) : "memory");
-    }
-#if ASDR_PIPE_PREFETCH_FENCE
-    // Round 5: the two LDS reads stay HERE, at the top of the step.  Left alone the scheduler sinks them to the step's last dozen
-    // instructions (their eight result registers are not needed before the next step), and the `s_waitcnt lgkmcnt(0)` at the top of the
-    // next step then sits out most of an LDS round trip -- once per step, 38 steps per block.
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #if ASDR_PIPE_CHUNK == 8
     if constexpr (PK) {
     // Packed form (same separately rounded operations): samples j and j + 4 share a register pair, so that x[j-1] and x[j-2] of
@@ -489,7 +450,7 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
       for (int q = 0; q < C / 4; ++q) reinterpret_cast<float4 *>(row)[cn * (C / 4) + q] = make_float4(y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]);
     }
   };
-#if defined(ASDR_PIPE_ONE_LOOP) || ASDR_PIPE_CHUNK != 8
+#if ASDR_PIPE_CHUNK != 8
 #pragma unroll 1
   for (int c = 0; c < NSTEP; ++c) step(std::true_type{}, c);
 #else
@@ -503,7 +464,6 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
 #pragma unroll 1
   for (int c = 16; c < NSTEP; ++c) step(std::true_type{}, c);
 #endif
-  if constexpr (SIGNAL) { if (sig) asm volatile("ds_write_b32 %0, %1" :: "v"(prog_lds), "v"(ASDR_N / C) : "memory"); }   // ... and the last one
   sv[0] = x1; sv[1] = x2; sv[2] = y1; sv[3] = y2;
 }
 
@@ -528,9 +488,6 @@ __device__ __forceinline__ void store4_nt(float *p, const float *v) {
   const f4v tv = {v[0], v[1], v[2], v[3]};
   __builtin_nontemporal_store(tv, reinterpret_cast<f4v *>(p));
 }
-#ifndef ASDR_NT_LOADS
-#define ASDR_NT_LOADS 2   /* non-temporal loads for rows a launch reads once and nobody reads again: 1 = input rows, 2 = + the blanker ring's oldest block (-1.5 % on C2), 3 = + the Hilbert ring's oldest block (no further gain) */
-#endif
 __device__ __forceinline__ int4 load_int4_nt(const int4 *p) {
   typedef int i4v __attribute__((ext_vector_type(4)));
   const i4v t = __builtin_nontemporal_load(reinterpret_cast<const i4v *>(p));
@@ -546,13 +503,11 @@ __device__ __forceinline__ void store_int4_nt(int4 *p, int4 v) {
   const i4v tv = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(tv, reinterpret_cast<i4v *>(p));
 }
-#ifndef ASDR_STATE_POLICY
-#define ASDR_STATE_POLICY 1   /* cache policy of the state rows that come back a launch later (newest blanker slot, hil_i / hil_q slots) in the plain kind's one-block
-                                 instantiations (asdr_update_kernel_mw_u / _mw / _one: EVERY launch of them, direct group or not, whatever order it walks):
-                                 0 = as everywhere else: non-temporal stores, the blanker ring's oldest block by non-temporal loads (ASDR_NT_LOADS);
-                                 1 (shipped) = those rows as plain stores: -2.5 % on the C2 step, with or without the alternating order;
-                                 2 = plain stores, and the oldest block by plain loads (gives a part of that back).  Measured: profiles/README.md */
-#endif
+// ASDR_STATE_POLICY: cache policy of the state rows that come back a launch later (newest blanker slot, hil_i / hil_q slots) in the plain kind's one-block
+// instantiations (asdr_update_kernel_mw_u / _mw / _one: EVERY launch of them, direct group or not, whatever order it walks):
+//   0 = as everywhere else: non-temporal stores, the blanker ring's oldest block by non-temporal loads (ASDR_NT_LOADS);
+//   1 (shipped) = those rows as plain stores: -2.5 % on the C2 step, with or without the alternating order;
+//   2 = plain stores, and the oldest block by plain loads (gives a part of that back).  Measured: profiles/README.md
 // a state row's 16 bytes: plain (PLAIN) or streaming
 template <bool PLAIN> __device__ __forceinline__ void store4_state(float *p, const float *v) { if constexpr (PLAIN) store4(p, v); else store4_nt(p, v); }
 template <bool PLAIN> __device__ __forceinline__ void store_int4_state(int4 *p, int4 v) { if constexpr (PLAIN) *p = v; else store_int4_nt(p, v); }
@@ -583,11 +538,7 @@ __device__ __forceinline__ void scale8(const int16_t *s, double g, float *out, b
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-#ifdef ASDR_OLD_SCALE
-    out[j] = (float)(div_by_const((double)s[j], 32767.0, 1.0 / 32767.0) * g);
-#else
     out[j] = (float)(div_i16_by_32767((double)s[j]) * g);
-#endif
     if ((j & 1) == 1) SCHED_FENCE();
   }
 }
@@ -791,15 +742,12 @@ __device__ __forceinline__ const T *row_ptr(const T *base, uint32_t byte_off) {
 // CH = samples per loop trip (4 from LDS; 16 in the PLL kernel, whose accessor requests the next trip's samples from HBM first).
 // PF: the accessor reads HBM (the stand-alone PLL kernel): the NEXT trip's samples are requested before this trip's arithmetic, so
 // that the chain never waits for memory.
-#ifndef ASDR_PLL_CONSTS_IN_VGPRS
-#define ASDR_PLL_CONSTS_IN_VGPRS 1   /* the stand-alone PLL kernel keeps the loop's constants in VGPRs (a quarter of its vector instructions read the scalar file otherwise: tools/ubench/issue_rate.hip) */
-#endif
 template <bool TWO_SUMS, int CH, bool PF = false, typename LD, typename ST>
 __device__ __forceinline__ bool pll_loop(ChanSmall *Sc, const ChainConsts &K_, const float *sine, float two_pi, LD ld, ST st) {
     // PF = the stand-alone PLL kernel (51 VGPRs, four homogeneous waves per SIMD: exactly the situation of the issue-rate micro-benchmark): its
     // constants as VGPR operands.  The fused kernels (no register to spare) keep them scalar.
     ChainConsts K = K_;
-    if constexpr (PF && ASDR_PLL_CONSTS_IN_VGPRS) {
+    if constexpr (PF) {
       asm("" : "+v"(K.pll_a1), "+v"(K.pll_b0), "+v"(K.pll_b1), "+v"(K.half_pi_f), "+v"(two_pi), "+v"(K.pll_alpha_freq), "+v"(K.pll_beta_freq), "+v"(K.pll_f_conv),
                "+v"(K.pll_lock_lo), "+v"(K.pll_lock_hi));
       asm("" : "+v"(K.sin_index_scale_d), "+v"(K.half_pi_d));
@@ -851,12 +799,7 @@ __device__ __forceinline__ bool pll_loop(ChanSmall *Sc, const ChainConsts &K_, c
             while (phase_est <= -pi_up && turns < ASDR_PLL_WRAP_MAX) { phase_est += two_pi; ++turns; }
             if (turns >= ASDR_PLL_WRAP_MAX) phase_est = 0.0f;
           } }
-#ifndef ASDR_PLL_FLAT_LOOKUPS
         sincos_pll(sine, phase_est, y_re, y_im, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);   // |phase_est| < pi here (wrap above)
-#else
-        y_re = cos_f32<true>(sine, phase_est, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);   // |phase_est| < pi here (wrap above)
-        y_im = sin_f32<true>(sine, phase_est, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d});
-#endif
         pfreq = K.pll_alpha_freq * pfreq + K.pll_beta_freq * (filt * K.pll_f_conv);
         locked = (pfreq > K.pll_lock_lo) && (pfreq < K.pll_lock_hi);
         const float o_re = x_re * y_re + x_im * y_im, o_im = -x_re * y_im + x_im * y_re;
@@ -871,39 +814,13 @@ __device__ __forceinline__ bool pll_loop(ChanSmall *Sc, const ChainConsts &K_, c
 }
 
 // Folded Hilbert FIR of the update kernels (asdr_fir.h): Lrow = the channel's LDS row (history at XP), taps c_hilbert.
-template <int E0, int NE, bool TAPS_V = (ASDR_FIR_TAPS_IN_VGPRS != 0)>
+template <int E0, int NE>
 __device__ __forceinline__ void hilbert_fir(const float *Lrow, int p0, v2f *acc2) {
-  hilbert_fir_rows<E0, NE, TAPS_V>(Lrow + XP, p0, acc2, c_hilbert);
+  hilbert_fir_rows<E0, NE>(Lrow + XP, p0, acc2, c_hilbert);
 }
 // ... and of the four-wave kernels: sliding windows in a register ring (asdr_fir.h).
-#ifndef ASDR_MW_FIR_RING
-#define ASDR_MW_FIR_RING 1   /* 0: the four-wave kernels run the chunked FIR of every other form (measurements) */
-#endif
-#ifndef ASDR_MW_HIST_B128
-#define ASDR_MW_HIST_B128 0   /* 1: the four-wave kernels stage the Hilbert history with one LDS store per 16 bytes (hilbert_hist_store16: 12 ds_write_b128 for 38 stores).  Built,
-                                 bit-exact, measured (profiles/README.md): 28 LDS instructions and 288 bank-conflict cycles fewer per wave, 35 DPP moves / selects and 36 register
-                                 moves more -- +0.6 % alone, +0.8 % on top of the ring FIR, every run above every run of the build without it -- off */
-#endif
 __device__ __forceinline__ void hilbert_fir_ring(const float *Lrow, int p0, v2f *acc2) {
   hilbert_fir_rows_ring(Lrow + XP, p0, acc2, c_hilbert);
-}
-// One block of the Hilbert history, 16-byte stores.  v[4 m + j] = x[B + kF + 32 m + j] goes to word B + kF + 32 m + j - 1: the aligned piece at word
-// B + kF + 32 m holds this lane's j = 1..3 and the j = 0 of the lane that follows in the channel (DPP row_shl:1, lane i <- lane i + 1) or, behind the
-// channel's last lane, the first lane's j = 0 of piece m + 1 (row_shr:7, lane i <- lane i - 7; next0 = v[0] of the block that follows).  All 64 lanes run it.
-// LAST: no block follows -- the seam word of piece 3 is word 383, which nothing reads.
-template <bool LAST>
-__device__ __forceinline__ void hilbert_hist_store16(float *dst, const float *v, float next0, bool seam) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    float w = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[4 * m]), 0x101, 0xF, 0xF, true));
-    float p1 = v[4 * m + 1], p2 = v[4 * m + 2], p3 = v[4 * m + 3];
-    asm volatile("" : "+v"(p1), "+v"(p2), "+v"(p3));   // (the piece is put together HERE: a register quadruple that starts at j = 1 from the load on costs a fifth register per piece while the block waits)
-    if (!(LAST && m == 3)) {
-      const float s = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m < 3 ? v[4 * m + 4] : next0), 0x117, 0xF, 0xF, true));
-      w = seam ? s : w;
-    }
-    *reinterpret_cast<float4 *>(dst + 32 * m) = make_float4(p1, p2, p3, w);
-  }
 }
 // Second wave of a role-2 workgroup of the streaming pipeline: nothing but the other half of the FIR, in step with the first
 // wave's three barriers per block (history staged | all reads done | both halves in W1).
@@ -1015,7 +932,6 @@ __device__ __forceinline__ void als_compute(float *L, bool als_en, bool adaptive
         for (int j = 0; j < 16; ++j) L[OUT + k0 + j] = yo[j];
       }
     }
-#ifndef ASDR_ALS_TAPS_IN_LDS
     if (als_m_default) {
       // The reference's default length (55 taps, adaptive) in the whole wave: THE TAPS LIVE IN REGISTERS for the block, each held
       // once.  A channel's eight lanes are two quads: the low one works on the even taps, the high one on the odd taps, and lane
@@ -1074,18 +990,13 @@ __device__ __forceinline__ void als_compute(float *L, bool als_en, bool adaptive
           if (g == 6) p[3] = (h == 0) ? p[3] : 0.0f;   // tap 55 does not exist (the running sum starts at +0.0: adding +0.0 leaves it)
 #pragma unroll
           for (int t = 0; t < 4; ++t) { y += p[t]; y += dpp_row_shl4(p[t]); }
-#ifdef ASDR_ALS_GROUP_BARRIER   /* (round 3, first form: kept the scheduler from forming all 28 products up front -- and kept 20 of the 28 DPP operands from folding) */
-          __builtin_amdgcn_sched_barrier(0);
-#endif
         }
-#ifndef ASDR_ALS_SUMS_SINKABLE
         // The sum is formed by ALL lanes, here: left to itself the compiler sinks the 56 additions into the `mine` branch below (only
         // there is y used), where the partner quad is inactive -- so the 28 `row_shl:4` operands cannot fold into the additions and
         // become 28 v_mov_b32_dpp per tap set in front of the branch.  With the sums here and no scheduling barrier between the tap
         // groups every one of them is a v_add_f32_dpp, the products rotate through four registers (mul | add | add_dpp per tap pair)
         // and a tap set is 144 instructions instead of 151 (21 of them one-cycle s_nop for the DPP read-after-write hazard): C4 -3.8 %.
         asm volatile("" : "+v"(y));
-#endif
         // The error of the updating sample (n = nu: lane tq = 3 of the low quad, tq = 0 in the first tap set) goes to the channel's
         // eight lanes through two DPP moves -- its quad, then the partner quad (row_shr:4 into banks 1 and 3 only) -- instead of an
         // LDS word between two wave syncs: the tap set's dependent path error -> tap update -> next products stays in registers.
@@ -1106,7 +1017,6 @@ __device__ __forceinline__ void als_compute(float *L, bool als_en, bool adaptive
         }
       };
       epoch(std::true_type{}, std::integral_constant<int, -1>{}, -1, nullptr, nullptr, nullptr);
-#if ASDR_ALS_WINDOW
       // OUT may overlay the history (the stand-alone kernel: output n at buffer index 128 + n - 65): a group's reads, made in front of its
       // first tap set, reach back to index i0 - D - h - 54 >= i0 - 64 - ... -- never below what the PREVIOUS groups' outputs (n <= base0 - 1,
       // index <= i0 - 66) have overwritten -- and forward to samples of the current block, which nothing writes.
@@ -1127,16 +1037,11 @@ __device__ __forceinline__ void als_compute(float *L, bool als_en, bool adaptive
         epoch(std::false_type{}, std::integral_constant<int, 2>{}, ep0 + 2, E, F, XI);
         epoch(std::false_type{}, std::integral_constant<int, 3>{}, ep0 + 3, E, F, XI);
       }
-#else
-#pragma unroll 1
-      for (int ep = 0; ep < 32; ++ep) epoch(std::false_type{}, std::integral_constant<int, -1>{}, ep, nullptr, nullptr, nullptr);
-#endif
       // the taps back to their LDS rows
 #pragma unroll
       for (int g = 0; g < 7; ++g) L[AW + WH * h + 4 * g + tq] = wr[g];
       WAVE_SYNC();
     } else
-#endif
     if (__any(als_en && adaptive)) {
       // taps change only after samples n = 0, 4, 8, ...; samples sharing one tap set run on lanes s8 = 0..3
 #pragma unroll 1
@@ -1222,15 +1127,13 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   constexpr bool DO1 = (ROLE == 0 || ROLE == 1 || PRE_ROLE || ROLE == 6 || ROLE == 7), DO2 = (ROLE == 0 || ROLE == 2 || POST_ROLE || ROLE == 6 || ROLE == 7),
                  DO3 = (ROLE == 0 || ROLE == 3 || POST_ROLE || ROLE == 6 || ROLE == 7);
   constexpr bool TO_ALS = (ROLE == 6 || ROLE == 7 || ROLE == 10);
-#ifndef ASDR_ALS_FULL_OPT
-#define ASDR_ALS_FULL_OPT 2
-#endif
   // The ALS instantiations gave up two of the plain kernel's orderings for registers (IF rows consumed before the ring prefetches; the
   // merged average + phase loop).  Their LOOP-FREE compact-row forms have the registers for both (round 5: asdr_update_kernel_als_small_one
-  // 160 VGPRs, no spills; C4 share -1.3 %, on the lanes -2.5 %); the looped forms keep the old orderings.  Level 0 / 1: measurements.
-  constexpr bool ALS_LOOPFREE = (ASDR_ONEBLK_ALS != 0) && (ONEBLK_ || (ROLE >= 4 && !LOOPED_ROLE && ASDR_ONEBLK_ROLES));
-  constexpr bool ALS_FULL_OPT = (ASDR_ALS_FULL_OPT >= 1) && ASDR_COMPACT_ROWS(STRIDE) && ALS_LOOPFREE,
-                 ALS_FULL_OPT2 = (ASDR_ALS_FULL_OPT >= 2) && ASDR_COMPACT_ROWS(STRIDE) && ALS_LOOPFREE;
+  // 160 VGPRs, no spills; C4 share -1.3 %, on the lanes -2.5 %); the looped forms keep the old orderings.
+  // (The ALS instantiations' loop-free builds failed the ALS parity tests until the guard of the tap store-back was taken from an opaque copy
+  // of the flag word: a compiler issue, see there.)
+  constexpr bool ONEBLK = ONEBLK_ || (ROLE >= 4 && !LOOPED_ROLE);   // (the SAM pre / post and the two-launch ALS pre roles always run one block per launch)
+  constexpr bool ALS_FULL_OPT = ASDR_COMPACT_ROWS(STRIDE) && ONEBLK;
   constexpr bool STREAM = (ROLE >= 1 && ROLE <= 3);
   // biquad pipelines with packed products (biquad_pipe<true>), by instantiation: bit 0 = the ALS kinds, 1 = the plain kinds, 2 = the SAM roles, 3 = the block pipeline
   constexpr bool PIPE_PK = ((ASDR_PIPE_PK_MASK & 1) && HAS_ALS) || ((ASDR_PIPE_PK_MASK & 2) && !HAS_ALS && !HAS_SAM && ROLE == 0) ||
@@ -1246,9 +1149,6 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   constexpr bool MW = (WAVES > 1) && !HAS_SAM && (ROLE == 0);
   constexpr int MW_SHARE = MW ? ASDR_MW_SHARE : 0;   // bit 0: audio cascades, bit 1: blanker / phase chains, bit 2: AGC chain (measurements: any subset)
   const int wave = (WAVES > 1) ? (int)(threadIdx.x >> 6) : 0;
-#ifndef ASDR_MW_ROT
-#define ASDR_MW_ROT 0
-#endif
   // The LOGICAL workgroup index: which channels / schedule slots this workgroup works on.  A launch with a.wg_reverse walks the sub-range from
   // its end (the plain kind's one-block instantiations only: everywhere else the field is not read), so that consecutive launches can
   // alternate and the state rows written last are read first (off by default: measured, no gain -- profiles/README.md).  Placement (XCD = workgroup mod 8, the SIMD patterns) and with it the duty
@@ -1257,29 +1157,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   constexpr bool ORDERED = (ROLE == 0) && !HAS_ALS && !HAS_SAM && UNIFORM && ONEBLK_ && (STRIDE == ASDR_STRIDE);
   constexpr bool ST_PLAIN = ORDERED && (ASDR_STATE_POLICY >= 1), LD_PLAIN = ORDERED && (ASDR_STATE_POLICY >= 2);   // (state rows: see ASDR_STATE_POLICY; the same three instantiations, independent of a.wg_reverse)
   const int wg_l = (ORDERED && a.wg_reverse != 0u) ? (int)(gridDim.x - 1u - blockIdx.x) : (int)blockIdx.x;
-  const uint32_t mw_b = blockIdx.x;
-  const uint32_t mw_rot = (ASDR_MW_ROT == 0) ? mw_b : (ASDR_MW_ROT == 1) ? (mw_b >> 3) : (ASDR_MW_ROT == 2) ? ((mw_b >> 3) + (mw_b >> 8)) :
-                          (ASDR_MW_ROT == 3) ? ((mw_b * 0x9E3779B1u) >> 30) : (ASDR_MW_ROT == 4) ? ((mw_b >> 3) % 3u) : (mw_b >> 5);
-  const int mw_rel = MW ? (int)(((uint32_t)wave - mw_rot) & (uint32_t)(WAVES - 1)) : 0;
+  const int mw_rel = MW ? (int)(((uint32_t)wave - blockIdx.x) & (uint32_t)(WAVES - 1)) : 0;
   float *const mwx = lds_wg + WAVES * 8 * STRIDE;   // MW: [8 * WAVES][MWX] floats of hand-off scratch behind the rows
-#ifndef ASDR_MW_STRAGGLER_PRIO
-#define ASDR_MW_STRAGGLER_PRIO 0   /* experiment (round 6): at three points between the chain duty and the audio duty a wave that finds itself the LAST of its workgroup raises its priority */
-#endif
-  // (progress words of the four waves behind the hand-off scratch and the sine table)
-  int *const mw_prog = reinterpret_cast<int *>(lds_wg + WAVES * 8 * STRIDE + 8 * WAVES * 16 + 260);
-  int *const mw_flags = mw_prog + 4;   // [0]: the AGC duty took the lean chain (this block); [1]: chunks whose |x| and beta |x| are in the rows, [2], [3]: chunks the audio duty waves have finished (the AGC duty beside the audio duty)
-  constexpr bool PIPE_AGC = MW && WAVES == 4 && (MW_SHARE & 7) == 7 && (ASDR_MW_AGC_PIPELINED != 0) && (ASDR_AGC_LEAN != 0) && (ASDR_MW_OWN_STORES != 0) && ABL_ON(ABL_AGC) && ABL_ON(ABL_AF) && ABL_ON(ABL_NB);
-  if constexpr (PIPE_AGC) { if (threadIdx.x < 3) mw_flags[1 + threadIdx.x] = 0; }   // (five barriers in front of the first reader)
-  if constexpr (MW && ASDR_MW_STRAGGLER_PRIO != 0) { if ((threadIdx.x & 63) == 0) mw_prog[wave] = 0; }
-  auto mw_straggler = [&](int point) {
-    if constexpr (MW && ASDR_MW_STRAGGLER_PRIO != 0) {
-      if ((threadIdx.x & 63) == 0) mw_prog[wave] = point;
-      const int4 pr = *reinterpret_cast<const int4 *>(mw_prog);
-      const int behind = (pr.x < point) + (pr.y < point) + (pr.z < point) + (pr.w < point);   // siblings that have not reached this point yet
-      const bool last = __builtin_amdgcn_readfirstlane(behind) == 0;
-      if (last) __builtin_amdgcn_s_setprio(ASDR_MW_STRAGGLER_PRIO); else __builtin_amdgcn_s_setprio(0);
-    }
-  };
+  // (flag words behind the hand-off scratch; the 264 words in between are not used)
+  int *const mw_flags = reinterpret_cast<int *>(lds_wg + WAVES * 8 * STRIDE + 8 * WAVES * 16 + 260) + 4;   // [0]: the AGC duty took the lean chain (this block)
   constexpr int MWX = 16;   // per channel: 0 blanker average in / out, 1 mixer phase in / "a phase sequence was computed" out, 2 increment, 3 flags, 4 phase after the block,
                             // 5 AGC quiet flag, 6 AM level, 7 gain after the block, 8 envelope in / out, 9 hang counter in / out, 10 gain in, 11..14 attack / release alpha, beta, 15 hang count
   // schedule slot / channel index of the workgroup's channel q (0 .. 8 * WAVES - 1), for the lanes that work on other waves' channels
@@ -1288,24 +1169,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   const int wave_g = STREAM ? wg_l % a.stream_waves : wg_l * WAVES + wave;
   float *const lds = lds_wg + wave * 8 * STRIDE;            // this wave's 8 channel rows
   const int lane = threadIdx.x & 63, c8 = lane >> 3, s8_ = lane & 7;
-#ifndef ASDR_MW_SINE_LDS
-#define ASDR_MW_SINE_LDS 0   /* 1: filled at the top of every workgroup (measured: divergent mixer phases -1.3 %, steady state +0.3 %: the fill and its barrier);
-                                  2: filled between the blanker chain's two barriers, by the three waves that park there, and only in a workgroup one of whose waves
-                                  carries different mixer phases (each wave says so in a word of its own in front of the first barrier; the wave-uniform lookups keep
-                                  the constant table): divergent phases -0.4 %, steady state +0.3 %.  Off */
-#endif
-  // Round 6: the four-wave form keeps a copy of the sine table in LDS as well (1 KB per workgroup of 32 channels: 3 workgroups per CU still fit) --
-  // waves whose channels carry DIFFERENT mixer phases (receivers tuned at different times: 2 x 16 lookups per lane) read it through the LDS
-  // instead of gathering from the constant table through L1; one barrier at the top of the kernel.
-  constexpr bool MW_SINE = MW && (ASDR_MW_SINE_LDS != 0);
-  constexpr bool MW_SINE_LAZY = MW_SINE && (ASDR_MW_SINE_LDS == 2) && (MW_SHARE & 2) != 0 && WAVES == 4;   // (the table exists where a wave needs it: the per-channel lookups; the wave-uniform ones read the constant table)
-  constexpr bool SINE_LDS = HAS_SAM || (MW_SINE && !MW_SINE_LAZY);   // the wave-uniform lookups (two per lane) and the oscillator cache's writer
-  constexpr bool SINE_LDS_PC = HAS_SAM || MW_SINE;                   // the per-channel lookups (16 per lane)
-  float *const sine_tab = HAS_SAM ? lds_wg + WAVES * 8 * STRIDE : (MW_SINE ? lds_wg + WAVES * 8 * STRIDE + 8 * WAVES * 16 : nullptr);
-  float *const sine = SINE_LDS ? sine_tab : nullptr;
-  int *const mw_sflag = reinterpret_cast<int *>(lds_wg + WAVES * 8 * STRIDE + 8 * WAVES * 16 + 260) + 8;   // MW_SINE_LAZY: per wave "my channels carry different mixer phases"
-  if (HAS_SAM) for (int i = lane; i < ASDR_SINE_TABLE_LEN; i += 64) sine_tab[i] = c_sine[i];
-  if (MW_SINE && !MW_SINE_LAZY) { for (int i = (int)threadIdx.x; i < ASDR_SINE_TABLE_LEN; i += 64 * WAVES) sine_tab[i] = c_sine[i]; __syncthreads(); }
+  // The SAM instantiation keeps a copy of the sine table in LDS behind the rows (the PLL's per-sample dependent lookups want the LDS latency); every other
+  // form reads the __constant__ table through L1.
+  float *const sine = HAS_SAM ? lds_wg + WAVES * 8 * STRIDE : nullptr;
+  if (HAS_SAM) for (int i = lane; i < ASDR_SINE_TABLE_LEN; i += 64) sine[i] = c_sine[i];
 
   int4 slot = make_int4(a.n_channels, 0, 0, 0);
   const bool mw_pad = MW && (wave_g * 8 >= a.n_sched);   // a wave behind the sub-range's last one: works on the dummy channel, stores nothing outside it
@@ -1327,18 +1194,9 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   const bool is_ssb = DO2 && ((mode == ASDR_USBmode) || (mode == ASDR_LSBmode) || (mode == ASDR_CW_USBmode) ||
                               (mode == ASDR_CW_LSBmode) || (mode == ASDR_WSPRmode));
   // the host launches SAM channels with the SAM (or ALS) instantiation only: the plain one carries no PLL code
-#ifndef ASDR_MW_NO_AM
-#define ASDR_MW_NO_AM 0   /* experiment: the four-wave form compiled without the AM paths (code size) */
-#endif
-  const bool is_am = !C16 && !(MW && ASDR_MW_NO_AM) && (mode == ASDR_AMmode), is_sam = (HAS_SAM || ROLE >= 4) && (mode == ASDR_SAMmode);
+  const bool is_am = !C16 && (mode == ASDR_AMmode), is_sam = (HAS_SAM || ROLE >= 4) && (mode == ASDR_SAMmode);
   const bool sub_q = (mode == ASDR_USBmode) || (mode == ASDR_CW_USBmode) || (mode == ASDR_WSPRmode);
   const bool nb_en = DO1 && (pflags & ASDR_F_NB_EN), af_en = DO3 && (pflags & ASDR_F_AF_EN), agc_en = DO3 && (pflags & ASDR_F_AGC_EN);
-  if constexpr (MW_SINE_LAZY) {
-    if (!(ABL_ON(ABL_NB) && __any(nb_en))) {   // no blanker in this launch (launch-uniform in the four-wave form), hence no chain barriers: the table is filled here
-      for (int i = (int)threadIdx.x; i < ASDR_SINE_TABLE_LEN; i += 64 * WAVES) sine_tab[i] = c_sine[i];
-      __syncthreads();
-    }
-  }
   const bool als_en = HAS_ALS && (pflags & ASDR_F_ALS_EN);
   const bool muted = pflags & ASDR_F_MUTED;
   const float two_pi = K.two_pi_f;
@@ -1350,32 +1208,19 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   // stores still happen: HBM holds the state after the call): mixer phase, frequency shift, Hilbert ring parity
   float carry_phase = 0.0f, carry_fsh = 0.0f;
   uint32_t carry_hs = 0u;
-#ifndef ASDR_STREAM_PREFETCH_IN
-#define ASDR_STREAM_PREFETCH_IN 1   /* the block pipeline's role 1 requests the NEXT block's input rows at the top of a block (its one HBM round trip per block otherwise sits in front of the scale) */
-#endif
   int4 pf_in[4] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};   // ROLE 1: the next block's input pieces (I, I + 64, Q, Q + 64)
-#ifndef ASDR_STREAM_R2_ONE_TRIP
-#define ASDR_STREAM_R2_ONE_TRIP 1   /* role 2 asks for everything another workgroup wrote for this block -- oscillator key, its 2 x 128 pairs, the IF rows -- in ONE round trip */
-#endif
-#ifndef ASDR_STREAM_R2_PREFETCH
-#define ASDR_STREAM_R2_PREFETCH 1   /* role 2 of the three-helper form asks for block k + 1's oscillator pairs and IF rows in front of block k's FIR, when both producers are known to be that far */
-#endif
-  constexpr bool R2_ONE_TRIP = (ROLE == 2) && (FIR_HELPERS == 3) && (ASDR_STREAM_R2_ONE_TRIP != 0);   // (68 registers in flight: the three-helper form has them -- one workgroup per compute unit --, the two-wave form spills with it)
-  constexpr bool R2_PREFETCH = R2_ONE_TRIP && (ASDR_STREAM_R2_PREFETCH != 0);
+  // Role 2 of the three-helper form asks for everything another workgroup wrote for a block -- oscillator key, its 2 x 128 pairs, the IF rows -- in ONE
+  // round trip, and for block k + 1's in front of block k's FIR when both producers are known to be that far.  (68 registers in flight: the three-helper
+  // form has them -- one workgroup per compute unit --, the two-wave form spills with it)
+  constexpr bool R2_ONE_TRIP = (ROLE == 2) && (FIR_HELPERS == 3);
   v4f r2n_key = (v4f){0.f, 0.f, 0.f, 0.f}, r2n_c4[4], r2n_s4[4], r2n_vi[4], r2n_vq[4];
   bool r2_pref = false;
   uint32_t r2_look_in = 0u, r2_look_lo = 0u;
-#ifndef ASDR_STREAM_R1_CARRY
-#define ASDR_STREAM_R1_CARRY 0   /* role 1 keeping its IF cascade's state and coefficients (and the input gains) in registers from block to block: measured +1.5 % (C5 share 4.025 vs 3.96 ms), off */
-#endif
   float4 r1_if_s4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float r1_if_cf[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, r1_gain_i = 0.f, r1_gain_q = 0.f;
   uint32_t *const my_prog = STREAM ? a.stream_prog + (ROLE - 1) * a.stream_waves + wave_g : nullptr;
 
-  // (The ALS instantiations' loop-free builds failed the ALS parity tests until the guard of the tap store-back was taken from an opaque copy
-  // of the flag word: a compiler issue, see there.)
-  constexpr bool ONEBLK = (!HAS_ALS || ASDR_ONEBLK_ALS) && (ONEBLK_ || (ROLE >= 4 && !LOOPED_ROLE && ASDR_ONEBLK_ROLES));
-  constexpr bool UNIT_OK = (ASDR_UNIT_SCALE != 0) && ((ONEBLK && ROLE == 0) || ROLE == 1);   // (round 6: the block pipeline's role 1 too -- its scale was 1.3 k cycles of binary64 per block on a wave that is alone on its SIMD)
+  constexpr bool UNIT_OK = (ONEBLK && ROLE == 0) || ROLE == 1;   // (round 6: the block pipeline's role 1 too -- its scale was 1.3 k cycles of binary64 per block on a wave that is alone on its SIMD)
   // C16 (round 5, asdr_update_kernel_c16): the same chain on 320-float rows and <= 128 VGPRs -- 10,240 B of LDS per wave, FOUR waves per
   // SIMD = 16 per CU.  Direct one-block launches of ONE SSB-class settings group without stage taps (the launcher's choice: mode and
   // flags are launch-uniform scalars, the AM / SAM / unknown-mode paths are compiled out).  What fits 320 floats and 128 registers:
@@ -1496,7 +1341,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     v4f r2_c4[4], r2_s4[4], r2_vi[4], r2_vq[4];
     if (ROLE == 2) {
       v4f key;
-      if (R2_PREFETCH && r2_pref) {   // asked for during the previous block (both producers had published this one by then)
+      if (R2_ONE_TRIP && r2_pref) {   // asked for during the previous block (both producers had published this one by then)
         key = r2n_key;
 #pragma unroll
         for (int m = 0; m < 4; ++m) { r2_c4[m] = r2n_c4[m]; r2_s4[m] = r2n_s4[m]; r2_vi[m] = r2n_vi[m]; r2_vq[m] = r2n_vq[m]; }
@@ -1547,14 +1392,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     if (ROLE == 1 && ASDR_STREAM_R1_CARRY && blk > 0) { gain_i = r1_gain_i; gain_q = r1_gain_q; }
     else { gain_i = pv(P.in_gain_i); gain_q = pv(P.in_gain_q); if (ROLE == 1) { r1_gain_i = gain_i; r1_gain_q = gain_q; } }
     float g_oi = gain_i, g_oq = gain_q, g_mi = 0.0f, g_mq = 0.0f, nb_avg0 = 0.0f;
-    uint32_t agc_hc_early = 0u, agc_hang_early = 0u;
-    bool agc_piped = false;   // (the four-wave form: the AGC duty runs the lean chain beside the audio duty: see the audio filter)
     if (nb_wave && nb_en) {
       // the gains first: they are converted right away, and a wait for the oldest loads leaves all the others in flight
       g_oi = S->nb_gain[ns][0]; g_oq = S->nb_gain[ns][1]; g_mi = S->nb_gain[ns_mid][0]; g_mq = S->nb_gain[ns_mid][1];
       nb_avg0 = S->nb_avg;
-      if constexpr (PIPE_AGC) { agc_hc_early = S->agc_hang_counter; agc_hang_early = P.agc_hang_count; }   // (for the decision "AGC chain beside the audio duty", published with the blanker chain's inputs)
-   // (for the decision "AGC chain beside the audio duty", published with the blanker chain's inputs)
       const int4 *old4 = reinterpret_cast<const int4 *>(hist + ns * 256 + kA), *mid4 = reinterpret_cast<const int4 *>(hist + ns_mid * 256 + kA);
 #if ASDR_NT_LOADS >= 2
       rmi[0].v = mid4[0]; rmi[1].v = mid4[8]; rmq[0].v = mid4[16]; rmq[1].v = mid4[24];   // (the middle block comes back once more: temporal)
@@ -1577,7 +1418,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     if (DO1 && valid) {
       const int4 *pi = reinterpret_cast<const int4 *>(a.in_i + io);
       const int4 *pq = reinterpret_cast<const int4 *>(a.in_q + io);
-      if constexpr (ROLE == 1 && ASDR_STREAM_PREFETCH_IN != 0) {
+      if constexpr (ROLE == 1) {
         // the pipeline's role 1: this block's rows were requested a block ago; the next block's are requested now (a role wave is alone on its
         // SIMD: nothing hides the round trip for it)
         if (blk == 0) { ri[0].v = load_int4_nt(pi); ri[1].v = load_int4_nt(pi + 8); rq[0].v = load_int4_nt(pq); rq[1].v = load_int4_nt(pq + 8); }
@@ -1723,11 +1564,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       }   // !C16
       if (nb_en && !C16) {   // newest block -> third ring slot, with its gains (blanker-off channels pass their own input: see above)
         int4 *ni = reinterpret_cast<int4 *>(hist + ns_new * 256 + kA);
-#ifndef ASDR_TEMPORAL_RINGS
         store_int4_state<ST_PLAIN>(ni, ri[0].v); store_int4_state<ST_PLAIN>(ni + 8, ri[1].v); store_int4_state<ST_PLAIN>(ni + 16, rq[0].v); store_int4_state<ST_PLAIN>(ni + 24, rq[1].v);
-#else
-        ni[0] = ri[0].v; ni[8] = ri[1].v; ni[16] = rq[0].v; ni[24] = rq[1].v;
-#endif
         if (lead) { S->nb_gain[ns_new][0] = gain_i; S->nb_gain[ns_new][1] = gain_q; }
       }
       if (tap_on) {
@@ -1737,10 +1574,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       }
       WAVE_SYNC();
       TL(2);
-#ifndef ASDR_MW_IF_PRE
-#define ASDR_MW_IF_PRE 1
-#endif
-      if (DO1 && ABL_ON(ABL_IF) && (WAVES == 1 || (MW && ASDR_MW_IF_PRE)) && !C16) {   // the IF pipeline's state and coefficient row are requested here: they arrive during the sequential pass
+      if (DO1 && ABL_ON(ABL_IF) && (WAVES == 1 || MW) && !C16) {   // the IF pipeline's state and coefficient row are requested here: they arrive during the sequential pass
                                             // (not in the multi-wave SAM instantiation: no registers to spare)
         if_s4 = *reinterpret_cast<const float4 *>(&Sp->if_state[pl_iq][4 * pl_st]);
         const float *cf = &c_bq_pool[Ppl->if_table][5 * pl_st];
@@ -1754,20 +1588,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       // The two recurrences of one channel on ONE lane (`Lc` = the channel's rows, avg0 / phase0 / inc = its carried average, mixer phase
       // and increment, Sc = its state row, chain_phase = the phase sequence is wanted (wave-uniform: a lane that does not need it computes
       // and drops it), en = the blanker is on).  Returns the phase after the block.
-#ifndef ASDR_CHAIN_CONSTS_IN_VGPRS
-#define ASDR_CHAIN_CONSTS_IN_VGPRS 0
-#endif
-#ifndef ASDR_MW_OWN_STORES
-#define ASDR_MW_OWN_STORES 1   /* the four-wave form: a chain's results go back to HBM from the channel's OWN wave (its lead lanes: stores beside its other state), not from the duty wave's 32 lanes */
-#endif
-      float nb_avg_end = 0.0f;   // (MW with ASDR_MW_OWN_STORES: the duty wave's lane leaves the average here instead of storing it)
+      float nb_avg_end = 0.0f;   // (the four-wave form: the duty wave's lane leaves the average here; the channel's own wave stores it)
       auto nb_chain = [&](float *Lc, ChanSmall *Sc, float avg0, float phase0, float inc, bool chain_phase, bool want_phase, bool en, bool ssb) -> float {
         float avg = avg0, phase = phase0;
-        // The chain's constants as VGPR operands (round 6): as scalar operands they are in every other instruction of the loops below, and a stream
-        // that dense in scalar-file reads does not share its SIMD -- each resident wave then issues once per 8 cycles instead of 4.5
-        // (tools/ubench/issue_rate.hip: chain2 against chain4x_vgpr_constants).  Not in the 16-waves-per-CU form (no register to spare).
-        float nb_alpha_v = K.nb_alpha, two_pi_v = two_pi;
-        if constexpr (!C16 && ONEBLK && ASDR_CHAIN_CONSTS_IN_VGPRS) asm("" : "+v"(nb_alpha_v), "+v"(two_pi_v));   // (nor in the looped forms: they spill with it)
+        float nb_alpha_v = K.nb_alpha, two_pi_v = two_pi;   // (the loops' constants, named here once)
         // `if (t > twoPI) t -= twoPI; else if (t < 0) t += twoPI;` (.h:514-517) with one test per sample: the phase stays in
         // [0, twoPI], so for inc >= 0 only the first branch can fire and for inc < 0 only the second.  The test is written as
         // (t with its sign flipped for inc < 0) > (twoPI or 0), and t - twoPI == t + (-twoPI) exactly.
@@ -1814,7 +1638,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
         // Both chains in ONE basic block (the scheduler interleaves them).  Every mode's shift is downwards (inc < 0): then the
         // wrap `t < 0 ? t + twoPI : t` is a sign-mask select (v_ashrrev + v_bfi, no compare -> VCC -> select hazard): the phase
         // chain is add, shift, select.  (t = -0.0 cannot occur: the phase is never -0.0 and x + y = -0.0 needs both -0.0.)
-        if (!(HAS_ALS && !ALS_FULL_OPT2) && __all(inc < 0.0f)) {   // (the ALS instantiations take the compact loop below: this one costs them spills)
+        if (!(HAS_ALS && !ALS_FULL_OPT) && __all(inc < 0.0f)) {   // (the ALS instantiations take the compact loop below: this one costs them spills)
 #pragma unroll 1
           for (int c = 0; c < 16; c += 2) {
             float av[8], bn[8], pv[8];
@@ -1828,12 +1652,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
                 pv[u] = phase;
                 const float t = phase + inc, tw = t + two_pi_v;
                 const uint32_t tb = __float_as_uint(t), m = (uint32_t)((int32_t)tb >> 31);
-#ifdef ASDR_PHASE_SELECT_C
-                phase = __uint_as_float((__float_as_uint(tw) & m) | (tb & ~m));
-#else
                 // (m & tw) | (~m & t) as ONE v_bfi_b32: from the C expression the compiler builds v_max_i32(0, t) + v_and_or_b32
                 asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(phase) : "v"(m), "v"(tw), "v"(t));
-#endif
               }
               if constexpr (C16) store4e(Lc + PH + 4 * (c + half), pv); else store8(Lc + PH + 8 * (c + half), pv);
               store8(Lc + NB_B + 2 + 8 * (c + half), av);
@@ -1871,7 +1691,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           }
         }
         }   // !C16
-        constexpr bool OWN_STORES = MW && ((MW_SHARE & 2) != 0) && (ASDR_MW_OWN_STORES != 0);
+        constexpr bool OWN_STORES = MW && ((MW_SHARE & 2) != 0);   // the four-wave form: a chain's results go back to HBM from the channel's OWN wave (its lead lanes: stores beside its other state), not from the duty wave's 32 lanes
         if (OWN_STORES) nb_avg_end = avg;
         if (!OWN_STORES && en) Sc->nb_avg = avg;
         if (!OWN_STORES && want_phase && c_tail != 0) {
@@ -1887,30 +1707,9 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       if constexpr ((MW_SHARE & 2) != 0) {
         // every channel's lead lane publishes its chain inputs; the duty wave (rel 0) runs the chains of all 8 * WAVES channels, one per lane
         if (lead) *reinterpret_cast<float4 *>(mwx + MWX * (wave * 8 + c8)) = make_float4(nb_avg0, mphase, minc, __int_as_float((chain_phase_own ? 1 : 0) | ((mix_early && !lo_hit) ? 2 : 0)));
-        if constexpr (PIPE_AGC) {
-          // bit 0: this channel's AGC is off or in the lean regime (no hang counter can run out inside the block); bit 1: it attacked in the PREVIOUS block
-          // (an attack at sample u leaves the counter at hang - (127 - u)).  See the audio filter: the AGC chain beside the audio duty.
-          if (lead) {
-            const bool capable = af_en && nb_en && (!agc_en || (!is_am && agc_hc_early >= 128u && agc_hang_early >= 128u));
-            const bool recent = agc_en && (agc_hang_early - agc_hc_early <= 127u);
-            mwx[MWX * (wave * 8 + c8) + 7] = __int_as_float((capable ? 1 : 0) | (recent ? 2 : 0));
-          }
-        }
-        if constexpr (MW_SINE_LAZY) {
-          const uint32_t p1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(mphase)), i1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(minc));
-          const bool differ = mix_early && !__all(__float_as_uint(mphase) == p1 && __float_as_uint(minc) == i1);
-          if (lane_i == 0) mw_sflag[wave] = differ ? 1 : 0;
-        }
         TL(17);
         __syncthreads();
         TL(18);
-        if constexpr (MW_SINE_LAZY) {
-          const int4 sf = *reinterpret_cast<const int4 *>(mw_sflag);
-          if (__builtin_amdgcn_readfirstlane(sf.x | sf.y | sf.z | sf.w) != 0 && mw_rel != 0) {   // the three waves that would park now fill the table (visible behind the second barrier)
-#pragma unroll 1
-            for (int i = (mw_rel - 1) * 64 + lane_i; i < ASDR_SINE_TABLE_LEN; i += 192) { sine_tab[i] = c_sine[i]; asm volatile("" ::: "memory"); }   // (one entry in flight: this is the kernel's register peak)
-          }
-        }
         if (ASDR_MW_PRIO && mw_rel == 0) __builtin_amdgcn_s_setprio(ASDR_MW_PRIO);
         if (mw_rel == 0 && lane_i < 8 * WAVES) {
           const int q = lane_i;
@@ -1919,30 +1718,20 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           const bool any_phase = __any((fl & 1) != 0);
           const float pe = nb_chain(lds_wg + q * STRIDE, row_ptr(a.small, (uint32_t)mw_channel(q) * (uint32_t)sizeof(ChanSmall)), in4.x, in4.y, in4.z, any_phase, (fl & 2) != 0, nb_en, is_ssb);
           mwx[MWX * q + 4] = pe;
-          if (ASDR_MW_OWN_STORES) { mwx[MWX * q] = nb_avg_end; mwx[MWX * q + 1] = __int_as_float(any_phase ? 1 : 0); }
+          mwx[MWX * q] = nb_avg_end; mwx[MWX * q + 1] = __int_as_float(any_phase ? 1 : 0);
         }
-#ifndef ASDR_MW_PRIO_REL0_TAIL
-#define ASDR_MW_PRIO_REL0_TAIL 0   /* experiments: the priority the blanker-chain duty wave keeps up to the audio barrier (the timeline's straggler there) */
-#endif
-        if (ASDR_MW_PRIO && mw_rel == 0) __builtin_amdgcn_s_setprio(ASDR_MW_PRIO_REL0_TAIL);
+        if (ASDR_MW_PRIO && mw_rel == 0) __builtin_amdgcn_s_setprio(0);
         TL(19);
         __syncthreads();
         TL(20);
-        if constexpr (PIPE_AGC) {   // (every wave forms the decision from the 32 channels' words; nothing waits for this read before the audio barrier)
-          const int fl = __float_as_int(mwx[MWX * (lane_i & (8 * WAVES - 1)) + 7]);
-          agc_piped = __all((fl & 1) != 0) && __any((fl & 2) != 0);
-        }
         if (lead) {
           mphase_end = mwx[MWX * (wave * 8 + c8) + 4];
-          if (ASDR_MW_OWN_STORES) {   // the chain's results back to the channel's state row, from its own wave
-            if (nb_en) S->nb_avg = mwx[MWX * (wave * 8 + c8)];
-            if (mix_early && !lo_hit && __float_as_int(mwx[MWX * (wave * 8 + c8) + 1]) != 0) { if (is_ssb) S->phase_ssb = mphase_end; else S->phase_am = mphase_end; }
-          }
+          // the chain's results back to the channel's state row, from its own wave
+          if (nb_en) S->nb_avg = mwx[MWX * (wave * 8 + c8)];
+          if (mix_early && !lo_hit && __float_as_int(mwx[MWX * (wave * 8 + c8) + 1]) != 0) { if (is_ssb) S->phase_ssb = mphase_end; else S->phase_am = mphase_end; }
         }
       } else {
-        CHAIN_PRIO_ON();
         if (lead) mphase_end = nb_chain(L, S, nb_avg0, mphase, minc, chain_phase_own, mix_early && !lo_hit, nb_en, is_ssb);
-        CHAIN_PRIO_OFF();
       }
       ph_ready = mix_early && !lo_hit;
       WAVE_SYNC();
@@ -2132,7 +1921,6 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     }
     WAVE_SYNC();
     TL(4);
-    mw_straggler(1);
     if (DO1) { TAP_ROW(ASDR_TAP_NB_I, W0); TAP_ROW(ASDR_TAP_NB_Q, W1); }
 
     // The IF pipeline's state and coefficients must be IN registers before the ring prefetches below are issued: memory waits
@@ -2200,7 +1988,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     }
     // ---- IF band-pass, AudioSDR.cpp:77-78: 2 x 4-stage cascade, 64 lanes = 8 ch x {I,Q} x 4 stages -------
     if (ROLE == 1 && sig_pending) { stream_signal(my_prog, sig_pending, lane); sig_pending = 0u; }   // the previous block's rows have left by now (they were stored a prologue and a scale ago)
-    if constexpr (ROLE == 1 && ASDR_STREAM_PREFETCH_IN != 0) {
+    if constexpr (ROLE == 1) {
       if (DO1 && valid && blk + 1 < a.n_blocks) {   // the next block's input rows: they arrive during the pipeline
         const int4 *pi = reinterpret_cast<const int4 *>(a.in_i + io) + ASDR_N / 8, *pq = reinterpret_cast<const int4 *>(a.in_q + io) + ASDR_N / 8;
         pf_in[0] = load_int4_nt(pi); pf_in[1] = load_int4_nt(pi + 8); pf_in[2] = load_int4_nt(pq); pf_in[3] = load_int4_nt(pq + 8);
@@ -2211,9 +1999,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       float sv[4];
       if (HAS_ALS && !ALS_FULL_OPT && !if_pre) load_if_rows();
       sv[0] = if_s4.x; sv[1] = if_s4.y; sv[2] = if_s4.z; sv[3] = if_s4.w;
-      CHAIN_PRIO_ON();
       biquad_pipe<PIPE_PK>(Lp + (iq ? W1 : W0), true, st, if_cf, sv);
-      CHAIN_PRIO_OFF();
       *reinterpret_cast<float4 *>(&Sp->if_state[iq][4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
       if (ROLE == 1 && ASDR_STREAM_R1_CARRY) {
         r1_if_s4 = make_float4(sv[0], sv[1], sv[2], sv[3]);
@@ -2224,7 +2010,6 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     if (C16 && lo_hit) store4(lds + (lane_i >> 4) * STRIDE + PH + ((4 * lane_i) & 63), lo4);   // word i of [cos | sin]: row i >> 6, place i & 63
     WAVE_SYNC();
     TL(5);
-    mw_straggler(2);
     if (DO1) { TAP_ROW(ASDR_TAP_IF_I, W0); TAP_ROW(ASDR_TAP_IF_Q, W1); }
     // A role's own status bits go back with atomics: the three roles of a channel group update one word
     auto store_status_bits = [&](uint32_t mask) {
@@ -2238,11 +2023,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
         for (int m = 0; m < 4; ++m) { vi[m] = *reinterpret_cast<const v4f *>(L + W0 + kF + 32 * m); vq[m] = *reinterpret_cast<const v4f *>(L + W1 + kF + 32 * m); }
         xch_store4x4(xa, vi[0], vi[1], vi[2], vi[3]); xch_store4x4(xa + ASDR_N, vq[0], vq[1], vq[2], vq[3]);
         store_status_bits(ASDR_S_NB_DETECTED);
-#ifndef ASDR_STREAM_LATE_SIGNAL
-#define ASDR_STREAM_LATE_SIGNAL 1   /* role 1 publishes block k in front of block k + 1's IF pipeline (the stores' round trip used to sit at the end of every block: ~1.7 k cycles) */
-#endif
-        if (ASDR_STREAM_LATE_SIGNAL) sig_pending = (uint32_t)blk + 1u;   // (published below, in front of the next block's IF pipeline; in front of any wait; behind the last block)
-        else stream_signal(a.stream_prog + wave_g, (uint32_t)blk + 1u, lane);
+        sig_pending = (uint32_t)blk + 1u;   // (published below, in front of the next block's IF pipeline; in front of any wait; behind the last block: here, the stores' round trip sat at the end of every block, ~1.7 k cycles)
         continue;
       } else {
         v4f vi[4], vq[4];
@@ -2255,7 +2036,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #pragma unroll
         for (int m = 0; m < 4; ++m) { *reinterpret_cast<v4f *>(L + W0 + kF + 32 * m) = vi[m]; *reinterpret_cast<v4f *>(L + W1 + kF + 32 * m) = vq[m]; }
         WAVE_SYNC();
-        if constexpr (R2_PREFETCH) {   // how far the two producers are: read in front of the Hilbert FIR (the prefetch of the next block's rows)
+        if constexpr (R2_ONE_TRIP) {   // how far the two producers are: read in front of the Hilbert FIR (the prefetch of the next block's rows)
           r2_look_in = __hip_atomic_load(a.stream_prog + wave_g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           r2_look_lo = __hip_atomic_load(a.stream_prog + 3 * a.stream_waves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -2388,7 +2169,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       if constexpr (C16) { ph2[0] = lds[PH + lane_i]; ph2[1] = phase_step(ph2[0], minc); WAVE_SYNC(); }   // (every lane has read channel 0's phases: the pairs below overwrite them)
       else { const float2 p2 = *reinterpret_cast<const float2 *>(lds + PH + 2 * lane); ph2[0] = p2.x; ph2[1] = p2.y; }
       float c2[2], s2[2];
-      sincos_batch<2, SINE_LDS>(sine, ph2, c2, s2, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
+      sincos_batch<2, HAS_SAM>(sine, ph2, c2, s2, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
       if constexpr (C16) {   // 128 cos in the 64-float phase areas of channels 0 and 1, 128 sin in those of channels 2 and 3
         *reinterpret_cast<float2 *>(lds + (lane_i >> 5) * STRIDE + PH + ((2 * lane_i) & 63)) = make_float2(c2[0], c2[1]);
         *reinterpret_cast<float2 *>(lds + (2 + (lane_i >> 5)) * STRIDE + PH + ((2 * lane_i) & 63)) = make_float2(s2[0], s2[1]);
@@ -2402,7 +2183,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     // in HBM (slot hs = this block, hs^1 = previous block = the reference's exact 128-sample delay, :111)
     // Uniform SSB waves (round 5): the mixed Q stays in registers for the Hilbert stage (same lane, same pieces) and neither mixed row
     // goes back to LDS -- the delayed I comes from the HBM ring, nothing reads W0 / W1 again before the history overlays them.
-    constexpr bool QN_DIRECT_K = UNIFORM && ABL_ON(ABL_MIX) && (ASDR_MIX_KEEP_Q != 0);
+    constexpr bool QN_DIRECT_K = UNIFORM && ABL_ON(ABL_MIX);
     const bool qn_direct = QN_DIRECT_K && is_ssb;
     float qn[16];   // own pieces (samples kF + 32m + j at [4m + j]) of the mixed Q
     DEFINE_ALL_PATHS(qn, 16);
@@ -2423,7 +2204,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
               float ph[4];                                                                                                                    \
               const float2 e2 = *reinterpret_cast<const float2 *>(L + PH + ((kF + 32 * m) >> 1));                                             \
               ph[0] = e2.x; ph[1] = phase_step(e2.x, minc); ph[2] = e2.y; ph[3] = phase_step(e2.y, minc);                                     \
-              sincos_batch<4, SINE_LDS>(sine, ph, cc, sn, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);                         \
+              sincos_batch<4, HAS_SAM>(sine, ph, cc, sn, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);                         \
             }                                                                                                                                 \
             _Pragma("unroll")                                                                                                                 \
             for (int j = 0; j < 4; ++j) {                                                                                                     \
@@ -2461,15 +2242,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           // per-channel phases (the wave's channels carry different mixer phases): 4 x (cos, sin) lookups per piece, gathers batched
           float ph[4];
           load4(L + PH + kF + 32 * m, ph);
-#ifndef ASDR_MIX_SERIAL_LOOKUPS
-          sincos_batch<4, SINE_LDS_PC>(SINE_LDS_PC ? sine_tab : nullptr, ph, cc, sn, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
-#else
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            cc[j] = cos_f32(sine, ph[j], two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d); sn[j] = sin_f32(sine, ph[j], two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d});
-            if ((j & 1) == 1) SCHED_FENCE();
-          }
-#endif
+          sincos_batch<4, HAS_SAM>(sine, ph, cc, sn, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -2480,11 +2253,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #pragma unroll
           for (int j = 0; j < 4; ++j) qn[4 * m + j] = mq[j];
         } else { store4(L + W0 + kF + 32 * m, mi); store4(L + W1 + kF + 32 * m, mq); }
-#ifndef ASDR_TEMPORAL_RINGS
         if (is_ssb) store4_state<ST_PLAIN>(hi_ring + hs * 128 + 32 * m, mi);
-#else
-        if (is_ssb) store4(hi_ring + hs * 128 + 32 * m, mi);
-#endif
       }
     }
 
@@ -2555,7 +2324,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
         v2f fa[4], fb[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) { fa[e] = (v2f){0.0f, 0.0f}; fb[e] = (v2f){0.0f, 0.0f}; }
-        if (ABL_ON(ABL_HIL)) hilbert_fir<0, 4, false>(L, 4 * s8, fa);   // outputs 8 s8 + 2e, + 1  (taps as scalar operands: this form has no register for them)
+        if (ABL_ON(ABL_HIL)) hilbert_fir<0, 4>(L, 4 * s8, fa);   // outputs 8 s8 + 2e, + 1
         WAVE_SYNC();                                               // pass 1 has read everything it needs
         {
           float t[32];
@@ -2571,7 +2340,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           for (int j = 0; j < 4; ++j) { const int k = kF + 32 * m + j; if (k >= 63 && k < 127) L[XP + 191 + k] = qn[4 * m + j]; }   // x[256 + k] at word 256 + k - 65
         }
         WAVE_SYNC();
-        if (ABL_ON(ABL_HIL)) hilbert_fir<0, 4, false>(L, 4 * s8, fb);   // the same window 64 samples on: outputs 64 + 8 s8 + 2e, + 1
+        if (ABL_ON(ABL_HIL)) hilbert_fir<0, 4>(L, 4 * s8, fb);   // the same window 64 samples on: outputs 64 + 8 s8 + 2e, + 1
         WAVE_SYNC();                                               // all history reads done: W1 may overwrite it
         TL(9);
         load_af_agc_state();
@@ -2594,14 +2363,6 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             load4(hq_ring + (hs ^ 1u) * 128 + 32 * m, hq_m + 4 * m);
           }
         }
-        constexpr bool HIST_B128 = MW && WAVES == 4 && (ASDR_MW_HIST_B128 != 0);   // (is_ssb is wave-uniform there: every lane is here for the DPP moves)
-        if constexpr (HIST_B128) {
-          hilbert_hist_store16<false>(L + XP + kF, hq_o, hq_m[0], s8 == 7);
-          __builtin_amdgcn_sched_barrier(0);   // (block by block: a block's registers are free before the next one's pieces are put together)
-          hilbert_hist_store16<false>(L + XP + 128 + kF, hq_m, qn[0], s8 == 7);
-          __builtin_amdgcn_sched_barrier(0);
-          hilbert_hist_store16<true>(L + XP + 256 + kF, qn, 0.0f, s8 == 7);
-        } else {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
 #pragma unroll
@@ -2611,26 +2372,18 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             L[XP + 127 + k] = hq_m[4 * m + j];
           }
         }
-        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          if constexpr (!HIST_B128) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) L[XP + 255 + kF + 32 * m + j] = qn[4 * m + j];
-          }
-#ifndef ASDR_TEMPORAL_RINGS
           store4_state<ST_PLAIN>(hq_ring + hs * 128 + 32 * m, qn + 4 * m);
-#else
-          store4(hq_ring + hs * 128 + 32 * m, qn + 4 * m);   // newest replaces oldest (loaded before the IF pipeline)
-#endif
         }
         if (lead) S->hil_slot = hs ^ 1u;
         carry_hs = hs ^ 1u;
       }
       WAVE_SYNC();
       TL(8);
-      mw_straggler(3);
-      if constexpr (R2_PREFETCH) {
+      if constexpr (R2_ONE_TRIP) {
         // The NEXT block's oscillator entry and IF rows, if both producers are known to have published it (the counters as last polled: a producer that is
         // ahead is polled once for several blocks): the round trip of ~1.9 k cycles runs under the FIR.  Ring slots (blk + 1) % depth are this wave's to read
         // until it publishes block blk + 1 itself.
@@ -2650,10 +2403,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           r2_pref = true;
         }
       }
-#ifndef ASDR_UPAR_IDL_EARLY
-#define ASDR_UPAR_IDL_EARLY 1   /* the launch-constant form requests the delayed I before the FIR too: the registers its parameter row no longer takes */
-#endif
-      constexpr bool IDL_EARLY = (ROLE == 2) || (UPAR && ASDR_UPAR_IDL_EARLY != 0);   // the pipeline's role 2 and the launch-constant form have the registers to request the delayed I before the FIR
+      constexpr bool IDL_EARLY = (ROLE == 2) || UPAR;   // the pipeline's role 2 and the launch-constant form have the registers to request the delayed I before the FIR
       if (IDL_EARLY && is_ssb) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) load4(hi_ring + (hs ^ 1u) * 128 + 32 * m, idl + 4 * m);
@@ -2666,7 +2416,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #pragma unroll
       for (int e = 0; e < FIR_NE; ++e) acc2[e] = (v2f){0.0f, 0.0f};
       if (ROLE == 2) __syncthreads();   // the history is staged: the helper may read it
-      if constexpr (MW && WAVES == 4 && ASDR_MW_FIR_RING != 0 && ASDR_FIR_TAPS_IN_VGPRS == 0) { if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir_ring(L, k0 >> 1, acc2); }
+      if constexpr (MW && WAVES == 4 && ASDR_MW_FIR_RING != 0) { if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir_ring(L, k0 >> 1, acc2); }
       else if (ABL_ON(ABL_HIL) && is_ssb) hilbert_fir<0, FIR_NE>(L, k0 >> 1, acc2);
       if (ROLE == 2) __syncthreads(); else WAVE_SYNC();   // all history reads done: rows W0/W1 may overwrite the start of the history
       TL(9);
@@ -2817,125 +2567,17 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
     // ---- audio IIR filter, AudioSDR.cpp:149, 280-286: lanes s8 = 0..3 are the four stages ---------------------
     if constexpr ((MW_SHARE & 1) != 0) {
       if (ABL_ON(ABL_AF) && af_en) {   // (launch-uniform: all four waves or none)
-        // Round 6: the AGC duty BESIDE the audio duty.  While the blocks of a bank attack (a fresh bank's first ~150 blocks, any bank after a level step)
-        // the AGC's envelope chain (6 k cycles for which three waves parked) follows the audio cascades on the two waves that would otherwise sit out
-        // the audio duty at the barrier: the blanker-duty wave (rel 0) takes the filtered samples from the rows as the cascades' last stage leaves
-        // them (progress words of the two audio waves in LDS), forms |x| and beta |x| for all 32 channels, four samples per lane; the AGC-duty wave
-        // (rel 3) follows IT with the lean chain (below): envelope after every sample, 32 channels on 32 lanes.  Taken when every channel of the
-        // workgroup is in the lean regime and some channel attacked in the PREVIOUS block (decided behind the blanker chain's barrier, from words
-        // published in front of it): a steady bank, whose blocks are quiet, does not pay for chains nobody needs.
-        if constexpr (PIPE_AGC) {
-          if (agc_piped && lead && agc_en) {
-            float *mq = mwx + MWX * (wave * 8 + c8);
-            mq[8] = agc_old0; mq[11] = agc_al_a; mq[12] = agc_be_a;
-          }
-        }
         TL(21);
-        if constexpr (MW && (ASDR_MW_STRAGGLER_PRIO != 0 || ASDR_MW_PRIO_REL0_TAIL != 0)) __builtin_amdgcn_s_setprio(0);
         __syncthreads();               // every wave's demodulated audio is in its W0 rows
         TL(22);
         if (mw_audio_duty) {           // 16 cascades x 4 stages: the whole wave works
-#ifndef ASDR_MW_PRIO_AUDIO
-#define ASDR_MW_PRIO_AUDIO ASDR_MW_PRIO   /* the audio-cascade duty's priority (experiments: 0 = only the short chain duties are raised) */
-#endif
-          if (ASDR_MW_PRIO_AUDIO) __builtin_amdgcn_s_setprio(ASDR_MW_PRIO_AUDIO);
+          if (ASDR_MW_PRIO) __builtin_amdgcn_s_setprio(ASDR_MW_PRIO);
           const int st = pl_st;
           float sv[4];
           sv[0] = af_s4.x; sv[1] = af_s4.y; sv[2] = af_s4.z; sv[3] = af_s4.w;
-          if (PIPE_AGC && agc_piped) biquad_pipe<PIPE_PK, PIPE_AGC>(lds_wg + (16 * (mw_rel - 1) + mw_casc) * STRIDE + W0, true, st, af_cf, sv, mw_flags + 1 + mw_rel, lane_i == 0);
-          else biquad_pipe<PIPE_PK>(lds_wg + (16 * (mw_rel - 1) + mw_casc) * STRIDE + W0, true, st, af_cf, sv);   // (a steady bank: the cascades as they were)
+          biquad_pipe<PIPE_PK>(lds_wg + (16 * (mw_rel - 1) + mw_casc) * STRIDE + W0, true, st, af_cf, sv);
           *reinterpret_cast<float4 *>(&mw_af_S->af_state[4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
-          if (ASDR_MW_PRIO_AUDIO) __builtin_amdgcn_s_setprio(0);
-        } else if constexpr (PIPE_AGC) {
-          if (agc_piped) {
-            // Progress words are read with explicit ds_read + s_waitcnt (a `volatile` access is completed on the spot by the compiler, and through a generic
-            // pointer it takes the flat path): the poll for a chunk is in flight during the previous chunk's arithmetic, and a chunk's operands are
-            // requested a chunk ahead whenever the producer is known to be that far (two dependent LDS round trips per chunk -- poll, then operands --
-            // are longer than the chunk's arithmetic under load).  The compiler does not count these reads in its own s_waitcnt operands: it then
-            // waits for MORE than it needs, never for less.
-            if (ASDR_MW_PRIO) __builtin_amdgcn_s_setprio(ASDR_MW_PRIO);
-            if (mw_rel == 0) {
-              // |x| clamped to 1.0 (:410-411; NaN-preserving like the owners' pass) -> [256 + ..), beta |x| -> [AGC_GV + ..): lane = (channel, half chunk)
-              const int q = lane_i >> 1;
-              float *Lc = lds_wg + q * STRIDE + 4 * (lane_i & 1);
-              const float be_a = mwx[MWX * q + 12];
-              const uint32_t src_lds = (uint32_t)(uintptr_t)(lds_int_ptr)(mw_flags + 2), dst_lds = (uint32_t)(uintptr_t)(lds_int_ptr)(mw_flags + 1);
-              v2i pr;
-              auto poll_issue = [&]() { asm volatile("ds_read_b64 %0, %1" : "=v"(pr) : "v"(src_lds) : "memory"); };
-              auto poll_value = [&]() -> int {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pr) :: "memory");   // (and no row read moves above the poll it depends on)
-                return __builtin_amdgcn_readfirstlane(pr.x < pr.y ? pr.x : pr.y);
-              };
-              poll_issue();
-              int known = poll_value();
-              while (known < 1) { __builtin_amdgcn_s_sleep(2); poll_issue(); known = poll_value(); }
-              float xr[4];
-              load4(Lc + W0, xr);
-#pragma unroll 1
-              for (int c = 0; c < ASDR_N / 8; ++c) {
-                const int nc = (c + 1 < ASDR_N / 8) ? c + 1 : c;
-                const bool pre = known > nc;   // (wave-uniform)
-                float xn[4];
-                if (pre) load4(Lc + W0 + 8 * nc, xn);
-                poll_issue();   // (consumed behind the chunk)
-                float ax[4], pb[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const float t = fabsf(xr[u]); ax[u] = (t > 1.0f) ? 1.0f : t; pb[u] = be_a * ax[u]; }
-                store4(Lc + 256 + 8 * c, ax); store4(Lc + AGC_GV + 8 * c, pb);
-                if (lane_i == 0) asm volatile("ds_write_b32 %0, %1" :: "v"(dst_lds), "v"(c + 1) : "memory");   // (the LDS executes a wave's operations in order)
-                known = poll_value();
-                if (!pre) {
-                  while (known <= nc) { __builtin_amdgcn_s_sleep(1); poll_issue(); known = poll_value(); }
-                  load4(Lc + W0 + 8 * nc, xn);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) xr[u] = xn[u];
-              }
-            } else if (lane_i < 8 * WAVES) {   // rel 3
-              const int q = lane_i;
-              float *Lc = lds_wg + q * STRIDE;
-              float old_abs = mwx[MWX * q + 8];
-              const float al_a = mwx[MWX * q + 11];
-              const uint32_t src_lds = (uint32_t)(uintptr_t)(lds_int_ptr)(mw_flags + 1);
-              int pr;
-              auto poll_issue = [&]() { asm volatile("ds_read_b32 %0, %1" : "=v"(pr) : "v"(src_lds) : "memory"); };
-              auto poll_value = [&]() -> int {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pr) :: "memory");
-                return __builtin_amdgcn_readfirstlane(pr);
-              };
-              poll_issue();
-              int known = poll_value();
-              while (known < 1) { __builtin_amdgcn_s_sleep(2); poll_issue(); known = poll_value(); }
-              float ax[8], pb[8];
-              load8(Lc + 256, ax); load8(Lc + AGC_GV, pb);
-#pragma unroll 1
-              for (int c = 0; c < ASDR_N / 8; ++c) {
-                const int nc = (c + 1 < ASDR_N / 8) ? c + 1 : c;
-                const bool pre = known > nc;
-                float axn[8], pbn[8];
-                if (pre) { load8(Lc + 256 + 8 * nc, axn); load8(Lc + AGC_GV + 8 * nc, pbn); }
-                poll_issue();
-                float ov[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                  const float pa = al_a * old_abs;
-                  const float v_new = pa + pb[u];
-                  old_abs = (ax[u] > old_abs) ? v_new : old_abs;
-                  ov[u] = old_abs;
-                }
-                store8(Lc + AGC_GV + 8 * c, ov);
-                known = poll_value();
-                if (!pre) {
-                  while (known <= nc) { __builtin_amdgcn_s_sleep(1); poll_issue(); known = poll_value(); }
-                  load8(Lc + 256 + 8 * nc, axn); load8(Lc + AGC_GV + 8 * nc, pbn);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { ax[u] = axn[u]; pb[u] = pbn[u]; }
-              }
-              mwx[MWX * q + 8] = old_abs;
-            }
-            if (ASDR_MW_PRIO) __builtin_amdgcn_s_setprio(0);
-          }
+          if (ASDR_MW_PRIO) __builtin_amdgcn_s_setprio(0);
         }
         TL(23);
         __syncthreads();
@@ -2948,9 +2590,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       float sv[4];
       sv[0] = af_s4.x; sv[1] = af_s4.y; sv[2] = af_s4.z; sv[3] = af_s4.w;
       ChanSmall *const Saf = Spa;   // (by all lanes)
-      CHAIN_PRIO_ON();
       biquad_pipe<PIPE_PK>(Lpa + W0, on, st, af_cf, sv);
-      CHAIN_PRIO_OFF();
       if (on) *reinterpret_cast<float4 *>(&Saf->af_state[4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
       WAVE_SYNC();
     }
@@ -2992,14 +2632,13 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       const float am_level = (float)(2.0 * (double)(carrier_fresh ? carrier_now : agc_carrier0));
       const float am_clamped = (am_level > 1.0f) ? 1.0f : am_level;
       // (AM: twice the carrier level stands in for |x| of every sample, :407-409 -- the lead lane holds it)
-      const bool agc_quiet = ASDR_AGC_QUIET_PATH && __all(!(agc_en && lead) || (agc_hc0 >= 128u && agc_hang >= 8u && !((is_am ? am_clamped : blockmax) > agc_old0)));
-      // (the four-wave form, round 6: the AGC duty wave ran the lean chain beside the audio duty -- the envelope rows are there already; behind barrier 4)
+      const bool agc_quiet = __all(!(agc_en && lead) || (agc_hc0 >= 128u && agc_hang >= 8u && !((is_am ? am_clamped : blockmax) > agc_old0)));
       if (agc_en && !agc_quiet) {   // stage the channel's gain table and the |x| rows in LDS
         if constexpr (!C16) {
 #pragma unroll
         for (int r = 0; r < 5; ++r) { const int q = s8 + 8 * r; if (q < 33) *reinterpret_cast<float4 *>(L + AGC_TAB + 4 * q) = agc_t4[r]; }
         }
-        if (!agc_piped) { store8(L + AGC_GV + kA, av16); store8(L + AGC_GV + kA + 64, av16 + 8); }
+        store8(L + AGC_GV + kA, av16); store8(L + AGC_GV + kA + 64, av16 + 8);
       }
       if (!agc_quiet) WAVE_SYNC();
       TL(12);
@@ -3058,13 +2697,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             for (int u = 0; u < 8; ++u) {
               const float av = x[u];
               const bool att = av > old_abs;
-#ifndef ASDR_AGC_ATTACK_BRANCHFREE
-#define ASDR_AGC_ATTACK_BRANCHFREE 1
-#endif
               // The four-wave form's duty wave runs 32 channels' chains at once: in an attacking chunk some channel attacks at almost every sample, so the
               // per-sample branch (right for the eight channels of a wave of its own: round 4) only adds its test -- straight-line selects there (round 6).
-              if ((MW && ASDR_AGC_ATTACK_BRANCHFREE) || __any(att)) {   // (one wave per workgroup: rare -- a sample above the envelope in some channel of the wave)
-                if (!(MW && ASDR_AGC_ATTACK_BRANCHFREE)) asm volatile("");   // keeps this a branch (the compiler would otherwise flatten it into selects for every sample)
+              if (MW || __any(att)) {   // (one wave per workgroup: rare -- a sample above the envelope in some channel of the wave)
+                if (!MW) asm volatile("");   // keeps this a branch (the compiler would otherwise flatten it into selects for every sample)
                 const float pa = al_a * old_abs, pb = be_a * av;   // (:418)
                 const float v_new = pa + pb;
                 old_abs = att ? v_new : old_abs;
@@ -3163,12 +2799,10 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       if constexpr ((MW_SHARE & 4) != 0) {
         // MW: every wave says whether its block is quiet; the AGC-duty wave (rel 3) runs the chains of the other waves' channels, one per lane
         // (the |x| rows and the gain tables are in the channels' LDS rows; the scalars come from the channels' state / parameter rows)
-        constexpr bool LEAN_OK = (ASDR_AGC_LEAN != 0) && (ASDR_MW_OWN_STORES != 0);
-        if (!agc_piped) {
         if (lead) {
           float *mq = mwx + MWX * (wave * 8 + c8);
           mq[5] = __int_as_float(agc_quiet ? 1 : 0); mq[6] = am_clamped;
-          if (ASDR_MW_OWN_STORES && !agc_quiet) {   // the chain's scalars: this wave has loaded them for the quiet test (the duty wave asked for them again: 8 scattered loads per lane in front of its chain)
+          if (!agc_quiet) {   // the chain's scalars: this wave has loaded them for the quiet test (the duty wave asked for them again: 8 scattered loads per lane in front of its chain)
             *reinterpret_cast<float4 *>(mq + 8) = make_float4(agc_old0, __uint_as_float(agc_hc0), gain_in, agc_al_a);
             *reinterpret_cast<float4 *>(mq + 12) = make_float4(agc_be_a, agc_al_r, agc_be_r, __uint_as_float(agc_hang));
           }
@@ -3187,8 +2821,8 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           const int q = lane_i;
           const bool active = (__float_as_int(mwx[MWX * q + 5]) == 0);
           float4 i0 = make_float4(0.f, 0.f, 0.f, 0.f), i1 = i0;
-          if (ASDR_MW_OWN_STORES && active) { i0 = *reinterpret_cast<const float4 *>(mwx + MWX * q + 8); i1 = *reinterpret_cast<const float4 *>(mwx + MWX * q + 12); }
-          const bool lean = LEAN_OK && !is_am && __all(!active || (__float_as_uint(i0.y) >= 128u && __float_as_uint(i1.w) >= 128u));
+          if (active) { i0 = *reinterpret_cast<const float4 *>(mwx + MWX * q + 8); i1 = *reinterpret_cast<const float4 *>(mwx + MWX * q + 12); }
+          const bool lean = !is_am && __all(!active || (__float_as_uint(i0.y) >= 128u && __float_as_uint(i1.w) >= 128u));
           if (q == 0) mw_flags[0] = lean ? 1 : 0;
           if (lean) {
             if (active) {
@@ -3222,42 +2856,29 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
             }
           } else
           if (active) {
-            if (ASDR_MW_OWN_STORES) {
-              mwx[MWX * q + 7] = agc_chain(std::true_type{}, lds_wg + q * STRIDE, nullptr, i0.x, __float_as_uint(i0.y), i0.z, i0.w, i1.x, i1.y, i1.z, __float_as_uint(i1.w), is_am, mwx[MWX * q + 6]);
-              mwx[MWX * q + 8] = agc_old_end; mwx[MWX * q + 9] = __uint_as_float(agc_hc_end);
-            } else {
-            const int chq = mw_channel(q);
-            ChanSmall *Sq = row_ptr(a.small, (uint32_t)chq * (uint32_t)sizeof(ChanSmall));
-            const ChanParams *Pq = UPAR ? &a.uni : row_ptr(a.params, (uint32_t)chq * (uint32_t)sizeof(ChanParams));
-            mwx[MWX * q + 7] = agc_chain(std::false_type{}, lds_wg + q * STRIDE, Sq, Sq->agc_old_abs, Sq->agc_hang_counter, Sq->agc_gain, Pq->agc_alpha_att, Pq->agc_beta_att,
-                                       Pq->agc_alpha_rel, Pq->agc_beta_rel, Pq->agc_hang_count, is_am, mwx[MWX * q + 6]);
-            }
+            mwx[MWX * q + 7] = agc_chain(std::true_type{}, lds_wg + q * STRIDE, nullptr, i0.x, __float_as_uint(i0.y), i0.z, i0.w, i1.x, i1.y, i1.z, __float_as_uint(i1.w), is_am, mwx[MWX * q + 6]);
+            mwx[MWX * q + 8] = agc_old_end; mwx[MWX * q + 9] = __uint_as_float(agc_hc_end);
           }
         }
         if (ASDR_MW_PRIO && mw_rel == 3) __builtin_amdgcn_s_setprio(0);
         TL(27);
         __syncthreads();
         TL(28);
-        } else { TL(25); TL(26); TL(27); TL(28); }
-        const bool lean_done = LEAN_OK && (agc_piped || __builtin_amdgcn_readfirstlane(mw_flags[0]) != 0);
+        const bool lean_done = __builtin_amdgcn_readfirstlane(mw_flags[0]) != 0;
         if (lean_done && !agc_quiet && agc_en) {
           agc_lean_finish(lead ? mwx[MWX * (wave * 8 + c8) + 8] : 0.0f);
         } else
         if (!agc_quiet && lead) {
           const float *mq = mwx + MWX * (wave * 8 + c8);
           const float g_end = mq[7]; status = (status & ~ASDR_S_AGC_ACTIVE) | (((double)g_end < 0.99) ? ASDR_S_AGC_ACTIVE : 0u);
-          if (ASDR_MW_OWN_STORES && agc_en) { S->agc_old_abs = mq[8]; S->agc_hang_counter = __float_as_uint(mq[9]); S->agc_gain = g_end; }
+          if (agc_en) { S->agc_old_abs = mq[8]; S->agc_hang_counter = __float_as_uint(mq[9]); S->agc_gain = g_end; }
         }
       } else {
-#ifndef ASDR_AGC_LEAN1
-#define ASDR_AGC_LEAN1 1   /* the lean chain for the forms whose waves run their own channels' chains too (one lane per channel) */
-#endif
         // The lean chain (see the four-wave form's AGC duty above) on the wave's own lead lanes: no channel of the wave can run out of its hang counter
         // inside the block (and none is AM: twice the carrier level stands in for |x| there) -- the envelope recurrence alone, half the general form's
         // instructions per sample; what the block leaves behind is formed in parallel by agc_lean_finish.
-        constexpr bool LEAN1_OK = (ASDR_AGC_LEAN1 != 0) && !C16 && !(ROLE == 0 && WAVES == 1 && !ONEBLK_ && !HAS_ALS && !HAS_SAM && UNIFORM);   // (the looped plain kernel spills with it)
+        constexpr bool LEAN1_OK = !C16 && !(ROLE == 0 && WAVES == 1 && !ONEBLK_ && !HAS_ALS && !HAS_SAM && UNIFORM);   // (the looped plain kernel spills with it)
         const bool lean1 = LEAN1_OK && !agc_quiet && __all(!(agc_en && lead) || (!is_am && agc_hc0 >= 128u && agc_hang >= 128u));
-        if (!agc_quiet) CHAIN_PRIO_ON();
         if (lean1) {
           float old_abs = agc_old0;
           if (agc_en && lead) {
@@ -3293,7 +2914,6 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           const float g_end = agc_chain(std::false_type{}, L, S, agc_old0, agc_hc0, gain_in, agc_al_a, agc_be_a, agc_al_r, agc_be_r, agc_hang, is_am, am_clamped);
           status = (status & ~ASDR_S_AGC_ACTIVE) | (((double)g_end < 0.99) ? ASDR_S_AGC_ACTIVE : 0u);
         }
-        if (!agc_quiet) CHAIN_PRIO_OFF();
       }
       }
       if (!agc_quiet) WAVE_SYNC();
@@ -3411,11 +3031,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         float t[4]; load4(L + W0 + kF + 32 * m, t);
-#ifndef ASDR_PREV_TEMPORAL
         store4_nt(ap + 32 * m, t);   // written every block, read (if ever) a launch later: streaming store, keeps L2 for the rows that come back
-#else
-        store4(ap + 32 * m, t);
-#endif
       }
     }
     {
@@ -3436,11 +3052,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       }
       if (DO3 && !TO_ALS && valid) {
         int4 *po = reinterpret_cast<int4 *>(a.out + io_out);
-#ifndef ASDR_TEMPORAL_OUT
         store_int4_nt(po, ro[0].v); store_int4_nt(po + 8, ro[1].v);
-#else
-        po[0] = ro[0].v; po[8] = ro[1].v;
-#endif
       }
     }
     if (POST_ROLE) store_status_bits(ASDR_S_AGC_ACTIVE);   // (the pre role and the PLL of the NEXT block may be running beside this one)
@@ -3476,7 +3088,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       const float2 p2 = *reinterpret_cast<const float2 *>(lds + (C16 ? 0 : PH) + 2 * lane_i);
       const float ph2[2] = {p2.x, p2.y};
       float c2[2], s2[2];
-      sincos_batch<2, SINE_LDS>(sine, ph2, c2, s2, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
+      sincos_batch<2, HAS_SAM>(sine, ph2, c2, s2, two_pi, SinIndexK{K.inv_two_pi_d, K.sin_index_scale_d}, K.half_pi_d);
       *reinterpret_cast<float2 *>(lo_wr->c + 2 * lane_i) = make_float2(c2[0], c2[1]);
       *reinterpret_cast<float2 *>(lo_wr->s + 2 * lane_i) = make_float2(s2[0], s2[1]);
       WAVE_SYNC();
@@ -3540,14 +3152,8 @@ extern "C" __global__ __launch_bounds__(64 * ASDR_MW_WAVES, ASDR_WAVES_PER_EU) v
 }
 // SAM: 4 waves = 32 channels per workgroup (50,704 B of LDS -> 3 workgroups = 12 waves per CU), general form only
 ASDR_KERNEL(asdr_update_kernel_sam, ASDR_SAM_WAVES * 8 * ASDR_STRIDE + 260, ASDR_WAVES_PER_EU, ASDR_STRIDE, false, true, false, ASDR_SAM_WAVES)
-#ifndef ASDR_ALS_WAVES_PER_EU
-#define ASDR_ALS_WAVES_PER_EU 3   /* LDS allows 9 waves/CU: needs 3 on one SIMD */
-#endif
-#ifndef ASDR_ALS_LDS_PAD
-#define ASDR_ALS_LDS_PAD 0        /* occupancy experiments only: extra floats of LDS per wave (tools/ablate.py) */
-#endif
-ASDR_KERNEL(asdr_update_kernel_als, 8 * 516 + 260 + ASDR_ALS_LDS_PAD, ASDR_ALS_WAVES_PER_EU, 516, true, true, true, 1)
-ASDR_KERNEL(asdr_update_kernel_als_mixed, 8 * 516 + 260 + ASDR_ALS_LDS_PAD, ASDR_ALS_WAVES_PER_EU, 516, true, true, false, 1)
+ASDR_KERNEL(asdr_update_kernel_als, 8 * 516 + 260, ASDR_ALS_WAVES_PER_EU, 516, true, true, true, 1)
+ASDR_KERNEL(asdr_update_kernel_als_mixed, 8 * 516 + 260, ASDR_ALS_WAVES_PER_EU, 516, true, true, false, 1)
 // ALS with a short filter (taps <= 64, delay + taps <= 65: the reference's defaults are 55 and 3) on a channel that is not in SAM
 // mode: the filter's rows fit the plain instantiation's 388 floats per channel -> 12 waves per CU
 ASDR_KERNEL(asdr_update_kernel_als_small, 8 * ASDR_ALS_STRIDE, ASDR_WAVES_PER_EU, ASDR_ALS_STRIDE, true, false, true, 1)
@@ -3572,16 +3178,10 @@ extern "C" __global__ __launch_bounds__(64, ASDR_WAVES_PER_EU) void asdr_sam_pos
 // the phase row, the Hilbert history and the AGC overlay belong to the post role): 260-float rows (260 = 65 sixteen-byte slots == 1
 // mod 16, like 388: the 8 channels' rows start on different slots) = 8,320 B per wave -> 19 waves per CU by LDS, and at 126 VGPRs
 // FOUR waves per SIMD: the first instantiation of the chain at 16 waves per CU (round 4).
-#ifndef ASDR_PRE_STRIDE
-#define ASDR_PRE_STRIDE 260
-#endif
 extern "C" __global__ __launch_bounds__(64, 4) void asdr_sam_pre_kernel_uniform(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_PRE_STRIDE];
   asdr_update_body<ASDR_PRE_STRIDE, false, false, true, 1, 4>(a, lds);
 }
-#ifndef ASDR_POST_BOUNDS
-#define ASDR_POST_BOUNDS ASDR_WAVES_PER_EU
-#endif
 extern "C" __global__ __launch_bounds__(64, ASDR_POST_BOUNDS) void asdr_sam_post_kernel_uniform(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_STRIDE];
   asdr_update_body<ASDR_STRIDE, false, false, true, 1, 5>(a, lds);
@@ -3611,9 +3211,6 @@ extern "C" __global__ __launch_bounds__(64, ASDR_WAVES_PER_EU) void asdr_sam_pos
   __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_ALS_STRIDE];
   asdr_update_body<ASDR_ALS_STRIDE, true, false, true, 1, 5>(a, lds);
 }
-#ifndef ASDR_PLL_LANES
-#define ASDR_PLL_LANES 64   /* channels per wave of the PLL kernel (experiments: 32 = twice the waves, each half empty) */
-#endif
 // Channels with a short ALS filter (kind ASDR_KERNEL_ALS_SMALL), when there are enough of them: the chain up to the AGC as the PLAIN
 // instantiation (ROLE 6: every optimisation of the plain kernel, which the fused ALS instantiations had to give up for registers),
 // then the filter as a launch of its own on small LDS rows (asdr_als_kernel below).
@@ -3636,9 +3233,6 @@ extern "C" __global__ __launch_bounds__(64, 2) void asdr_als_pre_loop_kernel(Upd
 #define ALS_K_XB (-63)     /* L[ALS_K_XB + idx] = sample idx of the reference's 256-sample buffer, idx >= 64 (word 1 ..) */
 #define ALS_K_AW 196       /* taps: 32 even | 32 odd */
 #define ALS_K_SCR 261
-#ifndef ASDR_ALS_K_WAVES_PER_EU
-#define ASDR_ALS_K_WAVES_PER_EU 3
-#endif
 extern "C" __global__ __launch_bounds__(64, ASDR_ALS_K_WAVES_PER_EU) void asdr_als_kernel(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[8 * ALS_K_STRIDE];
   const int lane = threadIdx.x, c8 = lane >> 3, s8_ = lane & 7;
@@ -3746,11 +3340,7 @@ extern "C" __global__ __launch_bounds__(64) void asdr_sam_pll_kernel(UpdateArgs 
   // (The kernel is bound by its instruction count -- ~120 per sample and lane, 61 k wave instructions per SIMD for C3, as many as
   // the whole C2 chain -- not by these 32-byte accesses: 16-sample trips with the next trip's values requested ahead, and without
   // the stores altogether, changed its 0.18 ms by less than 0.01 / 0.04 ms.)
-#ifndef ASDR_PLL_NO_PREFETCH
   lk = pll_loop<false, 4, true>(Sc, a.k, sine, a.k.two_pi_f,
-#else
-  lk = pll_loop<false, 4>(Sc, a.k, sine, a.k.two_pi_f,
-#endif
     [&](int i, float *xr, float *xi) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) { const float *e = xt + (size_t)(i + u) * 16; xr[u] = e[0]; xi[u] = e[8]; } },
@@ -4041,7 +3631,7 @@ extern "C" int asdr_launch_update_ordered(const UpdateArgs *a, int variant, int 
     ASDR_LAUNCH(asdr_als_pre_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
     ASDR_LAUNCH(asdr_als_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
   }
-  else if (variant == ASDR_KERNEL_ALS_SMALL) { if (uniform && ASDR_ONEBLK && ASDR_ONEBLK_ALS && a->n_blocks == 1 && a->run_if == nullptr) ASDR_LAUNCH(asdr_update_kernel_als_small_one, dim3(n_waves), dim3(64), 0, stream, *a); else if (uniform) ASDR_LAUNCH(asdr_update_kernel_als_small, dim3(n_waves), dim3(64), 0, stream, *a); else ASDR_LAUNCH(asdr_update_kernel_als_small_mixed, dim3(n_waves), dim3(64), 0, stream, *a); }
+  else if (variant == ASDR_KERNEL_ALS_SMALL) { if (uniform && a->n_blocks == 1 && a->run_if == nullptr) ASDR_LAUNCH(asdr_update_kernel_als_small_one, dim3(n_waves), dim3(64), 0, stream, *a); else if (uniform) ASDR_LAUNCH(asdr_update_kernel_als_small, dim3(n_waves), dim3(64), 0, stream, *a); else ASDR_LAUNCH(asdr_update_kernel_als_small_mixed, dim3(n_waves), dim3(64), 0, stream, *a); }
   else if ((variant == ASDR_KERNEL_SAM || variant == ASDR_KERNEL_SAM_ALS) && a->xch_sam != nullptr) {   // pre | PLL | post (one block per call: the host loops)
     if (uniform) ASDR_LAUNCH(asdr_sam_pre_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_sam_pre_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
@@ -4076,7 +3666,7 @@ extern "C" int asdr_launch_update_ordered(const UpdateArgs *a, int variant, int 
     { if (reversed) *reversed = (int)a->wg_reverse;
       ASDR_LAUNCH(asdr_update_kernel_mw, dim3((n_waves + ASDR_MW_WAVES - 1) / ASDR_MW_WAVES), dim3(64 * ASDR_MW_WAVES), 0, stream, *a); }
     else
-    if (uniform && ASDR_ONEBLK && a->n_blocks == 1 && a->run_if == nullptr) { if (reversed) *reversed = (int)a->wg_reverse; ASDR_LAUNCH(asdr_update_kernel_one, dim3(n_waves), dim3(64), 0, stream, *a); }
+    if (uniform && a->n_blocks == 1 && a->run_if == nullptr) { if (reversed) *reversed = (int)a->wg_reverse; ASDR_LAUNCH(asdr_update_kernel_one, dim3(n_waves), dim3(64), 0, stream, *a); }
     else if (uniform) ASDR_LAUNCH(asdr_update_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_update_kernel_mixed, dim3(n_waves), dim3(64), 0, stream, *a);
   }

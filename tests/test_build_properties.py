@@ -52,6 +52,35 @@ def test_the_16_waves_per_cu_kernel_fits_its_budget():
     assert r["VGPRs"] <= 128 and r.get("VGPRs Spill", 0) == 0 and r["LDS Size [bytes/block]"] <= 10240, r
 
 
+def test_every_build_switch_has_its_default_in_the_top_block():
+    """Every ASDR_* name that asdr_kernels.hip or asdr_fir.h tests in a preprocessor conditional is a switch whose default stands in the one block
+    at the top of asdr_kernels.hip, a name of asdr_device.h / include/asdr.h, or one of the bare -D flags; no default is defined further down
+    (inside a function body in particular); and tools/README.md names every switch of the block."""
+    def read(*p):
+        with open(os.path.join(ROOT, *p)) as f:
+            return f.read()
+    kernels = read("audiosdr_amd", "csrc", "asdr_kernels.hip")
+    begin, end = kernels.index("// ---- build switches"), kernels.index("// ---- end of the build switches")
+    assert begin < kernels.index("__global__") and begin < kernels.index("__device__")
+    block = kernels[begin:end]
+    guarded = re.findall(r"^#ifndef (ASDR_[A-Z0-9_]+)\n#define \1 .*   /\* .+ \*/\n#endif$", block, flags=re.M)
+    assert guarded and len(guarded) == block.count("#define") == len(set(guarded)), "one commented #ifndef / #define / #endif per switch"
+    known = set(guarded) | {"ASDR_TIMELINE", "ASDR_NB_ALWAYS_SLOW", "ASDR_FENCE"}
+    known |= set(re.findall(r"^\s*#\s*define\s+(ASDR_[A-Z0-9_]+)", read("audiosdr_amd", "csrc", "asdr_device.h") + read("include", "asdr.h"), flags=re.M))
+    rest = kernels[:begin] + kernels[end:]
+    for name, text in (("asdr_kernels.hip", kernels), ("asdr_fir.h", read("audiosdr_amd", "csrc", "asdr_fir.h"))):
+        for line in re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b.*$", text, flags=re.M):
+            if re.match(r"\s*#\s*ifndef ASDR_FIR_H\b", line):
+                continue   # (the header's include guard)
+            for sw in re.findall(r"ASDR_[A-Z0-9_]+", line):
+                assert sw in known, "%s tests %s, which has no default in the top block: %s" % (name, sw, line.strip())
+    later = [sw for sw in re.findall(r"^\s*#\s*define\s+(ASDR_[A-Z0-9_]+)", rest, flags=re.M) if sw in guarded or re.search(r"#\s*ifndef\s+%s\b" % sw, rest)]
+    assert not later, "defaults outside the top block: %s" % later
+    readme = read("tools", "README.md")
+    missing = [sw for sw in guarded if not re.search(r"\b%s\b" % sw, readme)]
+    assert not missing, "tools/README.md does not name %s" % missing
+
+
 def test_launch_census_names_every_kernel_of_the_chain():
     """The launch census (include/asdr.h asdr_kernels_*; bench.py's `roofline.kernel` comes from it) lists exactly the kernels asdr_kernels.hip
     defines, and every launch site goes through ASDR_LAUNCH (a raw hipLaunchKernelGGL would be a launch the census never sees)."""

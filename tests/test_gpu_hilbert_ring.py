@@ -1,6 +1,6 @@
 """The Hilbert stage of the four-wave chain kernels -- FIR windows sliding through a register ring (audiosdr_amd/csrc/asdr_fir.h
-hilbert_fir_rows_ring), the history staged in front of it (asdr_kernels.hip; with -DASDR_MW_HIST_B128=1 by hilbert_hist_store16, one LDS
-store per 16 bytes) -- against the oracle at tolerance 0, with inputs aimed at what those two touch: every position of the 383-sample
+hilbert_fir_rows_ring), the history staged in front of it (asdr_kernels.hip; the variant with one LDS store per 16 bytes is archived as
+profiles/experiments/r06_mw_hist_b128.diff) -- against the oracle at tolerance 0, with inputs aimed at what those two touch: every position of the 383-sample
 window, both slots of the history ring, the seams between a channel's lanes and between the 32-float pieces of a block.
 
 Blanker off, unit gains.  Channel c carries, on top of low noise, ONE full-scale sample at position c mod 384 of the first three blocks;
