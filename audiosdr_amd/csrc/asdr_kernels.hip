@@ -70,6 +70,9 @@
 #ifndef ASDR_PIPE_PK_MASK
 #define ASDR_PIPE_PK_MASK 8   /* kernel kinds whose biquad pipelines run their y-independent products packed: 1 ALS, 2 plain, 4 SAM roles, 8 block pipeline (see biquad_pipe); build flag, measurements */
 #endif
+#ifndef ASDR_PIPE_SKEW1_MASK
+#define ASDR_PIPE_SKEW1_MASK 2   /* kernel kinds whose AUDIO cascades run with ONE sample of stage skew (131 slots instead of 152: biquad_pipe_skew1): 1 ALS, 2 plain, 4 SAM roles; never the block pipeline (its packed form needs whole chunks); the IF / AM-image cascades keep the chunked form (measured: profiles/README.md); build flag, measurements */
+#endif
 #ifndef ASDR_PIPE_CHUNK
 #define ASDR_PIPE_CHUNK 8   /* samples per lane per pipeline step: 4 (35 steps) or 8 (19 steps, less per-step overhead); tools/ablate.py builds 4 */
 #endif
@@ -465,6 +468,107 @@ __device__ __forceinline__ void biquad_pipe(float *row, bool on, int st, const f
   for (int c = 16; c < NSTEP; ++c) step(std::true_type{}, c);
 #endif
   sv[0] = x1; sv[1] = x2; sv[2] = y1; sv[3] = y2;
+}
+
+// The same cascade with ONE SAMPLE of stage skew (ASDR_PIPE_SKEW1_MASK: the audio cascades of the kinds it names): at slot t = 0..130 lane `st` handles sample t - st, so fill and drain cost
+// 3 slots instead of 3 chunks (131 slots instead of 152).  Same contract and lane map as biquad_pipe, same operations on the same operands in the same
+// association per sample and stage -- only the lane-time at which they run differs.  Stage 0 takes sample t from the LDS row (whole 16-byte pieces, one
+// chunk ahead); stage k > 0 takes row_shr:1 of the previous lane's newest output, which is that lane's y1 register after the previous slot (sample
+// t - 1 - (k - 1) = t - k).  A step = 8 slots.  After step c stage 3 has finished samples .. 8c + 4, so chunk c - 1 goes out during step c: five of
+// its samples are carried over from step c - 1 (a register renaming: two steps per trip).  The writes stay behind the reads of the same row: stage 0
+// has read through 8c + 15 when stage 3 writes 8c - 8 .. 8c - 1.  Only slots 0..2 and 128..130 have idle stages and predicated state updates.
+// A steady slot is 10 vector instructions: the four state products first (they cover the wait states between the previous slot's last add, which wrote
+// y1, and the DPP read of it: no s_nop), the select (v_cndmask_b32_dpp: VOP2, the stage-0 mask in VCC, set once per step), b0 * x and the four sums.
+// The new x goes into the register of the dead x2, so the x state alternates between two registers; y1 / y2 are the two newest outputs.  A whole step
+// is one asm statement: with the select left to the compiler it is v_mov_b32_dpp + v_cndmask_b32_e64 on an SGPR pair, 11 per slot.
+__device__ __forceinline__ void load8(const float *p, float *v);
+#define ASDR_BQ_SLOT(YJ, NJ, XA, XB, YA, YB) \
+  "v_mul_f32 %[" YJ "], %[b1], %[" XA "]\n\t" \
+  "v_mul_f32 %[t1], %[b2], %[" XB "]\n\t" \
+  "v_mul_f32 %[t2], %[a1], %[" YA "]\n\t" \
+  "v_mul_f32 %[t3], %[a2], %[" YB "]\n\t" \
+  "v_cndmask_b32_dpp %[" XB "], %[" YA "], %[" NJ "], vcc row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_mul_f32 %[t0], %[b0], %[" XB "]\n\t" \
+  "v_add_f32 %[t0], %[t0], %[" YJ "]\n\t" \
+  "v_add_f32 %[t0], %[t0], %[t1]\n\t" \
+  "v_add_f32 %[t0], %[t0], %[t2]\n\t" \
+  "v_add_f32 %[" YJ "], %[t0], %[t3]\n\t"
+__device__ __forceinline__ void biquad_pipe_skew1(float *row, bool on, int st, const float *cf, float *sv) {
+  const float b0 = cf[0], b1 = cf[1], b2 = cf[2], a1 = cf[3], a2 = cf[4];
+  float x1 = sv[0], x2 = sv[1], y1 = sv[2], y2 = sv[3];
+  float xn[8], yp[8];   // stage 0's chunk of this step; the previous step's outputs (stage 3: samples 8c - 11 .. 8c - 4)
+  load8(row, xn);
+  const bool s0 = (st == 0), wr = on && (st == 3);
+  const unsigned long long s0m = __ballot(s0);   // EXEC is full here
+  // one slot in plain C++ (the fill and drain slots, and the rest of step 0)
+  auto slot = [&](auto edge_tag, const int t, const float xin) -> float {
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    const float d = dpp_row_shr1(y1);
+    const float x = s0 ? xin : d;
+    float acc = b0 * x; acc += b1 * x1; acc += b2 * x2; acc += a1 * y1; acc += a2 * y2;
+    if constexpr (EDGE) {   // an idle stage keeps its state: four selects (as a branch the compiler sinks the slot's arithmetic and its LDS read into it)
+      const int n = t - st;
+      const bool act = (n >= 0 && n < ASDR_N);
+      asm volatile("" : "+v"(acc));
+      x2 = act ? x1 : x2; x1 = act ? x : x1; y2 = act ? y1 : y2; y1 = act ? acc : y1;
+    } else { x2 = x1; x1 = x; y2 = y1; y1 = acc; }
+    return acc;
+  };
+  {   // step 0: slots 0..2 fill the pipeline
+    float nx[8];
+    load8(row + 8, nx);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) yp[j] = slot(std::true_type{}, j, xn[j]);
+#pragma unroll
+    for (int j = 3; j < 8; ++j) yp[j] = slot(std::false_type{}, j, xn[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xn[j] = nx[j];
+  }
+  auto step = [&](auto pf_tag, const int c) {   // steps 1..15: every stage has a sample in every slot
+    constexpr bool PF = decltype(pf_tag)::value;
+    float nx[8], y[8], t0, t1, t2, t3;
+    if constexpr (PF) load8(row + 8 * (c + 1), nx);   // the next chunk for stage 0
+    asm("s_mov_b64 vcc, %[m]\n\t"
+        ASDR_BQ_SLOT("y0", "n0", "xa", "xb", "p1", "p2")
+        ASDR_BQ_SLOT("y1", "n1", "xb", "xa", "y0", "p1")
+        ASDR_BQ_SLOT("y2", "n2", "xa", "xb", "y1", "y0")
+        ASDR_BQ_SLOT("y3", "n3", "xb", "xa", "y2", "y1")
+        ASDR_BQ_SLOT("y4", "n4", "xa", "xb", "y3", "y2")
+        ASDR_BQ_SLOT("y5", "n5", "xb", "xa", "y4", "y3")
+        ASDR_BQ_SLOT("y6", "n6", "xa", "xb", "y5", "y4")
+        ASDR_BQ_SLOT("y7", "n7", "xb", "xa", "y6", "y5")
+        : [y0] "=&v"(y[0]), [y1] "=&v"(y[1]), [y2] "=&v"(y[2]), [y3] "=&v"(y[3]), [y4] "=&v"(y[4]), [y5] "=&v"(y[5]), [y6] "=&v"(y[6]), [y7] "=&v"(y[7]),
+          [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [xa] "+v"(x1), [xb] "+v"(x2)
+        : [n0] "v"(xn[0]), [n1] "v"(xn[1]), [n2] "v"(xn[2]), [n3] "v"(xn[3]), [n4] "v"(xn[4]), [n5] "v"(xn[5]), [n6] "v"(xn[6]), [n7] "v"(xn[7]),
+          [b0] "v"(b0), [b1] "v"(b1), [b2] "v"(b2), [a1] "v"(a1), [a2] "v"(a2), [p1] "v"(y1), [p2] "v"(y2), [m] "s"(s0m)
+        : "vcc");
+    y1 = y[7]; y2 = y[6];   // (x1 / x2 are back in their registers after an even number of slots)
+    if (wr) {
+      float4 *const o = reinterpret_cast<float4 *>(row + 8 * (c - 1));
+      o[0] = make_float4(yp[3], yp[4], yp[5], yp[6]); o[1] = make_float4(yp[7], y[0], y[1], y[2]);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { yp[j] = y[j]; if constexpr (PF) xn[j] = nx[j]; }
+  };
+#pragma unroll 1
+  for (int c = 1; c < 15; c += 2) { step(std::true_type{}, c); step(std::true_type{}, c + 1); }
+  step(std::false_type{}, 15);
+  {   // slots 128..130 drain the pipeline; the last chunk goes out
+    float y[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) y[j] = slot(std::true_type{}, ASDR_N + j, 0.0f);
+    if (wr) {
+      float4 *const o = reinterpret_cast<float4 *>(row + ASDR_N - 8);
+      o[0] = make_float4(yp[3], yp[4], yp[5], yp[6]); o[1] = make_float4(yp[7], y[0], y[1], y[2]);
+    }
+  }
+  sv[0] = x1; sv[1] = x2; sv[2] = y1; sv[3] = y2;
+}
+#undef ASDR_BQ_SLOT
+// the pipeline form of a kernel kind (PK: packed products, SKEW1: one sample of skew; never both)
+template <bool PK, bool SKEW1>
+__device__ __forceinline__ void biquad_run(float *row, bool on, int st, const float *cf, float *sv) {
+  if constexpr (SKEW1) biquad_pipe_skew1(row, on, st, cf, sv); else biquad_pipe<PK>(row, on, st, cf, sv);
 }
 
 __device__ __forceinline__ void load16(const float *p, float *v) {
@@ -1138,6 +1242,11 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
   // biquad pipelines with packed products (biquad_pipe<true>), by instantiation: bit 0 = the ALS kinds, 1 = the plain kinds, 2 = the SAM roles, 3 = the block pipeline
   constexpr bool PIPE_PK = ((ASDR_PIPE_PK_MASK & 1) && HAS_ALS) || ((ASDR_PIPE_PK_MASK & 2) && !HAS_ALS && !HAS_SAM && ROLE == 0) ||
                            ((ASDR_PIPE_PK_MASK & 4) && (HAS_SAM || ROLE > 3)) || ((ASDR_PIPE_PK_MASK & 8) && STREAM);
+  // AUDIO cascades with one sample of stage skew (biquad_pipe_skew1), same bits; the block pipeline keeps the chunked packed form, and so does the
+  // 16-waves-per-CU kernel (with the routine: two VGPR spills at its budget of 128 registers)
+  constexpr bool PIPE_SKEW1 = !STREAM && !C16 && (((ASDR_PIPE_SKEW1_MASK & 1) && HAS_ALS) || ((ASDR_PIPE_SKEW1_MASK & 2) && !HAS_ALS && !HAS_SAM && ROLE == 0) ||
+                                          ((ASDR_PIPE_SKEW1_MASK & 4) && (HAS_SAM || ROLE > 3)));
+  static_assert(!(PIPE_SKEW1 && (PIPE_PK || ASDR_PIPE_BANK_SELECT)), "the one-sample skew has no packed form and hands over by row_shr:1");
   if (ROLE == 0 && a.run_if != nullptr && *a.run_if == 0u) return;   // the pipeline's fallback launch: nothing to do unless the pipeline gave up
   // MW (round 5): the plain chain in workgroups of FOUR waves = 32 channels that stop wasting lanes on the phases that use a fraction of
   // a wave: the audio cascade (4 lanes per channel: 32 of 64 busy in a wave of its own) runs for 16 channels per wave on TWO of the
@@ -1999,7 +2108,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       float sv[4];
       if (HAS_ALS && !ALS_FULL_OPT && !if_pre) load_if_rows();
       sv[0] = if_s4.x; sv[1] = if_s4.y; sv[2] = if_s4.z; sv[3] = if_s4.w;
-      biquad_pipe<PIPE_PK>(Lp + (iq ? W1 : W0), true, st, if_cf, sv);
+      biquad_pipe<PIPE_PK>(Lp + (iq ? W1 : W0), true, st, if_cf, sv);   // (chunked in every kind: with one sample of skew HERE the workgroup's slowest wave got slower, profiles/README.md)
       *reinterpret_cast<float4 *>(&Sp->if_state[iq][4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
       if (ROLE == 1 && ASDR_STREAM_R1_CARRY) {
         r1_if_s4 = make_float4(sv[0], sv[1], sv[2], sv[3]);
@@ -2575,7 +2684,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
           const int st = pl_st;
           float sv[4];
           sv[0] = af_s4.x; sv[1] = af_s4.y; sv[2] = af_s4.z; sv[3] = af_s4.w;
-          biquad_pipe<PIPE_PK>(lds_wg + (16 * (mw_rel - 1) + mw_casc) * STRIDE + W0, true, st, af_cf, sv);
+          biquad_run<PIPE_PK, PIPE_SKEW1>(lds_wg + (16 * (mw_rel - 1) + mw_casc) * STRIDE + W0, true, st, af_cf, sv);
           *reinterpret_cast<float4 *>(&mw_af_S->af_state[4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
           if (ASDR_MW_PRIO) __builtin_amdgcn_s_setprio(0);
         }
@@ -2590,7 +2699,7 @@ __device__ __forceinline__ void asdr_update_body(const UpdateArgs &a, float *lds
       float sv[4];
       sv[0] = af_s4.x; sv[1] = af_s4.y; sv[2] = af_s4.z; sv[3] = af_s4.w;
       ChanSmall *const Saf = Spa;   // (by all lanes)
-      biquad_pipe<PIPE_PK>(Lpa + W0, on, st, af_cf, sv);
+      biquad_run<PIPE_PK, PIPE_SKEW1>(Lpa + W0, on, st, af_cf, sv);
       if (on) *reinterpret_cast<float4 *>(&Saf->af_state[4 * st]) = make_float4(sv[0], sv[1], sv[2], sv[3]);
       WAVE_SYNC();
     }
