@@ -16,5 +16,7 @@ from .tuner import (IQ_CORRECTION_DTYPE, IQ_IDENTITY, IQ_STATS_DTYPE, TUNER_EXPO
                     design_channel_filter, estimate_iq_correction, fastconv_ratio, rate_ratio, spectrum_frequencies,
                     suggest_decimation, suggest_fft_decimation, tuner_channel_field, tuner_channel_record_fields)
 from .gate import GATE_EXPORTS, GATE_STATE_DTYPE, GATE_TILE, AudioGate, energy_from_dbfs  # noqa: E402
+from .resample import (RESAMPLE_DEFAULT_RATES, RESAMPLE_EXPORTS, RESAMPLE_FS_IN, RESAMPLE_STATE_SAMPLES,  # noqa: E402
+                       AudioResampler)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

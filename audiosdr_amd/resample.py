@@ -1,0 +1,168 @@
+"""ctypes mirror of include/asdr_resample.h: the audio resampler (the receivers' 44.1 kHz int16 audio rows at a decoder's rate such
+as 12 kHz, for every channel or for the channels a gate delivered).  Same rules as binding.py: the work happens in libasdr_hip.so
+on the GPU; there is no CPU fallback (tests/resample_ref.py is the independent numpy statement the tests compare with)."""
+import ctypes as C
+
+import numpy as np
+
+from .binding import AsdrError, load_library
+
+RESAMPLE_EXPORTS = ["asdr_resampler_create", "asdr_resampler_create_custom", "asdr_resampler_destroy", "asdr_resampler_n_channels",
+                    "asdr_resampler_up", "asdr_resampler_down", "asdr_resampler_taps_per_phase", "asdr_resampler_get_taps",
+                    "asdr_resampler_delay", "asdr_resampler_set_filter", "asdr_resampler_position", "asdr_resampler_output_position",
+                    "asdr_resampler_out_samples", "asdr_resampler_set_position", "asdr_resampler_update_device",
+                    "asdr_resampler_read_state", "asdr_resampler_write_state", "asdr_resampler_reset", "asdr_resampler_synchronize"]
+
+RESAMPLE_FS_IN = 44100
+RESAMPLE_STATE_SAMPLES = 256     # int16 per channel record (ASDR_RESAMPLE_STATE_SAMPLES)
+RESAMPLE_DEFAULT_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000)   # the rates of the header's table
+
+_typed = False
+
+
+def _lib():
+    global _typed
+    L = load_library()
+    if _typed:
+        return L
+    vp, i, lg, ll = C.c_void_p, C.c_int, C.c_long, C.c_longlong
+    ip = C.POINTER(C.c_int)
+    L.asdr_resampler_create.argtypes = [i, i, i]; L.asdr_resampler_create.restype = vp
+    L.asdr_resampler_create_custom.argtypes = [i, i, i, i, vp, i, i]; L.asdr_resampler_create_custom.restype = vp
+    L.asdr_resampler_destroy.argtypes = [vp]; L.asdr_resampler_destroy.restype = None
+    for n in ("n_channels", "up", "down", "taps_per_phase", "reset", "synchronize"):
+        getattr(L, "asdr_resampler_" + n).argtypes = [vp]; getattr(L, "asdr_resampler_" + n).restype = i
+    L.asdr_resampler_get_taps.argtypes = [vp, vp, ip]; L.asdr_resampler_get_taps.restype = i
+    L.asdr_resampler_delay.argtypes = [vp]; L.asdr_resampler_delay.restype = C.c_double
+    L.asdr_resampler_set_filter.argtypes = [vp, i, vp, i]; L.asdr_resampler_set_filter.restype = i
+    L.asdr_resampler_position.argtypes = [vp]; L.asdr_resampler_position.restype = ll
+    L.asdr_resampler_output_position.argtypes = [vp]; L.asdr_resampler_output_position.restype = ll
+    L.asdr_resampler_out_samples.argtypes = [vp, i]; L.asdr_resampler_out_samples.restype = lg
+    L.asdr_resampler_set_position.argtypes = [vp, ll]; L.asdr_resampler_set_position.restype = i
+    L.asdr_resampler_update_device.argtypes = [vp, vp, lg, i, vp, lg, vp, vp, i, vp]; L.asdr_resampler_update_device.restype = lg
+    L.asdr_resampler_read_state.argtypes = [vp, vp]; L.asdr_resampler_read_state.restype = i
+    L.asdr_resampler_write_state.argtypes = [vp, ip, i, vp]; L.asdr_resampler_write_state.restype = i
+    _typed = True
+    return L
+
+
+def _taps_array(taps, up):
+    t = np.ascontiguousarray(taps, dtype=np.int64).reshape(-1)
+    if t.size == 0 or (int(up) >= 1 and t.size % int(up)) or t.min() < -32768 or t.max() > 32767:
+        raise AsdrError("the taps must be int16, up * taps_per_phase of them")
+    return t.astype(np.int16)
+
+
+class AudioResampler:
+    """Resampler of n_channels receivers' audio rows from 44.1 kHz to fs_out (include/asdr_resample.h).  Either fs_out (the default
+    filter of that rate) or up, down, taps [up * K] as h[k * up + phi] and shift (a custom filter).  device = NO_DEVICE (-1) gives
+    the control plane and the state records only."""
+
+    def __init__(self, n_channels, fs_out=12000, device=0, up=None, down=None, taps=None, shift=15):
+        self._L = _lib()
+        if taps is None:
+            if up is not None or down is not None:
+                raise AsdrError("AudioResampler: up / down come with custom taps")
+            self._h = self._L.asdr_resampler_create(int(n_channels), int(fs_out), int(device))
+            what = "asdr_resampler_create"
+        else:
+            t = _taps_array(taps, up)
+            self._h = self._L.asdr_resampler_create_custom(int(n_channels), int(up), int(down), t.size // max(int(up), 1), t.ctypes.data_as(C.c_void_p),
+                                                           int(shift), int(device))
+            what = "asdr_resampler_create_custom"
+        if not self._h:
+            raise AsdrError("%s failed: %s" % (what, self._L.asdr_last_error().decode()))
+        self.n_channels = int(n_channels)
+        self.up, self.down = int(self._L.asdr_resampler_up(self._h)), int(self._L.asdr_resampler_down(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.asdr_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise AsdrError(self._L.asdr_last_error().decode())
+        return rc
+
+    # the rate and the filter
+    @property
+    def fs_out(self):
+        """44100 up / down, as a float (exact for the default rates)."""
+        return RESAMPLE_FS_IN * self.up / self.down
+
+    def taps_per_phase(self):
+        return int(self._chk(self._L.asdr_resampler_taps_per_phase(self._h)))
+
+    def get_taps(self):
+        """(taps int16 [up * K] as h[k * up + phi], shift)."""
+        t = np.zeros(self.up * self.taps_per_phase(), dtype=np.int16)
+        s = C.c_int(0)
+        self._chk(self._L.asdr_resampler_get_taps(self._h, t.ctypes.data_as(C.c_void_p), C.byref(s)))
+        return t, int(s.value)
+
+    def delay(self):
+        """The causal filter's delay in input samples, (up * K - 1) / (2 up)."""
+        return float(self._L.asdr_resampler_delay(self._h))
+
+    def set_filter(self, taps, shift=15):
+        """Swaps the filter (same up and down); the records and the position stay."""
+        t = _taps_array(taps, self.up)
+        self._chk(self._L.asdr_resampler_set_filter(self._h, t.size // self.up, t.ctypes.data_as(C.c_void_p), int(shift)))
+
+    # position
+    def position(self):
+        return int(self._L.asdr_resampler_position(self._h))
+
+    def output_position(self):
+        return int(self._L.asdr_resampler_output_position(self._h))
+
+    def out_samples(self, n_blocks):
+        """What the next update_device of n_blocks blocks returns."""
+        return int(self._chk(self._L.asdr_resampler_out_samples(self._h, int(n_blocks))))
+
+    def set_position(self, n):
+        if not -2**63 <= int(n) < 2**63:
+            raise AsdrError("resampler: position must be in 0..2^50")
+        self._chk(self._L.asdr_resampler_set_position(self._h, int(n)))
+
+    # the pass
+    def update_device(self, ptr, n_blocks, out_ptr, out_stride, stride_blocks=None, index_ptr=0, count_ptr=0, capacity_rows=0, stream=0):
+        """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle as int).  ptr: int16 rows
+        [n_channels][stride_blocks][128] (stride_blocks defaults to n_blocks); out_ptr: int16 rows [..][out_stride].  With index_ptr /
+        count_ptr (device int32 [..] and int32, e.g. a gate's index_tensor().data_ptr() / count_tensor().data_ptr()) row i is channel
+        index[i] for i < min(count, capacity_rows); otherwise row c is channel c.  Returns the per-row output count."""
+        stride = int(n_blocks) if stride_blocks is None else int(stride_blocks)
+        return int(self._chk(self._L.asdr_resampler_update_device(self._h, C.c_void_p(ptr or None), stride, int(n_blocks), C.c_void_p(out_ptr or None),
+                                                                  int(out_stride), C.c_void_p(index_ptr or None), C.c_void_p(count_ptr or None),
+                                                                  int(capacity_rows), C.c_void_p(stream or None))))
+
+    # state
+    def read_state(self):
+        """int16 [n_channels, 256]: every channel's last 256 input samples, oldest first; waits for the resampler's work."""
+        st = np.zeros((self.n_channels, RESAMPLE_STATE_SAMPLES), dtype=np.int16)
+        self._chk(self._L.asdr_resampler_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
+        return st
+
+    def write_state(self, records, channels=None):
+        """Writes int16 [k, 256] records into `channels` (default 0 .. k - 1); every channel is checked before one is written."""
+        rec = np.ascontiguousarray(records, dtype=np.int16).reshape(-1, RESAMPLE_STATE_SAMPLES)
+        chp = None
+        if channels is not None:
+            ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+            if ch.size != rec.shape[0]:
+                raise AsdrError("write_state: %d records for %d channels" % (rec.shape[0], ch.size))
+            chp = ch.ctypes.data_as(C.POINTER(C.c_int))
+        self._chk(self._L.asdr_resampler_write_state(self._h, chp, int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))
+
+    def reset(self):
+        self._chk(self._L.asdr_resampler_reset(self._h))
+
+    def synchronize(self):
+        self._chk(self._L.asdr_resampler_synchronize(self._h))

@@ -222,7 +222,8 @@ int asdr_synchronize(asdr_batch_t *b);
  * [channel][capacity_blocks*128] at 44.1 kHz, appended to by every asdr_capture_update_device() call, so that a
  * 2-minute WSPR slot (41,344 blocks) ends up as one row per receiver that a decoder can read in place
  * (asdr_capture_device_ptr) or copy out (asdr_capture_read).  The 12 kHz resampling WSPR decoders expect is not
- * part of the reference and is not done here. */
+ * part of the reference and is not done in this path: asdr_resample.h is an after-pass of its own that reads these rows
+ * (stride_blocks = capacity) and writes them at 8, 12, 16 kHz ... on the device. */
 int asdr_capture_open(asdr_batch_t *b, long capacity_blocks);       /* (re)allocates, position = 0 */
 int asdr_capture_close(asdr_batch_t *b);
 long asdr_capture_capacity(const asdr_batch_t *b);                  /* blocks per channel row */
