@@ -18,5 +18,7 @@ from .tuner import (IQ_CORRECTION_DTYPE, IQ_IDENTITY, IQ_STATS_DTYPE, TUNER_EXPO
 from .gate import GATE_EXPORTS, GATE_STATE_DTYPE, GATE_TILE, AudioGate, energy_from_dbfs  # noqa: E402
 from .resample import (RESAMPLE_DEFAULT_RATES, RESAMPLE_EXPORTS, RESAMPLE_FS_IN, RESAMPLE_STATE_SAMPLES,  # noqa: E402
                        AudioResampler)
+from .codec import (CODEC_EXPORTS, CODEC_KINDS, CODEC_MAX_SAMPLES, CODEC_STATE_DTYPE, AudioCodec, codec_decode,  # noqa: E402
+                    codec_row_bytes)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -1,0 +1,303 @@
+// asdr_codec_host.cpp -- host side + C ABI (include/asdr_codec.h) of the audio codec.  The state records live on the device only
+// (an ASDR_NO_DEVICE codec keeps them on the host instead); deliver's packet buffer grows on demand and is kept.  The decoder is
+// plain host code: a listener's side of the packet rows, and what the tests decode the device's bytes with.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "asdr_codec_device.h"
+
+int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
+
+static_assert(sizeof(asdr_codec_state_t) == 4, "asdr_codec_state_t is a 4-byte record");
+
+struct asdr_codec {
+  int n = 0, kind = 0, device = ASDR_NO_DEVICE;
+  std::vector<asdr_codec_state_t> host_state;   // ASDR_NO_DEVICE only
+  hipStream_t stream = nullptr, last_stream = nullptr;
+  hipEvent_t ev = nullptr;
+  bool ev_valid = false;
+  asdr_codec_state_t *d_state = nullptr;
+  void *d_rows = nullptr;
+  size_t rows_cap = 0;
+};
+
+namespace {
+int fail(const std::string &m) { return asdr_internal_fail(m); }
+#define HIPCHK(expr)                                                                                   \
+  do {                                                                                                 \
+    hipError_t e_ = (expr);                                                                            \
+    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
+  } while (0)
+
+const char *kNoDevice = "control-plane-only codec (ASDR_NO_DEVICE): the signal path needs a HIP device";
+const uint16_t kStep[ASDR_CODEC_STEPS] = {ASDR_CODEC_STEP_TABLE};
+
+bool kind_ok(int kind) { return kind == ASDR_CODEC_ULAW || kind == ASDR_CODEC_ALAW || kind == ASDR_CODEC_ADPCM; }
+long row_bytes(int kind, long n) { return kind == ASDR_CODEC_ADPCM ? ASDR_CODEC_ADPCM_HEADER_BYTES + (n + 1) / 2 : n; }
+long round4(long b) { return (b + 3) & ~3L; }
+
+// waits for the codec's work (nothing for ASDR_NO_DEVICE)
+int quiesce(asdr_codec_t *c) {
+  if (c->device == ASDR_NO_DEVICE) return 0;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->ev_valid) HIPCHK(hipEventSynchronize(c->ev));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+
+// what encode_device and deliver check alike, before they ask for a device: an ASDR_NO_DEVICE codec refuses a bad argument as
+// any other does.  Gives the rows of the launch
+int check_input(const asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long n_samples, const int32_t *dIndex,
+                const int32_t *dCount, int capacity_rows, int *grid_rows) {
+  if (!dRows) return fail("null device pointer");
+  if (n_samples < 1 || n_samples > ASDR_CODEC_MAX_SAMPLES) return fail("n_samples must be in 1..8388480");
+  if (row_stride_samples < n_samples) return fail("row stride shorter than n_samples");
+  if (row_stride_samples > (1L << 40)) return fail("row stride too large");
+  if (((uintptr_t)dRows & 1u) != 0) return fail("the input rows must be 2-byte aligned");
+  if (dIndex && !dCount) return fail("an index needs a count");
+  if (dIndex && capacity_rows < 0) return fail("capacity_rows is negative");
+  *grid_rows = dIndex ? std::min(capacity_rows, c->n) : c->n;
+  return 0;
+}
+
+// the bytes of the input that a launch may read
+size_t input_bytes(const asdr_codec_t *c, long row_stride_samples, long n_samples, const int32_t *dIndex, int rows_compact, int grid_rows) {
+  const int in_rows = (dIndex && rows_compact) ? grid_rows : c->n;
+  return in_rows > 0 ? ((size_t)(in_rows - 1) * row_stride_samples + n_samples) * sizeof(int16_t) : 0;
+}
+
+int launch(asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long n_samples, int rows_compact, uint8_t *dOut,
+           long out_stride_bytes, const int32_t *dIndex, const int32_t *dCount, int capacity_rows, int grid_rows, hipStream_t stream) {
+  CodecArgs a;
+  a.rows = dRows; a.row_stride = row_stride_samples;
+  a.out = dOut; a.out_stride = out_stride_bytes;
+  a.index = dIndex; a.count = dCount;
+  a.state = c->d_state;
+  a.n_channels = c->n; a.n_samples = (int32_t)n_samples; a.grid_rows = grid_rows; a.capacity_rows = dIndex ? capacity_rows : c->n;
+  a.rows_compact = rows_compact ? 1 : 0; a.kind = c->kind;
+  a.aligned = (((uintptr_t)dRows & 15u) == 0 && row_stride_samples % 8 == 0) ? 1 : 0;
+  a.pieces = (int32_t)((n_samples + 7) / 8);
+  if (c->kind != ASDR_CODEC_ADPCM && (unsigned long long)std::max(grid_rows, 0) * (unsigned long long)a.pieces >= (1ULL << 32))
+    return fail("codec: the call is too large for one launch; split it");
+  HIPCHK(hipSetDevice(c->device));
+  if (c->ev_valid && stream != c->last_stream) HIPCHK(hipStreamWaitEvent(stream, c->ev, 0));
+  if ((c->kind == ASDR_CODEC_ADPCM ? asdr_launch_codec_adpcm(&a, stream) : asdr_launch_codec_g711(&a, stream)) != 0)
+    return fail("codec kernel launch failed");
+  HIPCHK(hipEventRecord(c->ev, stream));
+  c->ev_valid = true; c->last_stream = stream;
+  return 0;
+}
+
+int check_record(const asdr_codec_t *c, int k, const asdr_codec_state_t &s) {
+  if (s.step_index > ASDR_CODEC_MAX_STEP_INDEX) return fail("record " + std::to_string(k) + ": step_index must be in 0..88");
+  if (s.reserved != 0) return fail("record " + std::to_string(k) + ": reserved byte must be 0");
+  if (c->kind != ASDR_CODEC_ADPCM && (s.predictor != 0 || s.step_index != 0))
+    return fail("record " + std::to_string(k) + ": a G.711 codec's records are all zero");
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+asdr_codec_t *asdr_codec_create(int n_channels, int kind, int device) {
+  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (!kind_ok(kind)) { fail("codec: kind must be ASDR_CODEC_ULAW (1), ASDR_CODEC_ALAW (2) or ASDR_CODEC_ADPCM (3)"); return nullptr; }
+  asdr_codec *c = new asdr_codec;
+  c->n = n_channels; c->kind = kind; c->device = device;
+  if (device == ASDR_NO_DEVICE) {
+    c->host_state.assign(n_channels, asdr_codec_state_t{});
+    return c;
+  }
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete c; return nullptr; }
+  if (device < 0 || device >= count) { fail("bad device index"); delete c; return nullptr; }
+  const size_t bytes = (size_t)n_channels * sizeof(asdr_codec_state_t);
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev) != hipSuccess ||
+      hipMalloc(&c->d_state, bytes) != hipSuccess || hipMemset(c->d_state, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    fail("codec: device allocation failed");
+    asdr_codec_destroy(c);
+    return nullptr;
+  }
+  return c;
+}
+
+void asdr_codec_destroy(asdr_codec_t *c) {
+  if (!c) return;
+  if (c->device != ASDR_NO_DEVICE) {
+    hipSetDevice(c->device);
+    if (c->ev_valid) hipEventSynchronize(c->ev);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    for (void *p : {(void *)c->d_state, c->d_rows})
+      if (p) hipFree(p);
+    if (c->ev) hipEventDestroy(c->ev);
+    if (c->stream) hipStreamDestroy(c->stream);
+  }
+  delete c;
+}
+
+int asdr_codec_n_channels(const asdr_codec_t *c) { return c ? c->n : fail("null codec"); }
+int asdr_codec_kind(const asdr_codec_t *c) { return c ? c->kind : fail("null codec"); }
+
+long asdr_codec_row_bytes(int kind, long n_samples) {
+  if (!kind_ok(kind)) return fail("codec: kind must be ASDR_CODEC_ULAW (1), ASDR_CODEC_ALAW (2) or ASDR_CODEC_ADPCM (3)");
+  if (n_samples < 1 || n_samples > ASDR_CODEC_MAX_SAMPLES) return fail("n_samples must be in 1..8388480");
+  return row_bytes(kind, n_samples);
+}
+
+long asdr_codec_encode_device(asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long n_samples, int rows_compact, uint8_t *dOut,
+                              long out_stride_bytes, const int32_t *dIndex, const int32_t *dCount, int capacity_rows, void *stream_) {
+  if (!c) return fail("null codec");
+  int grid_rows = 0;
+  if (check_input(c, dRows, row_stride_samples, n_samples, dIndex, dCount, capacity_rows, &grid_rows) != 0) return -1;
+  if (!dOut) return fail("null device pointer");
+  const long bytes = row_bytes(c->kind, n_samples), padded = round4(bytes);
+  if (((uintptr_t)dOut & 3u) != 0) return fail("the output rows must be 4-byte aligned");
+  if (out_stride_bytes % 4 != 0) return fail("out_stride_bytes must be a multiple of 4");
+  if (out_stride_bytes < padded) return fail("out_stride_bytes shorter than the row's bytes rounded up to 4");
+  if (out_stride_bytes > (1L << 40)) return fail("output row stride too large");
+  if (c->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  if (grid_rows > 0) {
+    const size_t out_bytes = (size_t)(grid_rows - 1) * out_stride_bytes + padded;
+    if (overlap((uintptr_t)dRows, input_bytes(c, row_stride_samples, n_samples, dIndex, rows_compact, grid_rows), (uintptr_t)dOut, out_bytes))
+      return fail("output span overlaps the input span");
+  }
+  if (launch(c, dRows, row_stride_samples, n_samples, rows_compact, dOut, out_stride_bytes, dIndex, dCount, capacity_rows, grid_rows,
+             (hipStream_t)stream_) != 0)
+    return -1;
+  return bytes;
+}
+
+long asdr_codec_deliver(asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long n_samples, int rows_compact, int32_t *host_index,
+                        uint8_t *host_rows, const int32_t *dIndex, const int32_t *dCount, int capacity_rows, void *stream_) {
+  if (!c) return fail("null codec");
+  int grid_rows = 0;
+  if (check_input(c, dRows, row_stride_samples, n_samples, dIndex, dCount, capacity_rows, &grid_rows) != 0) return -1;
+  if (grid_rows > 0 && !host_rows) return fail("null host rows");
+  if (c->device == ASDR_NO_DEVICE) return fail(kNoDevice);
+  const long padded = round4(row_bytes(c->kind, n_samples));
+  hipStream_t stream = (hipStream_t)stream_;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t need = (size_t)grid_rows * padded;
+  if (need > c->rows_cap) {                                   // growing waits for the work that may still use the old buffer
+    if (quiesce(c) != 0) return -1;
+    if (c->d_rows) HIPCHK(hipFree(c->d_rows));
+    c->d_rows = nullptr; c->rows_cap = 0;
+    HIPCHK(hipMalloc(&c->d_rows, need));
+    c->rows_cap = need;
+  }
+  if (grid_rows > 0) {
+    if (overlap((uintptr_t)dRows, input_bytes(c, row_stride_samples, n_samples, dIndex, rows_compact, grid_rows), (uintptr_t)c->d_rows, need))
+      return fail("internal: packet buffer overlaps the input span");
+    if (launch(c, dRows, row_stride_samples, n_samples, rows_compact, (uint8_t *)c->d_rows, padded, dIndex, dCount, capacity_rows, grid_rows,
+               stream) != 0)
+      return -1;
+  }
+  int32_t count = c->n;
+  if (dIndex) {
+    HIPCHK(hipMemcpyAsync(&count, dCount, sizeof(count), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (count < 0) count = 0;
+  }
+  const int rows = std::min<int32_t>(count, grid_rows);
+  if (rows > 0) {
+    if (host_index) {
+      if (dIndex) HIPCHK(hipMemcpyAsync(host_index, dIndex, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+      else for (int k = 0; k < rows; k++) host_index[k] = k;
+    }
+    HIPCHK(hipMemcpyAsync(host_rows, c->d_rows, (size_t)rows * padded, hipMemcpyDeviceToHost, stream));
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  return count;
+}
+
+int asdr_codec_decode(int kind, const uint8_t *row, long n_samples, int16_t *out) {
+  if (!kind_ok(kind)) return fail("codec: kind must be ASDR_CODEC_ULAW (1), ASDR_CODEC_ALAW (2) or ASDR_CODEC_ADPCM (3)");
+  if (n_samples < 1 || n_samples > ASDR_CODEC_MAX_SAMPLES) return fail("n_samples must be in 1..8388480");
+  if (!row || !out) return fail("null pointer");
+  if (kind == ASDR_CODEC_ULAW) {
+    for (long k = 0; k < n_samples; k++) {
+      const int u = ~row[k] & 0xFF, e = (u >> 4) & 7, q = u & 15;
+      const int t = (((q << 3) + 132) << e) - 132;
+      out[k] = (int16_t)((u & 0x80) ? -t : t);
+    }
+    return 0;
+  }
+  if (kind == ASDR_CODEC_ALAW) {
+    for (long k = 0; k < n_samples; k++) {
+      const int a = row[k] ^ 0x55, e = (a >> 4) & 7, q = a & 15;
+      const int t = e == 0 ? (q << 4) + 8 : ((q << 4) + 0x108) << (e - 1);
+      out[k] = (int16_t)((a & 0x80) ? t : -t);
+    }
+    return 0;
+  }
+  int p = (int16_t)(row[0] | (row[1] << 8)), i = row[2];
+  if (i > ASDR_CODEC_MAX_STEP_INDEX) return fail("codec: the row's step_index must be in 0..88");
+  if (row[3] != 0) return fail("codec: the row's fourth header byte must be 0");
+  for (long k = 0; k < n_samples; k++) {
+    const int nib = (row[ASDR_CODEC_ADPCM_HEADER_BYTES + k / 2] >> (4 * (k & 1))) & 15, c = nib & 7, s = kStep[i];
+    const int v = (s >> 3) + ((c & 4) ? s : 0) + ((c & 2) ? s >> 1 : 0) + ((c & 1) ? s >> 2 : 0);
+    p = std::min(std::max((nib & 8) ? p - v : p + v, -32768), 32767);
+    i = std::min(std::max(i + (c < 4 ? -1 : 2 * (c - 3)), 0), ASDR_CODEC_MAX_STEP_INDEX);
+    out[k] = (int16_t)p;
+  }
+  return 0;
+}
+
+int asdr_codec_read_state(asdr_codec_t *c, asdr_codec_state_t *dst) {
+  if (!c) return fail("null codec");
+  if (!dst) return fail("null destination");
+  const size_t bytes = (size_t)c->n * sizeof(asdr_codec_state_t);
+  if (c->device == ASDR_NO_DEVICE) { std::memcpy(dst, c->host_state.data(), bytes); return 0; }
+  if (quiesce(c) != 0) return -1;
+  HIPCHK(hipMemcpy(dst, c->d_state, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int asdr_codec_write_state(asdr_codec_t *c, const int *channels, int n, const asdr_codec_state_t *src) {
+  if (!c) return fail("null codec");
+  if (n < 0) return fail("negative record count");
+  if (n == 0) return 0;
+  if (!src) return fail("null source");
+  if (!channels && n > c->n) return fail("more records than channels");
+  for (int k = 0; k < n; k++) {
+    const int ch = channels ? channels[k] : k;
+    if (ch < 0 || ch >= c->n) return fail("record " + std::to_string(k) + ": bad channel");
+    if (check_record(c, k, src[k]) != 0) return -1;
+  }
+  if (quiesce(c) != 0) return -1;
+  if (!channels && c->device != ASDR_NO_DEVICE) {
+    HIPCHK(hipMemcpy(c->d_state, src, (size_t)n * sizeof(asdr_codec_state_t), hipMemcpyHostToDevice));
+    return 0;
+  }
+  for (int k = 0; k < n; k++) {
+    const int ch = channels ? channels[k] : k;
+    if (c->device == ASDR_NO_DEVICE) c->host_state[ch] = src[k];
+    else HIPCHK(hipMemcpy(c->d_state + ch, src + k, sizeof(asdr_codec_state_t), hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+int asdr_codec_reset(asdr_codec_t *c) {
+  if (!c) return fail("null codec");
+  if (c->device == ASDR_NO_DEVICE) {
+    c->host_state.assign(c->n, asdr_codec_state_t{});
+    return 0;
+  }
+  if (quiesce(c) != 0) return -1;
+  HIPCHK(hipMemsetAsync(c->d_state, 0, (size_t)c->n * sizeof(asdr_codec_state_t), c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int asdr_codec_synchronize(asdr_codec_t *c) {
+  if (!c) return fail("null codec");
+  return quiesce(c);
+}
+
+}  // extern "C"
