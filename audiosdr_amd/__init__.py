@@ -20,5 +20,7 @@ from .resample import (RESAMPLE_DEFAULT_RATES, RESAMPLE_EXPORTS, RESAMPLE_FS_IN,
                        AudioResampler)
 from .codec import (CODEC_EXPORTS, CODEC_KINDS, CODEC_MAX_SAMPLES, CODEC_STATE_DTYPE, AudioCodec, codec_decode,  # noqa: E402
                     codec_row_bytes)
+from .spectrogram import (SPECTROGRAM_EXPORTS, SPECTROGRAM_KINDS, SPECTROGRAM_MAX_SAMPLES, SPECTROGRAM_SIZES,  # noqa: E402
+                          SPECTROGRAM_WINDOWS, AudioSpectrogram)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
