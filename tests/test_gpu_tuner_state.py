@@ -2,7 +2,7 @@
 its channel records, or a channel moved between banks in lockstep, writes as its next output what the uninterrupted bank would have
 written -- tolerance 0 everywhere.  Expected values: the uninterrupted numpy restatements (tests/tuner_ref.py, tuner_rate_ref.py) for
 direct-form and rate banks; for fast-convolution banks an uninterrupted GPU bank given the same calls, which runs none of the new
-code (its kernels are held by the other suites; the monitors use no float atomics, so equality is exact there too)."""
+code (test_gpu_tuner_full.py holds the loaded bank to float64; the monitors use no float atomics, so equality is exact there too)."""
 import numpy as np
 import pytest
 
