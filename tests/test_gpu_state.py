@@ -361,3 +361,43 @@ def test_rejected_import_leaves_a_running_batch_alone(gpu, ao):
     assert np.array_equal(src.export_state(), rec)
     _run_source(src, ref, 6, 10)
     hip.free_all(); src.close()
+
+
+# ---- 15: the blanker's carried mask, all nine pairs of ring phases ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["dense-1.2", "pairs"])
+def test_blanker_carried_mask_across_ring_phases(gpu, ao, name):
+    """Banks on the designed blanker inputs of tests/blanker_scenarios.py (heavy-tailed noise: detections in every block; pairs of impulses
+    whose windows merge, touch or leave a gap), cut after three block counts with ring phases 0, 1 and 2 at which every receiver's carried
+    mask codes are not all ones (tests/test_blanker_scenarios.py shows it), each into destinations that have run 0, 1 and 2 blocks: the
+    nine pairs of source and destination phase.  Audio and nb_detected of the next five blocks against the uninterrupted oracles; the
+    source runs on to the end against them too."""
+    import blanker_scenarios as B
+    import four_wave_scenarios as F
+    from test_gpu_blanker import FORMS, _case
+    recipe = {r.name: r for r in B.all_recipes()}[name]
+    sc, run = _case(ao, recipe, FORMS["one"])
+    I, Q = recipe.rows()
+    n, T, want = sc.n, recipe.T, run.want()
+    assert n == recipe.U and {k % 3 for k in B.STATE_CUTS[name]} == {0, 1, 2}
+    nd = n + 3
+    dest_of = [(c + 2) % nd for c in range(n)]
+    src = gpu.AudioSDRBatch(n)
+    F.apply_to_batch(src, sc.setup, n)
+    pos = 0
+    for cut in B.STATE_CUTS[name]:
+        assert np.array_equal(src.update(I[:, pos:cut], Q[:, pos:cut]), want[:, pos:cut]), "source blocks %d..%d" % (pos, cut - 1)
+        pos = cut
+        rec = src.export_state()
+        for k_dst in (0, 1, 2):
+            d = _destination(gpu, nd, k_dst, seed=cut + k_dst, taps=False)
+            d.import_state(rec, dest_of)
+            for k in range(cut, min(T, cut + 5)):
+                dI = np.zeros((nd, 1, 128), np.int16); dQ = np.zeros((nd, 1, 128), np.int16)
+                dI[dest_of, 0] = I[:, k]; dQ[dest_of, 0] = Q[:, k]
+                got = d.update(dI, dQ)[:, 0]
+                bad = np.argwhere(got[dest_of] != want[:, k])
+                assert bad.size == 0, "cut %d into phase %d, block %d: first at (receiver, sample) %s" % (cut, k_dst, k, bad[0].tolist())
+                assert np.array_equal(d.read_status()["nb_detected"][dest_of], run.nb[:, k]), "cut %d into phase %d: nb_detected after block %d" % (cut, k_dst, k)
+            d.close()
+    assert np.array_equal(src.update(I[:, pos:], Q[:, pos:]), want[:, pos:])
+    src.close()
