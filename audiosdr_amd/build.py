@@ -21,7 +21,7 @@ DEPS = SOURCES + ["asdr_device.h", "asdr_fir.h", "asdr_tables.h", "asdr_front_de
                   os.path.join("..", "..", "include", "asdr_tuner.h"), os.path.join("..", "..", "include", "asdr_gate.h"),
                   "asdr_resample_device.h", os.path.join("..", "..", "include", "asdr_resample.h"),
                   "asdr_codec_device.h", os.path.join("..", "..", "include", "asdr_codec.h"),
-                  "asdr_spectrogram_device.h", os.path.join("..", "..", "include", "asdr_spectrogram.h")]
+                  "asdr_spectrogram_device.h", os.path.join("..", "..", "include", "asdr_spectrogram.h"), "asdr_stage_host.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-fast-math", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value"]

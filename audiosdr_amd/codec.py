@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import AsdrError, load_library
+from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from .binding import AsdrError
 
 CODEC_EXPORTS = ["asdr_codec_create", "asdr_codec_destroy", "asdr_codec_n_channels", "asdr_codec_kind", "asdr_codec_row_bytes",
                  "asdr_codec_encode_device", "asdr_codec_deliver", "asdr_codec_decode", "asdr_codec_read_state",
@@ -17,28 +18,14 @@ assert CODEC_STATE_DTYPE.itemsize == 4
 CODEC_KINDS = {"ulaw": 1, "alaw": 2, "adpcm": 3}     # ASDR_CODEC_ULAW, ASDR_CODEC_ALAW, ASDR_CODEC_ADPCM
 CODEC_MAX_SAMPLES = 8388480                          # per row and call (ASDR_CODEC_MAX_SAMPLES)
 
-_typed = False
+_API = {"create": ([i, i, i], vp), "destroy": ([vp], None), "n_channels": ([vp], i), "kind": ([vp], i), "reset": ([vp], i),
+        "synchronize": ([vp], i), "row_bytes": ([i, lg], lg), "encode_device": ([vp, vp, lg, lg, i, vp, lg, vp, vp, i, vp], lg),
+        "deliver": ([vp, vp, lg, lg, i, vp, vp, vp, vp, i, vp], lg), "decode": ([i, vp, lg, vp], i), "read_state": ([vp, vp], i),
+        "write_state": ([vp, ip, i, vp], i)}
 
 
 def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, lg = C.c_void_p, C.c_int, C.c_long
-    ip = C.POINTER(C.c_int)
-    L.asdr_codec_create.argtypes = [i, i, i]; L.asdr_codec_create.restype = vp
-    L.asdr_codec_destroy.argtypes = [vp]; L.asdr_codec_destroy.restype = None
-    for n in ("n_channels", "kind", "reset", "synchronize"):
-        getattr(L, "asdr_codec_" + n).argtypes = [vp]; getattr(L, "asdr_codec_" + n).restype = i
-    L.asdr_codec_row_bytes.argtypes = [i, lg]; L.asdr_codec_row_bytes.restype = lg
-    L.asdr_codec_encode_device.argtypes = [vp, vp, lg, lg, i, vp, lg, vp, vp, i, vp]; L.asdr_codec_encode_device.restype = lg
-    L.asdr_codec_deliver.argtypes = [vp, vp, lg, lg, i, vp, vp, vp, vp, i, vp]; L.asdr_codec_deliver.restype = lg
-    L.asdr_codec_decode.argtypes = [i, vp, lg, vp]; L.asdr_codec_decode.restype = i
-    L.asdr_codec_read_state.argtypes = [vp, vp]; L.asdr_codec_read_state.restype = i
-    L.asdr_codec_write_state.argtypes = [vp, ip, i, vp]; L.asdr_codec_write_state.restype = i
-    _typed = True
-    return L
+    return typed_library("asdr_codec_", _API)
 
 
 def _kind(kind):
@@ -56,33 +43,16 @@ def _fits_long(*values):
         raise AsdrError("codec: argument out of range")
 
 
-class AudioCodec:
+class AudioCodec(Stage):
     """Encoder of n_channels receivers' int16 audio rows into packet rows of one kind (include/asdr_codec.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
+    _prefix = "asdr_codec_"
 
     def __init__(self, n_channels, kind="adpcm", device=0):
         self._L = _lib()
-        self._h = self._L.asdr_codec_create(int(n_channels), _kind(kind), int(device))
-        if not self._h:
-            raise AsdrError("asdr_codec_create failed: %s" % self._L.asdr_last_error().decode())
+        self._create("asdr_codec_create", self._L.asdr_codec_create(int(n_channels), _kind(kind), int(device)))
         self.n_channels = int(n_channels)
         self.kind = int(self._L.asdr_codec_kind(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.asdr_codec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
 
     def row_bytes(self, n_samples):
         """Bytes of a packet row of n_samples samples: n for the G.711 kinds, 4 + ceil(n / 2) for ADPCM.  A row in a buffer is
@@ -144,19 +114,7 @@ class AudioCodec:
     def write_state(self, records, channels=None):
         """Writes CODEC_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
         rec = np.ascontiguousarray(records, dtype=CODEC_STATE_DTYPE).reshape(-1)
-        chp = None
-        if channels is not None:
-            ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
-            if ch.size != rec.size:
-                raise AsdrError("write_state: %d records for %d channels" % (rec.size, ch.size))
-            chp = ch.ctypes.data_as(C.POINTER(C.c_int))
-        self._chk(self._L.asdr_codec_write_state(self._h, chp, int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def reset(self):
-        self._chk(self._L.asdr_codec_reset(self._h))
-
-    def synchronize(self):
-        self._chk(self._L.asdr_codec_synchronize(self._h))
+        self._chk(self._L.asdr_codec_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
 
 
 def codec_row_bytes(kind, n_samples):

@@ -1,55 +1,29 @@
 // asdr_codec_host.cpp -- host side + C ABI (include/asdr_codec.h) of the audio codec.  The state records live on the device only
 // (an ASDR_NO_DEVICE codec keeps them on the host instead); deliver's packet buffer grows on demand and is kept.  The decoder is
 // plain host code: a listener's side of the packet rows, and what the tests decode the device's bytes with.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <cstring>
-#include <string>
 #include <vector>
 
 #include "asdr_codec_device.h"
-
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
+#include "asdr_stage_host.h"
 
 static_assert(sizeof(asdr_codec_state_t) == 4, "asdr_codec_state_t is a 4-byte record");
 
-struct asdr_codec {
-  int n = 0, kind = 0, device = ASDR_NO_DEVICE;
+struct asdr_codec : StageDev {
+  int kind = 0;
   std::vector<asdr_codec_state_t> host_state;   // ASDR_NO_DEVICE only
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev = nullptr;
-  bool ev_valid = false;
   asdr_codec_state_t *d_state = nullptr;
   void *d_rows = nullptr;
   size_t rows_cap = 0;
 };
 
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 const char *kNoDevice = "control-plane-only codec (ASDR_NO_DEVICE): the signal path needs a HIP device";
 const uint16_t kStep[ASDR_CODEC_STEPS] = {ASDR_CODEC_STEP_TABLE};
 
 bool kind_ok(int kind) { return kind == ASDR_CODEC_ULAW || kind == ASDR_CODEC_ALAW || kind == ASDR_CODEC_ADPCM; }
 long row_bytes(int kind, long n) { return kind == ASDR_CODEC_ADPCM ? ASDR_CODEC_ADPCM_HEADER_BYTES + (n + 1) / 2 : n; }
 long round4(long b) { return (b + 3) & ~3L; }
-
-// waits for the codec's work (nothing for ASDR_NO_DEVICE)
-int quiesce(asdr_codec_t *c) {
-  if (c->device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(c->device));
-  if (c->ev_valid) HIPCHK(hipEventSynchronize(c->ev));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
 
 // what encode_device and deliver check alike, before they ask for a device: an ASDR_NO_DEVICE codec refuses a bad argument as
 // any other does.  Gives the rows of the launch
@@ -85,13 +59,10 @@ int launch(asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long 
   a.pieces = (int32_t)((n_samples + 7) / 8);
   if (c->kind != ASDR_CODEC_ADPCM && (unsigned long long)std::max(grid_rows, 0) * (unsigned long long)a.pieces >= (1ULL << 32))
     return fail("codec: the call is too large for one launch; split it");
-  HIPCHK(hipSetDevice(c->device));
-  if (c->ev_valid && stream != c->last_stream) HIPCHK(hipStreamWaitEvent(stream, c->ev, 0));
+  if (stage_before_launch(*c, stream) != 0) return -1;
   if ((c->kind == ASDR_CODEC_ADPCM ? asdr_launch_codec_adpcm(&a, stream) : asdr_launch_codec_g711(&a, stream)) != 0)
     return fail("codec kernel launch failed");
-  HIPCHK(hipEventRecord(c->ev, stream));
-  c->ev_valid = true; c->last_stream = stream;
-  return 0;
+  return stage_after_launch(*c, stream);
 }
 
 int check_record(const asdr_codec_t *c, int k, const asdr_codec_state_t &s) {
@@ -106,20 +77,17 @@ int check_record(const asdr_codec_t *c, int k, const asdr_codec_state_t &s) {
 extern "C" {
 
 asdr_codec_t *asdr_codec_create(int n_channels, int kind, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   if (!kind_ok(kind)) { fail("codec: kind must be ASDR_CODEC_ULAW (1), ASDR_CODEC_ALAW (2) or ASDR_CODEC_ADPCM (3)"); return nullptr; }
   asdr_codec *c = new asdr_codec;
-  c->n = n_channels; c->kind = kind; c->device = device;
+  c->n = n_channels; c->kind = kind;
   if (device == ASDR_NO_DEVICE) {
     c->host_state.assign(n_channels, asdr_codec_state_t{});
     return c;
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete c; return nullptr; }
-  if (device < 0 || device >= count) { fail("bad device index"); delete c; return nullptr; }
   const size_t bytes = (size_t)n_channels * sizeof(asdr_codec_state_t);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev) != hipSuccess ||
-      hipMalloc(&c->d_state, bytes) != hipSuccess || hipMemset(c->d_state, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+  if (stage_open(*c, device, "codec") != 0) { asdr_codec_destroy(c); return nullptr; }
+  if (hipMalloc(&c->d_state, bytes) != hipSuccess || hipMemset(c->d_state, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     fail("codec: device allocation failed");
     asdr_codec_destroy(c);
     return nullptr;
@@ -129,15 +97,7 @@ asdr_codec_t *asdr_codec_create(int n_channels, int kind, int device) {
 
 void asdr_codec_destroy(asdr_codec_t *c) {
   if (!c) return;
-  if (c->device != ASDR_NO_DEVICE) {
-    hipSetDevice(c->device);
-    if (c->ev_valid) hipEventSynchronize(c->ev);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    for (void *p : {(void *)c->d_state, c->d_rows})
-      if (p) hipFree(p);
-    if (c->ev) hipEventDestroy(c->ev);
-    if (c->stream) hipStreamDestroy(c->stream);
-  }
+  stage_close(*c, {c->d_state, c->d_rows});
   delete c;
 }
 
@@ -184,13 +144,7 @@ long asdr_codec_deliver(asdr_codec_t *c, const int16_t *dRows, long row_stride_s
   hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(c->device));
   const size_t need = (size_t)grid_rows * padded;
-  if (need > c->rows_cap) {                                   // growing waits for the work that may still use the old buffer
-    if (quiesce(c) != 0) return -1;
-    if (c->d_rows) HIPCHK(hipFree(c->d_rows));
-    c->d_rows = nullptr; c->rows_cap = 0;
-    HIPCHK(hipMalloc(&c->d_rows, need));
-    c->rows_cap = need;
-  }
+  if (stage_reserve(*c, &c->d_rows, &c->rows_cap, need) != 0) return -1;
   if (grid_rows > 0) {
     if (overlap((uintptr_t)dRows, input_bytes(c, row_stride_samples, n_samples, dIndex, rows_compact, grid_rows), (uintptr_t)c->d_rows, need))
       return fail("internal: packet buffer overlaps the input span");
@@ -251,36 +205,13 @@ int asdr_codec_decode(int kind, const uint8_t *row, long n_samples, int16_t *out
 
 int asdr_codec_read_state(asdr_codec_t *c, asdr_codec_state_t *dst) {
   if (!c) return fail("null codec");
-  if (!dst) return fail("null destination");
-  const size_t bytes = (size_t)c->n * sizeof(asdr_codec_state_t);
-  if (c->device == ASDR_NO_DEVICE) { std::memcpy(dst, c->host_state.data(), bytes); return 0; }
-  if (quiesce(c) != 0) return -1;
-  HIPCHK(hipMemcpy(dst, c->d_state, bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_read_state(*c, dst, sizeof(asdr_codec_state_t), c->host_state.data(), c->d_state);
 }
 
 int asdr_codec_write_state(asdr_codec_t *c, const int *channels, int n, const asdr_codec_state_t *src) {
   if (!c) return fail("null codec");
-  if (n < 0) return fail("negative record count");
-  if (n == 0) return 0;
-  if (!src) return fail("null source");
-  if (!channels && n > c->n) return fail("more records than channels");
-  for (int k = 0; k < n; k++) {
-    const int ch = channels ? channels[k] : k;
-    if (ch < 0 || ch >= c->n) return fail("record " + std::to_string(k) + ": bad channel");
-    if (check_record(c, k, src[k]) != 0) return -1;
-  }
-  if (quiesce(c) != 0) return -1;
-  if (!channels && c->device != ASDR_NO_DEVICE) {
-    HIPCHK(hipMemcpy(c->d_state, src, (size_t)n * sizeof(asdr_codec_state_t), hipMemcpyHostToDevice));
-    return 0;
-  }
-  for (int k = 0; k < n; k++) {
-    const int ch = channels ? channels[k] : k;
-    if (c->device == ASDR_NO_DEVICE) c->host_state[ch] = src[k];
-    else HIPCHK(hipMemcpy(c->d_state + ch, src + k, sizeof(asdr_codec_state_t), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return stage_write_state(*c, channels, n, src, sizeof(asdr_codec_state_t), c->host_state.data(), c->d_state,
+                           [c](int k, const void *rec) { return check_record(c, k, *(const asdr_codec_state_t *)rec); });
 }
 
 int asdr_codec_reset(asdr_codec_t *c) {
@@ -289,7 +220,7 @@ int asdr_codec_reset(asdr_codec_t *c) {
     c->host_state.assign(c->n, asdr_codec_state_t{});
     return 0;
   }
-  if (quiesce(c) != 0) return -1;
+  if (stage_quiesce(*c) != 0) return -1;
   HIPCHK(hipMemsetAsync(c->d_state, 0, (size_t)c->n * sizeof(asdr_codec_state_t), c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -297,7 +228,7 @@ int asdr_codec_reset(asdr_codec_t *c) {
 
 int asdr_codec_synchronize(asdr_codec_t *c) {
   if (!c) return fail("null codec");
-  return quiesce(c);
+  return stage_quiesce(*c);
 }
 
 }  // extern "C"

@@ -2,24 +2,13 @@
 // AudioIQgenerator and AudioGrabberComplex256.  Control-plane members live in a host
 // mirror that is pushed before a launch when a setter touched it and pulled back lazily when a getter needs what
 // the kernels changed.  There is no CPU implementation of the signal paths: update calls need a HIP device.
-#include <hip/hip_runtime.h>
-
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "asdr_front_device.h"
-
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
+#include "asdr_stage_host.h"
 
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 int ensure_tables() {   // __constant__ tables are per device: (re)uploaded for the current device at every create (a few hundred bytes)
   if (asdr_front_upload_tables() != 0) return fail("front-end table upload failed");
   return 0;
@@ -37,9 +26,7 @@ struct DevBase {
 int dev_init(DevBase &d, int n, int device) {
   d.n = n; d.device = device;
   if (device == ASDR_NO_DEVICE) return 0;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail("no HIP device: this library has no CPU fallback");
-  if (device < 0 || device >= count) return fail("bad device index");
+  if (stage_check_device(device) != 0) return -1;
   HIPCHK(hipSetDevice(device));
   if (ensure_tables() != 0) return -1;
   HIPCHK(hipStreamCreate(&d.stream));

@@ -2,30 +2,21 @@
 // pushed before a launch when a setter touched it; the state rows, the delivered flags, count and index live on the device only
 // (an ASDR_NO_DEVICE gate keeps the state rows on the host instead).  The scratch of block energies and deliver's packet buffer
 // grow on demand and are kept.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <string>
 #include <vector>
 
 #include "asdr_gate_device.h"
-
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
+#include "asdr_stage_host.h"
 
 static_assert(sizeof(asdr_gate_state_t) == 32, "asdr_gate_state_t is a 32-byte record");
 static_assert(sizeof(GateSetting) == 24, "GateSetting is 24 bytes");
 
-struct asdr_gate {
-  int n = 0, device = ASDR_NO_DEVICE;
+struct asdr_gate : StageDev {
   std::vector<GateSetting> set;
   bool set_dirty = true;
   std::vector<asdr_gate_state_t> host_state;   // ASDR_NO_DEVICE only
   long long blocks = 0;
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev = nullptr;
-  bool ev_valid = false;
   GateSetting *d_set = nullptr;
   asdr_gate_state_t *d_state = nullptr;
   uint8_t *d_flag = nullptr;
@@ -35,36 +26,9 @@ struct asdr_gate {
 };
 
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 const char *kNoDevice = "control-plane-only gate (ASDR_NO_DEVICE): the signal path needs a HIP device";
 
 int n_tiles(const asdr_gate_t *g) { return (g->n + ASDR_GATE_TILE - 1) / ASDR_GATE_TILE; }
-
-// waits for the gate's work (nothing for ASDR_NO_DEVICE)
-int quiesce(asdr_gate_t *g) {
-  if (g->device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(g->device));
-  if (g->ev_valid) HIPCHK(hipEventSynchronize(g->ev));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  return 0;
-}
-
-// a device buffer of at least `bytes`, kept; growing waits for the work that may still use the old one
-int reserve(asdr_gate_t *g, void **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return 0;
-  if (quiesce(g) != 0) return -1;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  HIPCHK(hipMalloc(p, bytes));
-  *cap = bytes;
-  return 0;
-}
 
 GateArgs make_args(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks, int n_blocks, int16_t *dRows, int capacity_rows) {
   GateArgs a;
@@ -86,7 +50,13 @@ int check_audio(const asdr_gate_t *g, const int16_t *dAudio, long stride_blocks,
   return 0;
 }
 
-bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+// write_state's check of record k beyond its channel
+int check_record(int k, const void *rec) {
+  const asdr_gate_state_t &s = *(const asdr_gate_state_t *)rec;
+  if (s.open > 1) return fail("record " + std::to_string(k) + ": open must be 0 or 1");
+  if (s.reserved != 0) return fail("record " + std::to_string(k) + ": reserved byte must be 0");
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -98,20 +68,17 @@ uint64_t asdr_gate_energy_from_dbfs(double db) {
 }
 
 asdr_gate_t *asdr_gate_create(int n_channels, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_gate *g = new asdr_gate;
-  g->n = n_channels; g->device = device;
+  g->n = n_channels;
   g->set.assign(n_channels, GateSetting{0, 0, 0, 0});
   if (device == ASDR_NO_DEVICE) {
     g->host_state.assign(n_channels, asdr_gate_state_t{});
     return g;
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete g; return nullptr; }
-  if (device < 0 || device >= count) { fail("bad device index"); delete g; return nullptr; }
   const size_t n = n_channels, tiles = n_tiles(g);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&g->stream) != hipSuccess || hipEventCreate(&g->ev) != hipSuccess ||
-      hipMalloc(&g->d_set, n * sizeof(GateSetting)) != hipSuccess || hipMalloc(&g->d_state, n * sizeof(asdr_gate_state_t)) != hipSuccess ||
+  if (stage_open(*g, device, "gate") != 0) { asdr_gate_destroy(g); return nullptr; }
+  if (hipMalloc(&g->d_set, n * sizeof(GateSetting)) != hipSuccess || hipMalloc(&g->d_state, n * sizeof(asdr_gate_state_t)) != hipSuccess ||
       hipMalloc(&g->d_flag, n) != hipSuccess || hipMalloc(&g->d_tile, tiles * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&g->d_count, sizeof(int32_t)) != hipSuccess || hipMalloc(&g->d_index, n * sizeof(int32_t)) != hipSuccess ||
       hipMemset(g->d_state, 0, n * sizeof(asdr_gate_state_t)) != hipSuccess || hipMemset(g->d_flag, 0, n) != hipSuccess ||
@@ -126,16 +93,7 @@ asdr_gate_t *asdr_gate_create(int n_channels, int device) {
 
 void asdr_gate_destroy(asdr_gate_t *g) {
   if (!g) return;
-  if (g->device != ASDR_NO_DEVICE) {
-    hipSetDevice(g->device);
-    if (g->ev_valid) hipEventSynchronize(g->ev);
-    if (g->stream) hipStreamSynchronize(g->stream);
-    for (void *p : {(void *)g->d_set, (void *)g->d_state, (void *)g->d_flag, (void *)g->d_tile, (void *)g->d_count, (void *)g->d_index,
-                    g->d_scr, g->d_rows})
-      if (p) hipFree(p);
-    if (g->ev) hipEventDestroy(g->ev);
-    if (g->stream) hipStreamDestroy(g->stream);
-  }
+  stage_close(*g, {g->d_set, g->d_state, g->d_flag, g->d_tile, g->d_count, g->d_index, g->d_scr, g->d_rows});
   delete g;
 }
 
@@ -177,9 +135,8 @@ int asdr_gate_update_device(asdr_gate_t *g, const int16_t *dAudio, long stride_b
     if (overlap((uintptr_t)dAudio, audio_bytes, (uintptr_t)dRows, rows_bytes)) return fail("packet span overlaps the audio span");
   }
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(g->device));
-  if (n_blocks > 1 && reserve(g, &g->d_scr, &g->scr_cap, (size_t)g->n * n_blocks * sizeof(uint64_t)) != 0) return -1;
-  if (g->ev_valid && stream != g->last_stream) HIPCHK(hipStreamWaitEvent(stream, g->ev, 0));
+  if (n_blocks > 1 && stage_reserve(*g, &g->d_scr, &g->scr_cap, (size_t)g->n * n_blocks * sizeof(uint64_t)) != 0) return -1;
+  if (stage_before_launch(*g, stream) != 0) return -1;
   if (g->set_dirty) {
     HIPCHK(hipMemcpyAsync(g->d_set, g->set.data(), g->set.size() * sizeof(GateSetting), hipMemcpyHostToDevice, stream));
     g->set_dirty = false;
@@ -187,8 +144,7 @@ int asdr_gate_update_device(asdr_gate_t *g, const int16_t *dAudio, long stride_b
   const GateArgs a = make_args(g, dAudio, stride_blocks, n_blocks, dRows, grid_rows);
   if (asdr_launch_gate_pass(&a, stream) != 0) return fail("gate kernel launch failed");
   if (dRows && asdr_launch_gate_packet(&a, grid_rows, stream) != 0) return fail("gate packet kernel launch failed");
-  HIPCHK(hipEventRecord(g->ev, stream));
-  g->ev_valid = true; g->last_stream = stream;
+  if (stage_after_launch(*g, stream) != 0) return -1;
   g->blocks += n_blocks;
   return 0;
 }
@@ -225,7 +181,7 @@ int asdr_gate_deliver(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks,
   const size_t rows_bytes = (size_t)rows * n_blocks * 256;
   HIPCHK(hipMemcpyAsync(host_index, g->d_index, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
   if (rows > 0) {
-    if (reserve(g, &g->d_rows, &g->rows_cap, rows_bytes) != 0) return -1;
+    if (stage_reserve(*g, &g->d_rows, &g->rows_cap, rows_bytes) != 0) return -1;
     if (overlap((uintptr_t)dAudio, ((size_t)(g->n - 1) * stride_blocks + n_blocks) * 256, (uintptr_t)g->d_rows, rows_bytes))
       return fail("internal: packet buffer overlaps the audio span");
     const GateArgs a = make_args(g, dAudio, stride_blocks, n_blocks, (int16_t *)g->d_rows, rows);
@@ -238,35 +194,12 @@ int asdr_gate_deliver(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks,
 
 int asdr_gate_read_state(asdr_gate_t *g, asdr_gate_state_t *dst) {
   if (!g) return fail("null gate");
-  if (!dst) return fail("null destination");
-  if (g->device == ASDR_NO_DEVICE) {
-    std::memcpy(dst, g->host_state.data(), g->n * sizeof(asdr_gate_state_t));
-    return 0;
-  }
-  if (quiesce(g) != 0) return -1;
-  HIPCHK(hipMemcpy(dst, g->d_state, g->n * sizeof(asdr_gate_state_t), hipMemcpyDeviceToHost));
-  return 0;
+  return stage_read_state(*g, dst, sizeof(asdr_gate_state_t), g->host_state.data(), g->d_state);
 }
 
 int asdr_gate_write_state(asdr_gate_t *g, const int *channels, int n, const asdr_gate_state_t *src) {
   if (!g) return fail("null gate");
-  if (n < 0) return fail("negative record count");
-  if (n == 0) return 0;
-  if (!src) return fail("null source");
-  if (!channels && n > g->n) return fail("more records than channels");
-  for (int k = 0; k < n; k++) {
-    const int c = channels ? channels[k] : k;
-    if (c < 0 || c >= g->n) return fail("record " + std::to_string(k) + ": bad channel");
-    if (src[k].open > 1) return fail("record " + std::to_string(k) + ": open must be 0 or 1");
-    if (src[k].reserved != 0) return fail("record " + std::to_string(k) + ": reserved byte must be 0");
-  }
-  if (g->device != ASDR_NO_DEVICE && quiesce(g) != 0) return -1;
-  for (int k = 0; k < n; k++) {
-    const int c = channels ? channels[k] : k;
-    if (g->device == ASDR_NO_DEVICE) g->host_state[c] = src[k];
-    else HIPCHK(hipMemcpy(g->d_state + c, src + k, sizeof(asdr_gate_state_t), hipMemcpyHostToDevice));
-  }
-  return 0;
+  return stage_write_state(*g, channels, n, src, sizeof(asdr_gate_state_t), g->host_state.data(), g->d_state, check_record);
 }
 
 int asdr_gate_clear(asdr_gate_t *g) {
@@ -289,7 +222,7 @@ int asdr_gate_reset(asdr_gate_t *g) {
   if (g->device == ASDR_NO_DEVICE) {
     g->host_state.assign(g->n, asdr_gate_state_t{});
   } else {
-    if (quiesce(g) != 0) return -1;
+    if (stage_quiesce(*g) != 0) return -1;
     HIPCHK(hipMemsetAsync(g->d_state, 0, g->n * sizeof(asdr_gate_state_t), g->stream));
     HIPCHK(hipMemsetAsync(g->d_count, 0, sizeof(int32_t), g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -302,7 +235,7 @@ long long asdr_gate_blocks(const asdr_gate_t *g) { return g ? g->blocks : -1; }
 
 int asdr_gate_synchronize(asdr_gate_t *g) {
   if (!g) return fail("null gate");
-  return quiesce(g);
+  return stage_quiesce(*g);
 }
 
 }  // extern "C"

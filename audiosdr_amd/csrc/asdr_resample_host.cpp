@@ -2,42 +2,26 @@
 // (what the getters return) and, as the kernel's two pair tables, on the device; the state records live on the device only, in a
 // double buffer whose halves a call reads and writes (an ASDR_NO_DEVICE resampler keeps them on the host instead).  The position
 // N and everything a call derives from it (first output, first b, first phase, the tile's steps) is 64-bit host arithmetic.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <string>
 #include <vector>
 
 #include "asdr_resample_device.h"
+#include "asdr_stage_host.h"
 
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
-
-struct asdr_resampler {
-  int n = 0, device = ASDR_NO_DEVICE;
+struct asdr_resampler : StageDev {
   int up = 1, down = 1, K = 1, shift = 15;
   std::vector<int16_t> taps;                   // h[k * up + phi]
   long long pos = 0;                           // N
   std::vector<int16_t> host_state;             // ASDR_NO_DEVICE only
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev = nullptr;
-  bool ev_valid = false;
-  int16_t *d_carry[2] = {nullptr, nullptr};
-  int cur = 0;
+  CarryPair carry;
   uint32_t *d_taps = nullptr;
 };
 
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 const char *kNoDevice = "control-plane-only resampler (ASDR_NO_DEVICE): the signal path needs a HIP device";
 constexpr int kRecord = ASDR_RESAMPLE_STATE_SAMPLES;
 constexpr long long kMaxN = 1LL << 53;   // N U stays below 2^63
@@ -124,14 +108,6 @@ void pair_tables(const asdr_resampler_t *r, std::vector<uint32_t> &t) {
     }
 }
 
-int quiesce(asdr_resampler_t *r) {
-  if (r->device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(r->device));
-  if (r->ev_valid) HIPCHK(hipEventSynchronize(r->ev));
-  HIPCHK(hipStreamSynchronize(r->stream));
-  return 0;
-}
-
 int push_filter(asdr_resampler_t *r) {
   std::vector<uint32_t> t;
   pair_tables(r, t);
@@ -139,26 +115,21 @@ int push_filter(asdr_resampler_t *r) {
   return 0;
 }
 
-bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
-
 asdr_resampler_t *make(int n_channels, int up, int down, int K, const int16_t *taps, int shift, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   if (check_rate(up, down) != 0 || check_filter(up, K, taps, shift) != 0) return nullptr;
   asdr_resampler *r = new asdr_resampler;
-  r->n = n_channels; r->device = device; r->up = up; r->down = down; r->K = K; r->shift = shift;
+  r->n = n_channels; r->up = up; r->down = down; r->K = K; r->shift = shift;
   r->taps.assign(taps, taps + (size_t)up * K);
   if (device == ASDR_NO_DEVICE) {
     r->host_state.assign((size_t)n_channels * kRecord, 0);
     return r;
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete r; return nullptr; }
-  if (device < 0 || device >= count) { fail("bad device index"); delete r; return nullptr; }
   const size_t rec = (size_t)n_channels * kRecord * sizeof(int16_t);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&r->stream) != hipSuccess || hipEventCreate(&r->ev) != hipSuccess ||
-      hipMalloc(&r->d_carry[0], rec) != hipSuccess || hipMalloc(&r->d_carry[1], rec) != hipSuccess ||
+  if (stage_open(*r, device, "resampler") != 0) { asdr_resampler_destroy(r); return nullptr; }
+  if (hipMalloc(&r->carry.d[0], rec) != hipSuccess || hipMalloc(&r->carry.d[1], rec) != hipSuccess ||
       hipMalloc(&r->d_taps, tap_words(up, ASDR_RESAMPLE_MAX_TAPS) * sizeof(uint32_t)) != hipSuccess ||
-      hipMemset(r->d_carry[0], 0, rec) != hipSuccess || hipMemset(r->d_carry[1], 0, rec) != hipSuccess ||
+      hipMemset(r->carry.d[0], 0, rec) != hipSuccess || hipMemset(r->carry.d[1], 0, rec) != hipSuccess ||
       push_filter(r) != 0 || hipDeviceSynchronize() != hipSuccess) {
     fail("resampler: device allocation failed");
     asdr_resampler_destroy(r);
@@ -196,15 +167,7 @@ asdr_resampler_t *asdr_resampler_create_custom(int n_channels, int up, int down,
 
 void asdr_resampler_destroy(asdr_resampler_t *r) {
   if (!r) return;
-  if (r->device != ASDR_NO_DEVICE) {
-    hipSetDevice(r->device);
-    if (r->ev_valid) hipEventSynchronize(r->ev);
-    if (r->stream) hipStreamSynchronize(r->stream);
-    for (void *p : {(void *)r->d_carry[0], (void *)r->d_carry[1], (void *)r->d_taps})
-      if (p) hipFree(p);
-    if (r->ev) hipEventDestroy(r->ev);
-    if (r->stream) hipStreamDestroy(r->stream);
-  }
+  stage_close(*r, {r->carry.d[0], r->carry.d[1], r->d_taps});
   delete r;
 }
 
@@ -228,7 +191,7 @@ double asdr_resampler_delay(const asdr_resampler_t *r) {
 int asdr_resampler_set_filter(asdr_resampler_t *r, int taps_per_phase, const int16_t *taps, int shift) {
   if (!r) return fail("null resampler");
   if (check_filter(r->up, taps_per_phase, taps, shift) != 0) return -1;
-  if (quiesce(r) != 0) return -1;
+  if (stage_quiesce(*r) != 0) return -1;
   r->K = taps_per_phase; r->shift = shift;
   r->taps.assign(taps, taps + (size_t)r->up * taps_per_phase);
   return r->device == ASDR_NO_DEVICE ? 0 : push_filter(r);
@@ -251,7 +214,7 @@ long asdr_resampler_out_samples(const asdr_resampler_t *r, int n_blocks) {
 int asdr_resampler_set_position(asdr_resampler_t *r, long long n) {
   if (!r) return fail("null resampler");
   if (n < 0 || n > ASDR_RESAMPLE_MAX_POSITION) return fail("resampler: position must be in 0..2^50");
-  if (quiesce(r) != 0) return -1;
+  if (stage_quiesce(*r) != 0) return -1;
   r->pos = n;
   return 0;
 }
@@ -285,7 +248,7 @@ long asdr_resampler_update_device(asdr_resampler_t *r, const int16_t *dAudio, lo
 
   ResampleArgs a;
   a.audio = dAudio; a.stride_blocks = stride_blocks;
-  a.carry = r->d_carry[r->cur]; a.carry_next = r->d_carry[r->cur ^ 1];
+  a.carry = r->carry.current(); a.carry_next = r->carry.next();
   a.out = dOut; a.out_stride = out_stride_samples;
   a.index = dIndex; a.count = dCount;
   a.taps = r->d_taps;
@@ -315,67 +278,36 @@ long asdr_resampler_update_device(asdr_resampler_t *r, const int16_t *dAudio, lo
     return fail("resampler: the call is too large for one launch; split it");
 
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(r->device));
-  if (r->ev_valid && stream != r->last_stream) HIPCHK(hipStreamWaitEvent(stream, r->ev, 0));
+  if (stage_before_launch(*r, stream) != 0) return -1;
   if (asdr_launch_resample(&a, stream) != 0) return fail("resampler kernel launch failed");
   if (asdr_launch_resample_carry(&a, stream) != 0) return fail("resampler carry kernel launch failed");
-  HIPCHK(hipEventRecord(r->ev, stream));
-  r->ev_valid = true; r->last_stream = stream;
-  r->cur ^= 1;
+  if (stage_after_launch(*r, stream) != 0) return -1;
+  r->carry.flip();
   r->pos = n1;
   return (long)n_out;
 }
 
 int asdr_resampler_read_state(asdr_resampler_t *r, int16_t *dst) {
   if (!r) return fail("null resampler");
-  if (!dst) return fail("null destination");
-  const size_t bytes = (size_t)r->n * kRecord * sizeof(int16_t);
-  if (r->device == ASDR_NO_DEVICE) { std::memcpy(dst, r->host_state.data(), bytes); return 0; }
-  if (quiesce(r) != 0) return -1;
-  HIPCHK(hipMemcpy(dst, r->d_carry[r->cur], bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_read_state(*r, dst, kRecord * sizeof(int16_t), r->host_state.data(), r->carry.current());
 }
 
 int asdr_resampler_write_state(asdr_resampler_t *r, const int *channels, int n, const int16_t *src) {
   if (!r) return fail("null resampler");
-  if (n < 0) return fail("negative record count");
-  if (n == 0) return 0;
-  if (!src) return fail("null source");
-  if (!channels && n > r->n) return fail("more records than channels");
-  for (int k = 0; k < n; k++) {
-    const int c = channels ? channels[k] : k;
-    if (c < 0 || c >= r->n) return fail("record " + std::to_string(k) + ": bad channel");
-  }
-  if (quiesce(r) != 0) return -1;
-  const size_t rec = kRecord * sizeof(int16_t);
-  if (!channels && r->device != ASDR_NO_DEVICE) {
-    HIPCHK(hipMemcpy(r->d_carry[r->cur], src, (size_t)n * rec, hipMemcpyHostToDevice));
-    return 0;
-  }
-  for (int k = 0; k < n; k++) {
-    const size_t c = channels ? channels[k] : k;
-    if (r->device == ASDR_NO_DEVICE) std::memcpy(r->host_state.data() + c * kRecord, src + (size_t)k * kRecord, rec);
-    else HIPCHK(hipMemcpy(r->d_carry[r->cur] + c * kRecord, src + (size_t)k * kRecord, rec, hipMemcpyHostToDevice));
-  }
-  return 0;
+  return stage_write_state(*r, channels, n, src, kRecord * sizeof(int16_t), r->host_state.data(), r->carry.current());
 }
 
 int asdr_resampler_reset(asdr_resampler_t *r) {
   if (!r) return fail("null resampler");
-  if (r->device == ASDR_NO_DEVICE) {
-    std::fill(r->host_state.begin(), r->host_state.end(), (int16_t)0);
-  } else {
-    if (quiesce(r) != 0) return -1;
-    HIPCHK(hipMemsetAsync(r->d_carry[r->cur], 0, (size_t)r->n * kRecord * sizeof(int16_t), r->stream));
-    HIPCHK(hipStreamSynchronize(r->stream));
-  }
+  if (r->device == ASDR_NO_DEVICE) std::fill(r->host_state.begin(), r->host_state.end(), (int16_t)0);
+  else if (r->carry.reset(*r, (size_t)r->n * kRecord * sizeof(int16_t)) != 0) return -1;
   r->pos = 0;
   return 0;
 }
 
 int asdr_resampler_synchronize(asdr_resampler_t *r) {
   if (!r) return fail("null resampler");
-  return quiesce(r);
+  return stage_quiesce(*r);
 }
 
 }  // extern "C"

@@ -2,54 +2,29 @@
 // copy (what get_window returns) and on the device beside the float64-built twiddle table W_N; the state records live on the device
 // only, in a double buffer whose halves a call reads and writes (an ASDR_NO_DEVICE spectrogram keeps them on the host instead).  The
 // position T and everything a call derives from it (frame counts, the first frame's offset) is 64-bit host arithmetic.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <string>
 #include <vector>
 
 #include "asdr_spectrogram_device.h"
+#include "asdr_stage_host.h"
 
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
-
-struct asdr_spectrogram {
-  int n = 0, device = ASDR_NO_DEVICE;
+struct asdr_spectrogram : StageDev {
   int N = 0, log2n = 0, hop = 0, k0 = 0, bins = 0, window_kind = ASDR_SPECTROGRAM_RECT, kind = ASDR_SPECTROGRAM_POWER;
   std::vector<float> window;                   // [N]
   long long pos = 0;                           // T
   std::vector<int16_t> host_state;             // ASDR_NO_DEVICE only
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev = nullptr;
-  bool ev_valid = false;
-  int16_t *d_carry[2] = {nullptr, nullptr};
-  int cur = 0;
+  CarryPair carry;
   float *d_window = nullptr, *d_tw = nullptr;
 };
 
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 const char *kNoDevice = "control-plane-only spectrogram (ASDR_NO_DEVICE): the signal path needs a HIP device";
 const char *kNull = "null spectrogram";
 
 // F(T): the frames that lie wholly in the first T samples
 long long frames_at(const asdr_spectrogram_t *s, long long t) { return t < s->N ? 0 : (t - s->N) / s->hop + 1; }
-
-int quiesce(asdr_spectrogram_t *s) {
-  if (s->device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(s->device));
-  if (s->ev_valid) HIPCHK(hipEventSynchronize(s->ev));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return 0;
-}
 
 int push_window(asdr_spectrogram_t *s) {
   HIPCHK(hipMemcpy(s->d_window, s->window.data(), s->window.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -67,14 +42,12 @@ int push_twiddles(asdr_spectrogram_t *s) {
   HIPCHK(hipMemcpy(s->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
-
-bool overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
 }  // namespace
 
 extern "C" {
 
 asdr_spectrogram_t *asdr_spectrogram_create(int n_channels, int n_fft, int hop, int first_bin, int n_bins, int window, int kind, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   int log2n = 0;
   while ((1 << log2n) < n_fft && log2n < 30) log2n++;
   if (n_fft < ASDR_SPECTROGRAM_MIN_N || n_fft > ASDR_SPECTROGRAM_MAX_N || (1 << log2n) != n_fft) {
@@ -89,7 +62,7 @@ asdr_spectrogram_t *asdr_spectrogram_create(int n_channels, int n_fft, int hop, 
   if (window != ASDR_SPECTROGRAM_RECT && window != ASDR_SPECTROGRAM_HANN) { fail("spectrogram: the window must be rect or hann (custom: set_window)"); return nullptr; }
   if (kind != ASDR_SPECTROGRAM_POWER && kind != ASDR_SPECTROGRAM_COMPLEX) { fail("spectrogram: the output kind must be power or complex"); return nullptr; }
   asdr_spectrogram *s = new asdr_spectrogram;
-  s->n = n_channels; s->device = device; s->N = n_fft; s->log2n = log2n; s->hop = hop; s->k0 = first_bin; s->bins = n_bins;
+  s->n = n_channels; s->N = n_fft; s->log2n = log2n; s->hop = hop; s->k0 = first_bin; s->bins = n_bins;
   s->window_kind = window; s->kind = kind;
   s->window.assign(n_fft, 1.0f);
   if (window == ASDR_SPECTROGRAM_HANN) {
@@ -100,14 +73,11 @@ asdr_spectrogram_t *asdr_spectrogram_create(int n_channels, int n_fft, int hop, 
     s->host_state.assign((size_t)n_channels * n_fft, 0);
     return s;
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete s; return nullptr; }
-  if (device < 0 || device >= count) { fail("bad device index"); delete s; return nullptr; }
   const size_t rec = (size_t)n_channels * n_fft * sizeof(int16_t);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&s->stream) != hipSuccess || hipEventCreate(&s->ev) != hipSuccess ||
-      hipMalloc(&s->d_carry[0], rec) != hipSuccess || hipMalloc(&s->d_carry[1], rec) != hipSuccess ||
+  if (stage_open(*s, device, "spectrogram") != 0) { asdr_spectrogram_destroy(s); return nullptr; }
+  if (hipMalloc(&s->carry.d[0], rec) != hipSuccess || hipMalloc(&s->carry.d[1], rec) != hipSuccess ||
       hipMalloc(&s->d_window, (size_t)n_fft * sizeof(float)) != hipSuccess || hipMalloc(&s->d_tw, (size_t)2 * n_fft * sizeof(float)) != hipSuccess ||
-      hipMemset(s->d_carry[0], 0, rec) != hipSuccess || hipMemset(s->d_carry[1], 0, rec) != hipSuccess ||
+      hipMemset(s->carry.d[0], 0, rec) != hipSuccess || hipMemset(s->carry.d[1], 0, rec) != hipSuccess ||
       push_window(s) != 0 || push_twiddles(s) != 0 || hipDeviceSynchronize() != hipSuccess) {
     fail("spectrogram: device allocation failed");
     asdr_spectrogram_destroy(s);
@@ -118,15 +88,7 @@ asdr_spectrogram_t *asdr_spectrogram_create(int n_channels, int n_fft, int hop, 
 
 void asdr_spectrogram_destroy(asdr_spectrogram_t *s) {
   if (!s) return;
-  if (s->device != ASDR_NO_DEVICE) {
-    hipSetDevice(s->device);
-    if (s->ev_valid) hipEventSynchronize(s->ev);
-    if (s->stream) hipStreamSynchronize(s->stream);
-    for (void *p : {(void *)s->d_carry[0], (void *)s->d_carry[1], (void *)s->d_window, (void *)s->d_tw})
-      if (p) hipFree(p);
-    if (s->ev) hipEventDestroy(s->ev);
-    if (s->stream) hipStreamDestroy(s->stream);
-  }
+  stage_close(*s, {s->carry.d[0], s->carry.d[1], s->d_window, s->d_tw});
   delete s;
 }
 
@@ -150,7 +112,7 @@ int asdr_spectrogram_set_window(asdr_spectrogram_t *s, const float *w) {
   if (!w) return fail("null window");
   for (int i = 0; i < s->N; i++)
     if (!std::isfinite(w[i])) return fail("spectrogram: window value " + std::to_string(i) + " is not finite");
-  if (quiesce(s) != 0) return -1;
+  if (stage_quiesce(*s) != 0) return -1;
   s->window.assign(w, w + s->N);
   s->window_kind = ASDR_SPECTROGRAM_CUSTOM;
   return s->device == ASDR_NO_DEVICE ? 0 : push_window(s);
@@ -168,7 +130,7 @@ long asdr_spectrogram_out_frames(const asdr_spectrogram_t *s, long n_samples) {
 int asdr_spectrogram_set_position(asdr_spectrogram_t *s, long long t) {
   if (!s) return fail(kNull);
   if (t < 0 || t > ASDR_SPECTROGRAM_MAX_POSITION) return fail("spectrogram: position must be in 0..2^50");
-  if (quiesce(s) != 0) return -1;
+  if (stage_quiesce(*s) != 0) return -1;
   s->pos = t;
   return 0;
 }
@@ -204,7 +166,7 @@ long asdr_spectrogram_update_device(asdr_spectrogram_t *s, const int16_t *dAudio
 
   SpectrogramArgs a;
   a.audio = dAudio; a.stride = stride_samples;
-  a.carry = s->d_carry[s->cur]; a.carry_next = s->d_carry[s->cur ^ 1];
+  a.carry = s->carry.current(); a.carry_next = s->carry.next();
   a.out = dOut; a.out_stride = out_stride_frames;
   a.index = dIndex; a.count = dCount;
   a.window = s->d_window; a.tw = s->d_tw;
@@ -218,67 +180,36 @@ long asdr_spectrogram_update_device(asdr_spectrogram_t *s, const int16_t *dAudio
     return fail("internal: spectrogram launch geometry out of range");
 
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(s->device));
-  if (s->ev_valid && stream != s->last_stream) HIPCHK(hipStreamWaitEvent(stream, s->ev, 0));
+  if (stage_before_launch(*s, stream) != 0) return -1;
   if (asdr_launch_spectrogram(&a, stream) != 0) return fail("spectrogram kernel launch failed");
   if (asdr_launch_spectrogram_carry(&a, stream) != 0) return fail("spectrogram carry kernel launch failed");
-  HIPCHK(hipEventRecord(s->ev, stream));
-  s->ev_valid = true; s->last_stream = stream;
-  s->cur ^= 1;
+  if (stage_after_launch(*s, stream) != 0) return -1;
+  s->carry.flip();
   s->pos = t1;
   return (long)n_frames;
 }
 
 int asdr_spectrogram_read_state(asdr_spectrogram_t *s, int16_t *dst) {
   if (!s) return fail(kNull);
-  if (!dst) return fail("null destination");
-  const size_t bytes = (size_t)s->n * s->N * sizeof(int16_t);
-  if (s->device == ASDR_NO_DEVICE) { std::memcpy(dst, s->host_state.data(), bytes); return 0; }
-  if (quiesce(s) != 0) return -1;
-  HIPCHK(hipMemcpy(dst, s->d_carry[s->cur], bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return stage_read_state(*s, dst, s->N * sizeof(int16_t), s->host_state.data(), s->carry.current());
 }
 
 int asdr_spectrogram_write_state(asdr_spectrogram_t *s, const int *channels, int n, const int16_t *src) {
   if (!s) return fail(kNull);
-  if (n < 0) return fail("negative record count");
-  if (n == 0) return 0;
-  if (!src) return fail("null source");
-  if (!channels && n > s->n) return fail("more records than channels");
-  for (int k = 0; k < n; k++) {
-    const int c = channels ? channels[k] : k;
-    if (c < 0 || c >= s->n) return fail("record " + std::to_string(k) + ": bad channel");
-  }
-  if (quiesce(s) != 0) return -1;
-  const size_t len = (size_t)s->N, rec = len * sizeof(int16_t);
-  if (!channels && s->device != ASDR_NO_DEVICE) {
-    HIPCHK(hipMemcpy(s->d_carry[s->cur], src, (size_t)n * rec, hipMemcpyHostToDevice));
-    return 0;
-  }
-  for (int k = 0; k < n; k++) {
-    const size_t c = channels ? channels[k] : k;
-    if (s->device == ASDR_NO_DEVICE) std::memcpy(s->host_state.data() + c * len, src + (size_t)k * len, rec);
-    else HIPCHK(hipMemcpy(s->d_carry[s->cur] + c * len, src + (size_t)k * len, rec, hipMemcpyHostToDevice));
-  }
-  return 0;
+  return stage_write_state(*s, channels, n, src, s->N * sizeof(int16_t), s->host_state.data(), s->carry.current());
 }
 
 int asdr_spectrogram_reset(asdr_spectrogram_t *s) {
   if (!s) return fail(kNull);
-  if (s->device == ASDR_NO_DEVICE) {
-    std::fill(s->host_state.begin(), s->host_state.end(), (int16_t)0);
-  } else {
-    if (quiesce(s) != 0) return -1;
-    HIPCHK(hipMemsetAsync(s->d_carry[s->cur], 0, (size_t)s->n * s->N * sizeof(int16_t), s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-  }
+  if (s->device == ASDR_NO_DEVICE) std::fill(s->host_state.begin(), s->host_state.end(), (int16_t)0);
+  else if (s->carry.reset(*s, (size_t)s->n * s->N * sizeof(int16_t)) != 0) return -1;
   s->pos = 0;
   return 0;
 }
 
 int asdr_spectrogram_synchronize(asdr_spectrogram_t *s) {
   if (!s) return fail(kNull);
-  return quiesce(s);
+  return stage_quiesce(*s);
 }
 
 }  // extern "C"

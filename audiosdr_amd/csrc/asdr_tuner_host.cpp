@@ -6,27 +6,16 @@
 // gain 1 also pushes the palette's table and the channels' slots and gains, and runs asdr_tuner_palette.hip's channel step.
 // Source conditioning (asdr_tuner_condition.hip) is a pre-pass of run_stage1: a bank with a correction off the identity reads its
 // stage-1 input from a scratch of corrected CS16 / RS16 rows instead of the caller's; one with the statistics on also sums there.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <string>
 #include <vector>
 
+#include "asdr_stage_host.h"
 #include "asdr_tuner_device.h"
 #include "asdr_tuner_state.h"
 
-int asdr_internal_fail(const std::string &m);   // asdr_host.cpp: sets the thread's asdr_last_error() text, returns -1
-
 namespace {
-int fail(const std::string &m) { return asdr_internal_fail(m); }
-#define HIPCHK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 const char *kFormatNames[] = {"CS16", "CU8", "CS8", "CF32", "RS16"};
 const char *kNoDevice = "control-plane-only tuner bank (ASDR_NO_DEVICE): the signal path needs a HIP device";
 constexpr int kTapWords = 1088;   // >= ceil(L / D) * ceil(D / 2) for every D <= 64, L <= 1024 (the largest is 1024, D = 1)
@@ -354,7 +343,6 @@ int push(asdr_tuner_t *t, hipStream_t stream) {
   return 0;
 }
 
-bool overlap(uintptr_t a0, size_t an, uintptr_t b0, size_t bn) { return a0 < b0 + bn && b0 < a0 + an; }
 
 // stage 2 is a pass-through (the output is u): U = M = 1, K = 1, h2 = {1 << s2}
 bool pass_through(const asdr_tuner_t *t) {
@@ -547,9 +535,7 @@ asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int de
 asdr_tuner_t *open_device(asdr_tuner_bank *t) {
   const int device = t->device, n_sources = t->n_src, n_channels = t->n;
   if (device == ASDR_NO_DEVICE) return t;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { fail("no HIP device: this library has no CPU fallback"); delete t; return nullptr; }
-  if (device < 0 || device >= count) { fail("bad device index"); delete t; return nullptr; }
+  if (stage_check_device(device) != 0) { delete t; return nullptr; }
   const size_t hist = (size_t)n_sources * t->hist_slots * sizeof(int32_t);
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&t->stream) != hipSuccess || hipEventCreate(&t->ev0) != hipSuccess ||
       hipEventCreate(&t->ev1) != hipSuccess || hipMalloc(&t->d_chan, n_channels * sizeof(asdr_tuner_state_t)) != hipSuccess ||

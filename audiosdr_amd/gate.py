@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import ALL, BLOCK, AsdrError, load_library
+from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from .binding import ALL, BLOCK, AsdrError
 
 GATE_EXPORTS = ["asdr_gate_create", "asdr_gate_destroy", "asdr_gate_n_channels", "asdr_gate_set_squelch", "asdr_gate_get_squelch",
                 "asdr_gate_energy_from_dbfs", "asdr_gate_update_device", "asdr_gate_count_device", "asdr_gate_index_device",
@@ -17,32 +18,16 @@ GATE_STATE_DTYPE = np.dtype([("energy", "<u8"), ("last_energy", "<u8"), ("peak",
 assert GATE_STATE_DTYPE.itemsize == 32
 GATE_TILE = 256          # channels per tile of the index step's scan (ASDR_GATE_TILE)
 
-_typed = False
+_u64, _u64p = C.c_uint64, C.POINTER(C.c_uint64)
+_API = {"create": ([i, i], vp), "destroy": ([vp], None), "n_channels": ([vp], i), "clear": ([vp], i), "reset": ([vp], i),
+        "synchronize": ([vp], i), "set_squelch": ([vp, i, _u64, _u64, i], i), "get_squelch": ([vp, i, _u64p, _u64p, ip], i),
+        "energy_from_dbfs": ([C.c_double], _u64), "update_device": ([vp, vp, lg, i, vp, i, vp], i), "count_device": ([vp], vp),
+        "index_device": ([vp], vp), "deliver": ([vp, vp, lg, i, vp, vp, i, ip], i), "read_state": ([vp, vp], i),
+        "write_state": ([vp, ip, i, vp], i), "blocks": ([vp], C.c_longlong)}
 
 
 def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, u64, lg = C.c_void_p, C.c_int, C.c_uint64, C.c_long
-    u64p, ip = C.POINTER(C.c_uint64), C.POINTER(C.c_int)
-    L.asdr_gate_create.argtypes = [i, i]; L.asdr_gate_create.restype = vp
-    L.asdr_gate_destroy.argtypes = [vp]; L.asdr_gate_destroy.restype = None
-    for n in ("n_channels", "clear", "reset", "synchronize"):
-        getattr(L, "asdr_gate_" + n).argtypes = [vp]; getattr(L, "asdr_gate_" + n).restype = i
-    L.asdr_gate_set_squelch.argtypes = [vp, i, u64, u64, i]; L.asdr_gate_set_squelch.restype = i
-    L.asdr_gate_get_squelch.argtypes = [vp, i, u64p, u64p, ip]; L.asdr_gate_get_squelch.restype = i
-    L.asdr_gate_energy_from_dbfs.argtypes = [C.c_double]; L.asdr_gate_energy_from_dbfs.restype = u64
-    L.asdr_gate_update_device.argtypes = [vp, vp, lg, i, vp, i, vp]; L.asdr_gate_update_device.restype = i
-    L.asdr_gate_count_device.argtypes = [vp]; L.asdr_gate_count_device.restype = vp
-    L.asdr_gate_index_device.argtypes = [vp]; L.asdr_gate_index_device.restype = vp
-    L.asdr_gate_deliver.argtypes = [vp, vp, lg, i, vp, vp, i, ip]; L.asdr_gate_deliver.restype = i
-    L.asdr_gate_read_state.argtypes = [vp, vp]; L.asdr_gate_read_state.restype = i
-    L.asdr_gate_write_state.argtypes = [vp, ip, i, vp]; L.asdr_gate_write_state.restype = i
-    L.asdr_gate_blocks.argtypes = [vp]; L.asdr_gate_blocks.restype = C.c_longlong
-    _typed = True
-    return L
+    return typed_library("asdr_gate_", _API)
 
 
 def energy_from_dbfs(db):
@@ -58,32 +43,15 @@ class _DeviceInts:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
-class AudioGate:
+class AudioGate(Stage):
     """Audio meters and squelch of n_channels receivers over the chain's int16 audio rows (include/asdr_gate.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
+    _prefix = "asdr_gate_"
 
     def __init__(self, n_channels, device=0):
         self._L = _lib()
-        self._h = self._L.asdr_gate_create(int(n_channels), int(device))
-        if not self._h:
-            raise AsdrError("asdr_gate_create failed: %s" % self._L.asdr_last_error().decode())
+        self._create("asdr_gate_create", self._L.asdr_gate_create(int(n_channels), int(device)))
         self.n_channels = int(n_channels)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.asdr_gate_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
 
     # settings
     def set_squelch(self, open_db=None, close_db=None, hang_blocks=0, ch=ALL, energies=None):
@@ -164,22 +132,10 @@ class AudioGate:
     def write_state(self, records, channels=None):
         """Writes GATE_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
         rec = np.ascontiguousarray(records, dtype=GATE_STATE_DTYPE).reshape(-1)
-        chp = None
-        if channels is not None:
-            ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
-            if ch.size != rec.size:
-                raise AsdrError("write_state: %d records for %d channels" % (rec.size, ch.size))
-            chp = ch.ctypes.data_as(C.POINTER(C.c_int))
-        self._chk(self._L.asdr_gate_write_state(self._h, chp, int(rec.size), rec.ctypes.data_as(C.c_void_p)))
+        self._chk(self._L.asdr_gate_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
 
     def clear(self):
         self._chk(self._L.asdr_gate_clear(self._h))
 
-    def reset(self):
-        self._chk(self._L.asdr_gate_reset(self._h))
-
     def blocks(self):
         return int(self._L.asdr_gate_blocks(self._h))
-
-    def synchronize(self):
-        self._chk(self._L.asdr_gate_synchronize(self._h))

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import AsdrError, load_library
+from ._stage import Stage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from .binding import AsdrError
 
 RESAMPLE_EXPORTS = ["asdr_resampler_create", "asdr_resampler_create_custom", "asdr_resampler_destroy", "asdr_resampler_n_channels",
                     "asdr_resampler_up", "asdr_resampler_down", "asdr_resampler_taps_per_phase", "asdr_resampler_get_taps",
@@ -17,33 +18,15 @@ RESAMPLE_FS_IN = 44100
 RESAMPLE_STATE_SAMPLES = 256     # int16 per channel record (ASDR_RESAMPLE_STATE_SAMPLES)
 RESAMPLE_DEFAULT_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000)   # the rates of the header's table
 
-_typed = False
+_API = {"create": ([i, i, i], vp), "create_custom": ([i, i, i, i, vp, i, i], vp), "destroy": ([vp], None), "n_channels": ([vp], i),
+        "up": ([vp], i), "down": ([vp], i), "taps_per_phase": ([vp], i), "reset": ([vp], i), "synchronize": ([vp], i),
+        "get_taps": ([vp, vp, ip], i), "delay": ([vp], C.c_double), "set_filter": ([vp, i, vp, i], i), "position": ([vp], ll),
+        "output_position": ([vp], ll), "out_samples": ([vp, i], lg), "set_position": ([vp, ll], i),
+        "update_device": ([vp, vp, lg, i, vp, lg, vp, vp, i, vp], lg), "read_state": ([vp, vp], i), "write_state": ([vp, ip, i, vp], i)}
 
 
 def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, lg, ll = C.c_void_p, C.c_int, C.c_long, C.c_longlong
-    ip = C.POINTER(C.c_int)
-    L.asdr_resampler_create.argtypes = [i, i, i]; L.asdr_resampler_create.restype = vp
-    L.asdr_resampler_create_custom.argtypes = [i, i, i, i, vp, i, i]; L.asdr_resampler_create_custom.restype = vp
-    L.asdr_resampler_destroy.argtypes = [vp]; L.asdr_resampler_destroy.restype = None
-    for n in ("n_channels", "up", "down", "taps_per_phase", "reset", "synchronize"):
-        getattr(L, "asdr_resampler_" + n).argtypes = [vp]; getattr(L, "asdr_resampler_" + n).restype = i
-    L.asdr_resampler_get_taps.argtypes = [vp, vp, ip]; L.asdr_resampler_get_taps.restype = i
-    L.asdr_resampler_delay.argtypes = [vp]; L.asdr_resampler_delay.restype = C.c_double
-    L.asdr_resampler_set_filter.argtypes = [vp, i, vp, i]; L.asdr_resampler_set_filter.restype = i
-    L.asdr_resampler_position.argtypes = [vp]; L.asdr_resampler_position.restype = ll
-    L.asdr_resampler_output_position.argtypes = [vp]; L.asdr_resampler_output_position.restype = ll
-    L.asdr_resampler_out_samples.argtypes = [vp, i]; L.asdr_resampler_out_samples.restype = lg
-    L.asdr_resampler_set_position.argtypes = [vp, ll]; L.asdr_resampler_set_position.restype = i
-    L.asdr_resampler_update_device.argtypes = [vp, vp, lg, i, vp, lg, vp, vp, i, vp]; L.asdr_resampler_update_device.restype = lg
-    L.asdr_resampler_read_state.argtypes = [vp, vp]; L.asdr_resampler_read_state.restype = i
-    L.asdr_resampler_write_state.argtypes = [vp, ip, i, vp]; L.asdr_resampler_write_state.restype = i
-    _typed = True
-    return L
+    return typed_library("asdr_resampler_", _API)
 
 
 def _taps_array(taps, up):
@@ -53,43 +36,25 @@ def _taps_array(taps, up):
     return t.astype(np.int16)
 
 
-class AudioResampler:
+class AudioResampler(Stage):
     """Resampler of n_channels receivers' audio rows from 44.1 kHz to fs_out (include/asdr_resample.h).  Either fs_out (the default
     filter of that rate) or up, down, taps [up * K] as h[k * up + phi] and shift (a custom filter).  device = NO_DEVICE (-1) gives
     the control plane and the state records only."""
+    _prefix = "asdr_resampler_"
 
     def __init__(self, n_channels, fs_out=12000, device=0, up=None, down=None, taps=None, shift=15):
         self._L = _lib()
         if taps is None:
             if up is not None or down is not None:
                 raise AsdrError("AudioResampler: up / down come with custom taps")
-            self._h = self._L.asdr_resampler_create(int(n_channels), int(fs_out), int(device))
-            what = "asdr_resampler_create"
+            self._create("asdr_resampler_create", self._L.asdr_resampler_create(int(n_channels), int(fs_out), int(device)))
         else:
             t = _taps_array(taps, up)
-            self._h = self._L.asdr_resampler_create_custom(int(n_channels), int(up), int(down), t.size // max(int(up), 1), t.ctypes.data_as(C.c_void_p),
-                                                           int(shift), int(device))
-            what = "asdr_resampler_create_custom"
-        if not self._h:
-            raise AsdrError("%s failed: %s" % (what, self._L.asdr_last_error().decode()))
+            self._create("asdr_resampler_create_custom",
+                         self._L.asdr_resampler_create_custom(int(n_channels), int(up), int(down), t.size // max(int(up), 1),
+                                                              t.ctypes.data_as(C.c_void_p), int(shift), int(device)))
         self.n_channels = int(n_channels)
         self.up, self.down = int(self._L.asdr_resampler_up(self._h)), int(self._L.asdr_resampler_down(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.asdr_resampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
 
     # the rate and the filter
     @property
@@ -153,16 +118,4 @@ class AudioResampler:
     def write_state(self, records, channels=None):
         """Writes int16 [k, 256] records into `channels` (default 0 .. k - 1); every channel is checked before one is written."""
         rec = np.ascontiguousarray(records, dtype=np.int16).reshape(-1, RESAMPLE_STATE_SAMPLES)
-        chp = None
-        if channels is not None:
-            ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
-            if ch.size != rec.shape[0]:
-                raise AsdrError("write_state: %d records for %d channels" % (rec.shape[0], ch.size))
-            chp = ch.ctypes.data_as(C.POINTER(C.c_int))
-        self._chk(self._L.asdr_resampler_write_state(self._h, chp, int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))
-
-    def reset(self):
-        self._chk(self._L.asdr_resampler_reset(self._h))
-
-    def synchronize(self):
-        self._chk(self._L.asdr_resampler_synchronize(self._h))
+        self._chk(self._L.asdr_resampler_write_state(self._h, _channel_ptr(channels, rec.shape[0]), int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))

@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import AsdrError, load_library
+from ._stage import Stage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from .binding import AsdrError
 
 SPECTROGRAM_EXPORTS = ["asdr_spectrogram_create", "asdr_spectrogram_destroy", "asdr_spectrogram_n_channels", "asdr_spectrogram_n_fft",
                        "asdr_spectrogram_hop", "asdr_spectrogram_first_bin", "asdr_spectrogram_n_bins", "asdr_spectrogram_window_kind",
@@ -20,39 +21,24 @@ SPECTROGRAM_WINDOWS = ("rect", "hann", "custom")      # ASDR_SPECTROGRAM_RECT / 
 SPECTROGRAM_KINDS = ("power", "complex")              # ASDR_SPECTROGRAM_POWER / _COMPLEX
 SPECTROGRAM_MAX_SAMPLES = 1 << 24                     # per call
 
-_typed = False
+_API = {"create": ([i] * 8, vp), "destroy": ([vp], None), "n_channels": ([vp], i), "n_fft": ([vp], i), "hop": ([vp], i),
+        "first_bin": ([vp], i), "n_bins": ([vp], i), "window_kind": ([vp], i), "output_kind": ([vp], i), "reset": ([vp], i),
+        "synchronize": ([vp], i), "get_window": ([vp, vp], i), "set_window": ([vp, vp], i), "position": ([vp], ll),
+        "frame_position": ([vp], ll), "out_frames": ([vp, lg], lg), "set_position": ([vp, ll], i),
+        "update_device": ([vp, vp, lg, lg, vp, lg, vp, vp, i, vp], lg), "read_state": ([vp, vp], i), "write_state": ([vp, ip, i, vp], i)}
 
 
 def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, lg, ll = C.c_void_p, C.c_int, C.c_long, C.c_longlong
-    ip = C.POINTER(C.c_int)
-    L.asdr_spectrogram_create.argtypes = [i] * 8; L.asdr_spectrogram_create.restype = vp
-    L.asdr_spectrogram_destroy.argtypes = [vp]; L.asdr_spectrogram_destroy.restype = None
-    for n in ("n_channels", "n_fft", "hop", "first_bin", "n_bins", "window_kind", "output_kind", "reset", "synchronize"):
-        getattr(L, "asdr_spectrogram_" + n).argtypes = [vp]; getattr(L, "asdr_spectrogram_" + n).restype = i
-    L.asdr_spectrogram_get_window.argtypes = [vp, vp]; L.asdr_spectrogram_get_window.restype = i
-    L.asdr_spectrogram_set_window.argtypes = [vp, vp]; L.asdr_spectrogram_set_window.restype = i
-    L.asdr_spectrogram_position.argtypes = [vp]; L.asdr_spectrogram_position.restype = ll
-    L.asdr_spectrogram_frame_position.argtypes = [vp]; L.asdr_spectrogram_frame_position.restype = ll
-    L.asdr_spectrogram_out_frames.argtypes = [vp, lg]; L.asdr_spectrogram_out_frames.restype = lg
-    L.asdr_spectrogram_set_position.argtypes = [vp, ll]; L.asdr_spectrogram_set_position.restype = i
-    L.asdr_spectrogram_update_device.argtypes = [vp, vp, lg, lg, vp, lg, vp, vp, i, vp]; L.asdr_spectrogram_update_device.restype = lg
-    L.asdr_spectrogram_read_state.argtypes = [vp, vp]; L.asdr_spectrogram_read_state.restype = i
-    L.asdr_spectrogram_write_state.argtypes = [vp, ip, i, vp]; L.asdr_spectrogram_write_state.restype = i
-    _typed = True
-    return L
+    return typed_library("asdr_spectrogram_", _API)
 
 
-class AudioSpectrogram:
+class AudioSpectrogram(Stage):
     """Spectrogram of n_channels receivers' int16 audio rows (include/asdr_spectrogram.h): frames of n_fft samples (a power of two in
     128 .. 8192) every hop samples (n_fft / 16 .. n_fft, default n_fft / 2), of which the bins first_bin .. first_bin + n_bins - 1
     (default: all n_fft / 2 + 1) are written per frame, as |X|^2 (kind "power") or (re, im) (kind "complex"), float32, scaled by
     1 / n_fft and not window-corrected.  window: "rect", "hann" or a float32 array [n_fft].  device = NO_DEVICE (-1) gives the control
     plane and the state records only."""
+    _prefix = "asdr_spectrogram_"
 
     def __init__(self, n_channels, n_fft=8192, hop=None, first_bin=0, n_bins=None, window="hann", kind="power", device=0):
         self._L = _lib()
@@ -68,10 +54,9 @@ class AudioSpectrogram:
         n_bins = n_fft // 2 + 1 - int(first_bin) if n_bins is None else int(n_bins)
         if max(abs(int(n_channels)), abs(n_fft), abs(hop), abs(int(first_bin)), abs(n_bins)) >= 2**31:
             raise AsdrError("AudioSpectrogram: a parameter does not fit an int")
-        self._h = self._L.asdr_spectrogram_create(int(n_channels), n_fft, hop, int(first_bin), n_bins, SPECTROGRAM_WINDOWS.index(window),
-                                                  SPECTROGRAM_KINDS.index(kind), int(device))
-        if not self._h:
-            raise AsdrError("asdr_spectrogram_create failed: %s" % self._L.asdr_last_error().decode())
+        self._create("asdr_spectrogram_create",
+                     self._L.asdr_spectrogram_create(int(n_channels), n_fft, hop, int(first_bin), n_bins, SPECTROGRAM_WINDOWS.index(window),
+                                                     SPECTROGRAM_KINDS.index(kind), int(device)))
         self.n_channels = int(n_channels)
         self.n_fft, self.hop = int(self._L.asdr_spectrogram_n_fft(self._h)), int(self._L.asdr_spectrogram_hop(self._h))
         self.first_bin, self.n_bins = int(self._L.asdr_spectrogram_first_bin(self._h)), int(self._L.asdr_spectrogram_n_bins(self._h))
@@ -82,22 +67,6 @@ class AudioSpectrogram:
             except AsdrError:
                 self.close()
                 raise
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.asdr_spectrogram_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
 
     # the parameters
     @property
@@ -174,16 +143,4 @@ class AudioSpectrogram:
     def write_state(self, records, channels=None):
         """Writes int16 [k, n_fft] records into `channels` (default 0 .. k - 1); every channel is checked before one is written."""
         rec = np.ascontiguousarray(records, dtype=np.int16).reshape(-1, self.n_fft)
-        chp = None
-        if channels is not None:
-            ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
-            if ch.size != rec.shape[0]:
-                raise AsdrError("write_state: %d records for %d channels" % (rec.shape[0], ch.size))
-            chp = ch.ctypes.data_as(C.POINTER(C.c_int))
-        self._chk(self._L.asdr_spectrogram_write_state(self._h, chp, int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))
-
-    def reset(self):
-        self._chk(self._L.asdr_spectrogram_reset(self._h))
-
-    def synchronize(self):
-        self._chk(self._L.asdr_spectrogram_synchronize(self._h))
+        self._chk(self._L.asdr_spectrogram_write_state(self._h, _channel_ptr(channels, rec.shape[0]), int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))

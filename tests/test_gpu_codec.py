@@ -333,6 +333,26 @@ def test_deliver_into_pageable_and_pinned_memory(gpu, kind, pinned):
     codec.close()
 
 
+def test_deliver_grows_its_kept_buffer_and_reuses_it(gpu):
+    """deliver's packet buffer is kept between calls: a call of 128 samples, one of 512 that needs a larger buffer, one of 256 that
+    fits what the second left; every call's count, index and rows are the reference's, the ADPCM state running through all three."""
+    import torch
+    rng = np.random.default_rng(32)
+    n = 3
+    codec, ref = gpu.AudioCodec(n, kind="adpcm"), CR.CodecRef(n, "adpcm")
+    for ns in (128, 512, 256):
+        x = full_range(rng, n, ns)
+        d_x = torch.from_numpy(x).cuda()
+        torch.cuda.synchronize()
+        count, index, rows = codec.deliver(d_x.data_ptr(), ns)
+        chans, want = ref.encode(x)
+        assert count == n and index.tolist() == chans.tolist() == [0, 1, 2]
+        assert rows.shape == (n, CR.padded_bytes(ref.kind, ns)) and np.array_equal(rows, want)
+    st = codec.read_state()
+    assert list(zip(st["predictor"].tolist(), st["step_index"].tolist(), st["reserved"].tolist())) == ref.state_tuples()
+    codec.close()
+
+
 # ---- state
 def test_records_move_between_codecs_and_reset(gpu):
     """Read after two calls and written into other channels of a second codec: each channel continues bit for bit as in a codec

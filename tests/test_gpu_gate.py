@@ -342,6 +342,23 @@ def test_capacity_below_count(gpu, nb):
     r.close()
 
 
+def test_deliver_grows_its_kept_buffers_and_reuses_them(gpu):
+    """deliver's packet buffer and the scratch of block energies are kept between calls: a call of 1 block, one of 4 blocks that
+    needs both larger, one of 2 blocks that fits what the second left.  All 3 channels are open (the default squelch), so the packet
+    is 3 n_blocks rows of 256 bytes each time; every call's index and rows are the reference's."""
+    rng = np.random.default_rng(31)
+    r = Rig(gpu, 3)
+    for nb in (1, 4, 2):
+        audio = mixed_rows(rng, 3, nb)
+        d_audio = r.torch.from_numpy(audio).cuda()
+        index, rows = r.gate.deliver(d_audio.data_ptr(), nb)
+        want_index, want_rows, _ = r.ref.update(audio)
+        assert want_index.tolist() == [0, 1, 2] and want_rows.shape == (3, nb, 128)
+        assert np.array_equal(index, want_index) and np.array_equal(rows, want_rows)
+        r.check_state()
+    r.close()
+
+
 def test_update_device_refusals_change_nothing(gpu):
     import torch
     r = Rig(gpu, 10)
