@@ -22,5 +22,7 @@ from .codec import (CODEC_EXPORTS, CODEC_KINDS, CODEC_MAX_SAMPLES, CODEC_STATE_D
                     codec_row_bytes)
 from .spectrogram import (SPECTROGRAM_EXPORTS, SPECTROGRAM_KINDS, SPECTROGRAM_MAX_SAMPLES, SPECTROGRAM_SIZES,  # noqa: E402
                           SPECTROGRAM_WINDOWS, AudioSpectrogram)
+from .fm import (FM_CHUNK_BLOCKS, FM_EXPORTS, FM_MAX_NOISE, FM_NARROW_ROWS, FM_ROWS, FM_STATE_DTYPE,  # noqa: E402
+                 FM_WIDE_CHANNELS, FmDemodulator, fm_deemphasis_from_tau_us, fm_gain_from_deviation)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -1,7 +1,8 @@
-// asdr_stage_host.h -- what the host sides of the audio stages (gate, resampler, codec, spectrogram) share: the device, stream and
-// event of a handle and the rules that order its work (a launch on another stream than the last waits for the last; whatever frees
-// or rewrites what a launch may still use waits for the handle's work first), the kept grow-on-demand buffer, the record I/O of
-// read_state / write_state, and the double buffer of carry rows.  An ASDR_NO_DEVICE handle never reaches HIP through these.
+// asdr_stage_host.h -- what the host sides of the audio stages (gate, resampler, codec, spectrogram, FM demodulator) share: the
+// device, stream and event of a handle and the rules that order its work (a launch on another stream than the last waits for the
+// last; whatever frees or rewrites what a launch may still use waits for the handle's work first), the kept grow-on-demand buffer,
+// the record I/O of read_state / write_state, and the double buffer of carry rows.  An ASDR_NO_DEVICE handle never reaches HIP
+// through these.
 // Internal and header-only; the front end and the tuner bank take HIPCHK, fail, overlap and the device check from here.
 #pragma once
 #include <hip/hip_runtime.h>
