@@ -24,5 +24,7 @@ from .spectrogram import (SPECTROGRAM_EXPORTS, SPECTROGRAM_KINDS, SPECTROGRAM_MA
                           SPECTROGRAM_WINDOWS, AudioSpectrogram)
 from .fm import (FM_CHUNK_BLOCKS, FM_EXPORTS, FM_MAX_NOISE, FM_NARROW_ROWS, FM_ROWS, FM_STATE_DTYPE,  # noqa: E402
                  FM_WIDE_CHANNELS, FmDemodulator, fm_deemphasis_from_tau_us, fm_gain_from_deviation)
+from .tone import (CTCSS_TONES, TONE_ANY, TONE_EXPORTS, TONE_MAX_TONES, TONE_PASS, TONE_ROWS, TONE_STATE_DTYPE,  # noqa: E402
+                   TONE_WAVE_ROWS, ToneSquelch, tone_highpass_design, tone_min_power)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

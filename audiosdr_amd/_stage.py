@@ -1,4 +1,4 @@
-"""What the ctypes mirrors of the audio stages (gate.py, resample.py, codec.py, spectrogram.py, fm.py) share: the typing of a stage's
+"""What the ctypes mirrors of the audio stages (gate.py, resample.py, codec.py, spectrogram.py, fm.py, tone.py) share: the typing of a stage's
 entry points, the life of a handle, and the channel list of write_state."""
 import ctypes as C
 
