@@ -1,5 +1,5 @@
-"""What the ctypes mirrors of the audio stages (gate.py, resample.py, codec.py, spectrogram.py, fm.py, tone.py) share: the typing of a stage's
-entry points, the life of a handle, and the channel list of write_state."""
+"""What the ctypes mirrors of every handle but the receiver batch (gate.py, resample.py, codec.py, spectrogram.py, fm.py, tone.py, tuner.py,
+front.py) share: the typing of a handle's entry points, the life of a handle, and the channel list of write_state."""
 import ctypes as C
 
 import numpy as np
@@ -60,8 +60,12 @@ class Stage:
             raise AsdrError(self._L.asdr_last_error().decode())
         return rc
 
-    def reset(self):
-        self._call("reset")
-
     def synchronize(self):
         self._call("synchronize")
+
+
+class ResetStage(Stage):
+    """A handle whose C API has <prefix>reset (every one but the front end's three)."""
+
+    def reset(self):
+        self._call("reset")

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
 from .binding import AsdrError
 
 CODEC_EXPORTS = ["asdr_codec_create", "asdr_codec_destroy", "asdr_codec_n_channels", "asdr_codec_kind", "asdr_codec_row_bytes",
@@ -43,7 +43,7 @@ def _fits_long(*values):
         raise AsdrError("codec: argument out of range")
 
 
-class AudioCodec(Stage):
+class AudioCodec(ResetStage):
     """Encoder of n_channels receivers' int16 audio rows into packet rows of one kind (include/asdr_codec.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
     _prefix = "asdr_codec_"

@@ -14,59 +14,25 @@ int ensure_tables() {   // __constant__ tables are per device: (re)uploaded for 
   return 0;
 }
 
-struct DevBase {
-  int n = 0, device = ASDR_NO_DEVICE;
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool ev_valid = false;
-  int16_t *d_io[4] = {nullptr, nullptr, nullptr, nullptr};   // staging for the host-pointer entry points
+// what the three batches share beyond StageDev: the staging of the host-pointer entry points, one kept buffer
+struct FrontDev : StageDev {
+  void *d_io = nullptr;
   size_t io_cap = 0;
 };
 
-int dev_init(DevBase &d, int n, int device) {
-  d.n = n; d.device = device;
+// the device side of a new batch (nothing for ASDR_NO_DEVICE): stream, both events, the tables
+int front_open(FrontDev &d, int n, int device, const char *what) {
+  d.n = n;
   if (device == ASDR_NO_DEVICE) return 0;
-  if (stage_check_device(device) != 0) return -1;
-  HIPCHK(hipSetDevice(device));
-  if (ensure_tables() != 0) return -1;
-  HIPCHK(hipStreamCreate(&d.stream));
-  HIPCHK(hipEventCreate(&d.ev0));
-  HIPCHK(hipEventCreate(&d.ev1));
+  if (stage_open(d, device, what, true) != 0) return -1;
+  return ensure_tables();
+}
+// `slices` staging rows of `count` int16 each, cut from the kept buffer; every row starts 256-byte aligned
+int front_stage(FrontDev &d, size_t count, int slices, int16_t **row) {
+  const size_t pad = (count * sizeof(int16_t) + 255) & ~(size_t)255;
+  if (stage_reserve(d, &d.d_io, &d.io_cap, slices * pad) != 0) return -1;
+  for (int k = 0; k < slices; k++) row[k] = (int16_t *)((char *)d.d_io + k * pad);
   return 0;
-}
-void dev_fini(DevBase &d) {
-  if (d.device == ASDR_NO_DEVICE) return;
-  hipSetDevice(d.device);
-  hipDeviceSynchronize();
-  for (int16_t *p : d.d_io) if (p) hipFree(p);
-  if (d.ev0) hipEventDestroy(d.ev0);
-  if (d.ev1) hipEventDestroy(d.ev1);
-  if (d.stream) hipStreamDestroy(d.stream);
-}
-int dev_stage(DevBase &d, size_t count) {   // staging buffers of `count` int16 each
-  if (count <= d.io_cap) return 0;
-  HIPCHK(hipStreamSynchronize(d.stream));
-  for (int i = 0; i < 4; i++) {
-    if (d.d_io[i]) HIPCHK(hipFree(d.d_io[i]));
-    d.d_io[i] = nullptr;
-    HIPCHK(hipMalloc(&d.d_io[i], count * sizeof(int16_t)));
-  }
-  d.io_cap = count;
-  return 0;
-}
-int dev_sync(DevBase &d) {
-  if (d.device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(d.device));
-  HIPCHK(hipStreamSynchronize(d.last_stream));   // nullptr = the null stream
-  HIPCHK(hipStreamSynchronize(d.stream));
-  return 0;
-}
-float dev_last_ms(DevBase &d) {
-  if (!d.ev_valid) return -1.0f;
-  float ms = -1.0f;
-  if (hipEventSynchronize(d.ev1) != hipSuccess) return -1.0f;
-  if (hipEventElapsedTime(&ms, d.ev0, d.ev1) != hipSuccess) return -1.0f;
-  return ms;
 }
 int check_io(const char *what, int n_blocks, long in_stride, long out_stride, uintptr_t ptr_bits) {
   if (in_stride < n_blocks || out_stride < n_blocks) return fail(std::string(what) + ": row stride shorter than n_blocks");
@@ -78,7 +44,7 @@ const char *kNoDevice = "control-plane-only batch (ASDR_NO_DEVICE): the signal p
 }  // namespace
 
 // ============================== AudioSDRpreProcessor ==============================
-struct asdr_pre_batch : DevBase {
+struct asdr_pre_batch : FrontDev {
   std::vector<asdr_pre_state_t> host;   // mirror of the device state
   asdr_pre_state_t *d_state = nullptr;
   bool host_dirty = true;               // a setter changed the mirror since the last push
@@ -88,7 +54,7 @@ struct asdr_pre_batch : DevBase {
 namespace {
 int pre_pull(asdr_pre_batch *p) {
   if (p->device == ASDR_NO_DEVICE || !p->device_newer) return 0;
-  if (dev_sync(*p) != 0) return -1;
+  if (stage_quiesce(*p) != 0) return -1;
   HIPCHK(hipMemcpy(p->host.data(), p->d_state, p->n * sizeof(asdr_pre_state_t), hipMemcpyDeviceToHost));
   p->device_newer = false;
   return 0;
@@ -107,22 +73,21 @@ void pre_each(asdr_pre_batch *p, int ch, F f) {
 extern "C" {
 
 asdr_pre_t *asdr_pre_create(int n_channels, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_pre_batch *p = new asdr_pre_batch();
-  if (dev_init(*p, n_channels, device) != 0) { delete p; return nullptr; }
   asdr_pre_state_t z;
   memset(&z, 0, sizeof z);              // AudioSDRpreProcessor.h:72-83: correction 0, counters 0, no swap, autoDetectFlag false
   p->host.assign(n_channels, z);
+  if (front_open(*p, n_channels, device, "pre-processor") != 0) { asdr_pre_destroy(p); return nullptr; }
   if (device != ASDR_NO_DEVICE && hipMalloc(&p->d_state, n_channels * sizeof(asdr_pre_state_t)) != hipSuccess) {
-    fail("out of device memory"); dev_fini(*p); delete p; return nullptr;
+    fail("out of device memory"); asdr_pre_destroy(p); return nullptr;
   }
   return p;
 }
 
 void asdr_pre_destroy(asdr_pre_t *p) {
   if (!p) return;
-  dev_fini(*p);
-  if (p->d_state) hipFree(p->d_state);
+  stage_close(*p, {p->d_io, p->d_state});
   delete p;
 }
 
@@ -138,7 +103,7 @@ int asdr_pre_update_device(asdr_pre_t *p, const int16_t *dI, const int16_t *dQ, 
   if (check_io("asdr_pre_update_device", n_blocks, in_stride_blocks, out_stride_blocks,
                (uintptr_t)dI | (uintptr_t)dQ | (uintptr_t)dIout | (uintptr_t)dQout) != 0) return -1;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(p->device));
+  if (stage_before_launch(*p, stream) != 0) return -1;
   if (p->host_dirty) {
     if (pre_pull(p) != 0) return -1;    // (a setter always pulls first; this is for the very first launch)
     HIPCHK(hipMemcpyAsync(p->d_state, p->host.data(), p->n * sizeof(asdr_pre_state_t), hipMemcpyHostToDevice, stream));
@@ -148,11 +113,10 @@ int asdr_pre_update_device(asdr_pre_t *p, const int16_t *dI, const int16_t *dQ, 
   PreArgs a;
   a.state = p->d_state; a.in_i = dI; a.in_q = dQ; a.out_i = dIout; a.out_q = dQout;
   a.n_channels = p->n; a.n_blocks = n_blocks; a.in_stride = (int32_t)in_stride_blocks; a.out_stride = (int32_t)out_stride_blocks;
-  HIPCHK(hipEventRecord(p->ev0, stream));
+  if (stage_mark_start(*p, stream) != 0) return -1;
   if (asdr_launch_pre(&a, stream) != 0) return fail("pre-processor kernel launch failed");
-  HIPCHK(hipEventRecord(p->ev1, stream));
-  p->ev_valid = true; p->last_stream = stream; p->device_newer = true;
-  return 0;
+  p->device_newer = true;
+  return stage_after_launch(*p, stream);
 }
 
 int asdr_pre_update(asdr_pre_t *p, int16_t *I, int16_t *Q, int n_blocks) {
@@ -162,18 +126,19 @@ int asdr_pre_update(asdr_pre_t *p, int16_t *I, int16_t *Q, int n_blocks) {
   if (n_blocks <= 0) return 0;
   HIPCHK(hipSetDevice(p->device));
   const size_t count = (size_t)p->n * n_blocks * ASDR_N;
-  if (dev_stage(*p, count) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(p->d_io[0], I, count * sizeof(int16_t), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemcpyAsync(p->d_io[1], Q, count * sizeof(int16_t), hipMemcpyHostToDevice, p->stream));
-  if (asdr_pre_update_device(p, p->d_io[0], p->d_io[1], p->d_io[0], p->d_io[1], n_blocks, n_blocks, n_blocks, p->stream) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(I, p->d_io[0], count * sizeof(int16_t), hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipMemcpyAsync(Q, p->d_io[1], count * sizeof(int16_t), hipMemcpyDeviceToHost, p->stream));
+  int16_t *d[2];
+  if (front_stage(*p, count, 2, d) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(d[0], I, count * sizeof(int16_t), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemcpyAsync(d[1], Q, count * sizeof(int16_t), hipMemcpyHostToDevice, p->stream));
+  if (asdr_pre_update_device(p, d[0], d[1], d[0], d[1], n_blocks, n_blocks, n_blocks, p->stream) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(I, d[0], count * sizeof(int16_t), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipMemcpyAsync(Q, d[1], count * sizeof(int16_t), hipMemcpyDeviceToHost, p->stream));
   HIPCHK(hipStreamSynchronize(p->stream));
   return 0;
 }
 
-int asdr_pre_synchronize(asdr_pre_t *p) { return p ? dev_sync(*p) : fail("null batch"); }
-float asdr_pre_last_kernel_ms(asdr_pre_t *p) { return p ? dev_last_ms(*p) : -1.0f; }
+int asdr_pre_synchronize(asdr_pre_t *p) { return p ? stage_quiesce(*p) : fail("null batch"); }
+float asdr_pre_last_kernel_ms(asdr_pre_t *p) { return p ? stage_last_ms(*p) : -1.0f; }
 
 void asdr_pre_startAutoI2SerrorDetection(asdr_pre_t *p, int ch) {
   pre_each(p, ch, [](asdr_pre_state_t &s) { s.auto_detect = 1; s.correction = 0; s.failure_count = 0; s.success_count = 0; });
@@ -206,7 +171,7 @@ int asdr_pre_read_state(asdr_pre_t *p, asdr_pre_state_t *dst) {
 }  // extern "C"
 
 // ============================== AudioIQgenerator ==============================
-struct asdr_iqgen_batch : DevBase {
+struct asdr_iqgen_batch : FrontDev {
   std::vector<float> gains;   // [n][2]: gainI, gainQ (AudioIQgenerator.h:69-70)
   float *d_gains = nullptr;
   int16_t *d_hist = nullptr;   // [n][2][128]: raw ring of the two carried blocks
@@ -217,15 +182,15 @@ struct asdr_iqgen_batch : DevBase {
 extern "C" {
 
 asdr_iqgen_t *asdr_iqgen_create(int n_channels, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_iqgen_batch *g = new asdr_iqgen_batch();
-  if (dev_init(*g, n_channels, device) != 0) { delete g; return nullptr; }
   g->gains.assign(2 * (size_t)n_channels, 1.0f);
+  if (front_open(*g, n_channels, device, "IQ generator") != 0) { asdr_iqgen_destroy(g); return nullptr; }
   if (device != ASDR_NO_DEVICE) {
     if (hipMalloc(&g->d_gains, 2 * (size_t)n_channels * sizeof(float)) != hipSuccess ||
         hipMalloc(&g->d_hist, 256 * (size_t)n_channels * sizeof(int16_t)) != hipSuccess ||
         hipMemset(g->d_hist, 0, 256 * (size_t)n_channels * sizeof(int16_t)) != hipSuccess) {   // static buffers start zeroed (.cpp:37-38)
-      fail("out of device memory"); if (g->d_gains) hipFree(g->d_gains); if (g->d_hist) hipFree(g->d_hist); dev_fini(*g); delete g; return nullptr;
+      fail("out of device memory"); asdr_iqgen_destroy(g); return nullptr;
     }
     hipDeviceSynchronize();
   }
@@ -233,9 +198,7 @@ asdr_iqgen_t *asdr_iqgen_create(int n_channels, int device) {
 }
 void asdr_iqgen_destroy(asdr_iqgen_t *g) {
   if (!g) return;
-  dev_fini(*g);
-  if (g->d_gains) hipFree(g->d_gains);
-  if (g->d_hist) hipFree(g->d_hist);
+  stage_close(*g, {g->d_io, g->d_gains, g->d_hist});
   delete g;
 }
 int asdr_iqgen_n_channels(const asdr_iqgen_t *g) { return g ? g->n : 0; }
@@ -257,7 +220,7 @@ int asdr_iqgen_update_device(asdr_iqgen_t *g, const int16_t *dIn, int16_t *dI, i
   if (n_blocks <= 0) return 0;
   if (check_io("asdr_iqgen_update_device", n_blocks, in_stride_blocks, out_stride_blocks, (uintptr_t)dIn | (uintptr_t)dI | (uintptr_t)dQ) != 0) return -1;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(g->device));
+  if (stage_before_launch(*g, stream) != 0) return -1;
   if (g->gains_dirty) {
     HIPCHK(hipMemcpyAsync(g->d_gains, g->gains.data(), g->gains.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -266,12 +229,10 @@ int asdr_iqgen_update_device(asdr_iqgen_t *g, const int16_t *dIn, int16_t *dI, i
   IqgenArgs a;
   a.hist = g->d_hist; a.phase = g->phase; a.gains = g->d_gains; a.in = dIn; a.out_i = dI; a.out_q = dQ;
   a.n_channels = g->n; a.n_blocks = n_blocks; a.in_stride = (int32_t)in_stride_blocks; a.out_stride = (int32_t)out_stride_blocks;
-  HIPCHK(hipEventRecord(g->ev0, stream));
+  if (stage_mark_start(*g, stream) != 0) return -1;
   if (asdr_launch_iqgen(&a, stream) != 0) return fail("IQ generator kernel launch failed");
   g->phase = (g->phase + (uint32_t)n_blocks) & 1u;
-  HIPCHK(hipEventRecord(g->ev1, stream));
-  g->ev_valid = true; g->last_stream = stream;
-  return 0;
+  return stage_after_launch(*g, stream);
 }
 
 int asdr_iqgen_update(asdr_iqgen_t *g, const int16_t *in, int16_t *I, int16_t *Q, int n_blocks) {
@@ -282,21 +243,22 @@ int asdr_iqgen_update(asdr_iqgen_t *g, const int16_t *in, int16_t *I, int16_t *Q
   if (n_blocks <= 0) return 0;
   HIPCHK(hipSetDevice(g->device));
   const size_t count = (size_t)g->n * n_blocks * ASDR_N;
-  if (dev_stage(*g, count) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(g->d_io[0], in, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
-  if (asdr_iqgen_update_device(g, g->d_io[0], g->d_io[1], g->d_io[2], n_blocks, n_blocks, n_blocks, g->stream) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(I, g->d_io[1], count * sizeof(int16_t), hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipMemcpyAsync(Q, g->d_io[2], count * sizeof(int16_t), hipMemcpyDeviceToHost, g->stream));
+  int16_t *d[3];
+  if (front_stage(*g, count, 3, d) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(d[0], in, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
+  if (asdr_iqgen_update_device(g, d[0], d[1], d[2], n_blocks, n_blocks, n_blocks, g->stream) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(I, d[1], count * sizeof(int16_t), hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipMemcpyAsync(Q, d[2], count * sizeof(int16_t), hipMemcpyDeviceToHost, g->stream));
   HIPCHK(hipStreamSynchronize(g->stream));
   return 0;
 }
-int asdr_iqgen_synchronize(asdr_iqgen_t *g) { return g ? dev_sync(*g) : fail("null batch"); }
-float asdr_iqgen_last_kernel_ms(asdr_iqgen_t *g) { return g ? dev_last_ms(*g) : -1.0f; }
+int asdr_iqgen_synchronize(asdr_iqgen_t *g) { return g ? stage_quiesce(*g) : fail("null batch"); }
+float asdr_iqgen_last_kernel_ms(asdr_iqgen_t *g) { return g ? stage_last_ms(*g) : -1.0f; }
 
 }  // extern "C"
 
 // ============================== AudioGrabberComplex256 ==============================
-struct asdr_grab_batch : DevBase {
+struct asdr_grab_batch : FrontDev {
   int16_t *d_buffer = nullptr, *d_out = nullptr;
   float *d_spec = nullptr;          // staging for the host-destination spectrum call
   int parity = 0;                   // _buffStart / 256: identical for every channel, updates are batch-wide
@@ -307,15 +269,15 @@ struct asdr_grab_batch : DevBase {
 extern "C" {
 
 asdr_grab_t *asdr_grab_create(int n_channels, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
+  if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_grab_batch *g = new asdr_grab_batch();
-  if (dev_init(*g, n_channels, device) != 0) { delete g; return nullptr; }
   g->new_data.assign(n_channels, 0);
+  if (front_open(*g, n_channels, device, "grabber") != 0) { asdr_grab_destroy(g); return nullptr; }
   if (device != ASDR_NO_DEVICE) {
     const size_t bytes = 512 * (size_t)n_channels * sizeof(int16_t);
     if (hipMalloc(&g->d_buffer, bytes) != hipSuccess || hipMalloc(&g->d_out, bytes) != hipSuccess ||
         hipMemset(g->d_buffer, 0, bytes) != hipSuccess || hipMemset(g->d_out, 0, bytes) != hipSuccess) {
-      fail("out of device memory"); if (g->d_buffer) hipFree(g->d_buffer); if (g->d_out) hipFree(g->d_out); dev_fini(*g); delete g; return nullptr;
+      fail("out of device memory"); asdr_grab_destroy(g); return nullptr;
     }
     hipDeviceSynchronize();
   }
@@ -323,10 +285,7 @@ asdr_grab_t *asdr_grab_create(int n_channels, int device) {
 }
 void asdr_grab_destroy(asdr_grab_t *g) {
   if (!g) return;
-  dev_fini(*g);
-  if (g->d_buffer) hipFree(g->d_buffer);
-  if (g->d_out) hipFree(g->d_out);
-  if (g->d_spec) hipFree(g->d_spec);
+  stage_close(*g, {g->d_io, g->d_buffer, g->d_out, g->d_spec});
   delete g;
 }
 int asdr_grab_n_channels(const asdr_grab_t *g) { return g ? g->n : 0; }
@@ -338,14 +297,13 @@ int asdr_grab_update_device(asdr_grab_t *g, const int16_t *dI, const int16_t *dQ
   if (n_blocks <= 0) return 0;
   if (check_io("asdr_grab_update_device", n_blocks, in_stride_blocks, in_stride_blocks, (uintptr_t)dI | (uintptr_t)dQ) != 0) return -1;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(g->device));
+  if (stage_before_launch(*g, stream) != 0) return -1;
   GrabArgs a;
   a.buffer = g->d_buffer; a.out_buffer = g->d_out; a.in_i = dI; a.in_q = dQ;
   a.n_channels = g->n; a.n_blocks = n_blocks; a.in_stride = (int32_t)in_stride_blocks; a.parity = g->parity;
-  HIPCHK(hipEventRecord(g->ev0, stream));
+  if (stage_mark_start(*g, stream) != 0) return -1;
   if (asdr_launch_grab(&a, stream) != 0) return fail("grabber kernel launch failed");
-  HIPCHK(hipEventRecord(g->ev1, stream));
-  g->ev_valid = true; g->last_stream = stream;
+  if (stage_after_launch(*g, stream) != 0) return -1;
   const int total = g->parity + n_blocks;
   if (total >= 2) { g->valid = true; std::fill(g->new_data.begin(), g->new_data.end(), (uint8_t)1); }   // .cpp:62-68
   g->parity = total & 1;
@@ -359,10 +317,11 @@ int asdr_grab_update(asdr_grab_t *g, const int16_t *I, const int16_t *Q, int n_b
   if (n_blocks <= 0) return 0;
   HIPCHK(hipSetDevice(g->device));
   const size_t count = (size_t)g->n * n_blocks * ASDR_N;
-  if (dev_stage(*g, count) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(g->d_io[0], I, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
-  HIPCHK(hipMemcpyAsync(g->d_io[1], Q, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
-  if (asdr_grab_update_device(g, g->d_io[0], g->d_io[1], n_blocks, n_blocks, g->stream) != 0) return -1;
+  int16_t *d[2];
+  if (front_stage(*g, count, 2, d) != 0) return -1;
+  HIPCHK(hipMemcpyAsync(d[0], I, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
+  HIPCHK(hipMemcpyAsync(d[1], Q, count * sizeof(int16_t), hipMemcpyHostToDevice, g->stream));
+  if (asdr_grab_update_device(g, d[0], d[1], n_blocks, n_blocks, g->stream) != 0) return -1;
   HIPCHK(hipStreamSynchronize(g->stream));
   return 0;
 }
@@ -376,7 +335,7 @@ int asdr_grab_grab(asdr_grab_t *g, int ch, int16_t *destination) {
   int copied = 0;
   if (g->valid) {                       // .cpp:81-86
     if (g->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-    if (dev_sync(*g) != 0) return -1;
+    if (stage_quiesce(*g) != 0) return -1;
     HIPCHK(hipMemcpy(destination, g->d_out + (size_t)ch * 512, 512 * sizeof(int16_t), hipMemcpyDeviceToHost));
     copied = 1;
   }
@@ -390,7 +349,7 @@ int asdr_grab_grab_all(asdr_grab_t *g, int16_t *destination) {
   int copied = 0;
   if (g->valid) {
     if (g->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-    if (dev_sync(*g) != 0) return -1;
+    if (stage_quiesce(*g) != 0) return -1;
     HIPCHK(hipMemcpy(destination, g->d_out, (size_t)g->n * 512 * sizeof(int16_t), hipMemcpyDeviceToHost));
     copied = 1;
   }
@@ -407,10 +366,9 @@ int asdr_grab_power_spectrum_device(asdr_grab_t *g, float *dDestination, void *s
   if (((uintptr_t)dDestination & 15u) != 0) return fail("asdr_grab_power_spectrum_device: device pointers must be 16-byte aligned");
   if (!g->valid) return 0;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(g->device));
-  if (stream != g->last_stream) HIPCHK(hipStreamSynchronize(g->last_stream));   // the buffers were written on the update stream
+  if (stage_before_launch(*g, stream) != 0) return -1;   // the buffers were written on the update stream
   if (asdr_launch_grab_spectrum(g->d_out, dDestination, g->n, stream) != 0) return fail("spectrum kernel launch failed");
-  return 1;
+  return stage_after_launch(*g, stream) != 0 ? -1 : 1;
 }
 
 int asdr_grab_power_spectrum(asdr_grab_t *g, float *destination) {
@@ -426,6 +384,6 @@ int asdr_grab_power_spectrum(asdr_grab_t *g, float *destination) {
   HIPCHK(hipStreamSynchronize(g->stream));
   return 1;
 }
-int asdr_grab_synchronize(asdr_grab_t *g) { return g ? dev_sync(*g) : fail("null batch"); }
+int asdr_grab_synchronize(asdr_grab_t *g) { return g ? stage_quiesce(*g) : fail("null batch"); }
 
 }  // extern "C"

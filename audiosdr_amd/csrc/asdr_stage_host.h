@@ -1,9 +1,11 @@
-// asdr_stage_host.h -- what the host sides of the audio stages (gate, resampler, codec, spectrogram, FM demodulator) share: the
-// device, stream and event of a handle and the rules that order its work (a launch on another stream than the last waits for the
-// last; whatever frees or rewrites what a launch may still use waits for the handle's work first), the kept grow-on-demand buffer,
-// the record I/O of read_state / write_state, and the double buffer of carry rows.  An ASDR_NO_DEVICE handle never reaches HIP
-// through these.
-// Internal and header-only; the front end and the tuner bank take HIPCHK, fail, overlap and the device check from here.
+// asdr_stage_host.h -- what the host sides of every handle but the receiver batch share (the audio stages: gate, resampler, codec,
+// spectrogram, FM demodulator, tone squelch; the tuner bank; the front end's three batches): the device, stream and events of a
+// handle and the rules that order its work (a launch on another stream than the last waits for the last; whatever frees or rewrites
+// what a launch may still use waits for the handle's work first), the kept grow-on-demand buffer, the record I/O of read_state /
+// write_state, and the double buffer of carry rows.  The tuner bank and the front end also time a call's launches (*_last_kernel_ms)
+// between a start event, which only a handle opened `timed` has, and the event behind the launches.  An ASDR_NO_DEVICE handle never
+// reaches HIP through these.
+// Internal and header-only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,15 +42,17 @@ struct StageDev {
   int n = 0, device = ASDR_NO_DEVICE;
   hipStream_t stream = nullptr, last_stream = nullptr;   // the handle's own stream; the stream of the last launch
   hipEvent_t ev = nullptr;                               // recorded behind every launch
+  hipEvent_t ev_start = nullptr;                         // timed handles: recorded in front of a call's launches
   bool ev_valid = false;
 };
 
-// the device of a handle that is not ASDR_NO_DEVICE, its stream and its event; `what` names the stage in the error text.  A handle
-// whose device index was refused stays ASDR_NO_DEVICE, so that stage_close leaves HIP alone
-static inline int stage_open(StageDev &d, int device, const char *what) {
+// the device of a handle that is not ASDR_NO_DEVICE, its stream and its event (a timed handle's two); `what` names the stage in the
+// error text.  A handle whose device index was refused stays ASDR_NO_DEVICE, so that stage_close leaves HIP alone
+static inline int stage_open(StageDev &d, int device, const char *what, bool timed = false) {
   if (stage_check_device(device) != 0) return -1;
   d.device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&d.stream) != hipSuccess || hipEventCreate(&d.ev) != hipSuccess)
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&d.stream) != hipSuccess || hipEventCreate(&d.ev) != hipSuccess ||
+      (timed && hipEventCreate(&d.ev_start) != hipSuccess))
     return fail(std::string(what) + ": device allocation failed");
   return 0;
 }
@@ -74,6 +78,20 @@ static inline int stage_after_launch(StageDev &d, hipStream_t stream) {
   return 0;
 }
 
+// a timed handle: between the pushes of a call and its launches; stage_last_ms is the time between this and stage_after_launch's
+// event, -1 without a recorded pair
+static inline int stage_mark_start(StageDev &d, hipStream_t stream) {
+  if (d.ev_start) HIPCHK(hipEventRecord(d.ev_start, stream));
+  return 0;
+}
+static inline float stage_last_ms(StageDev &d) {
+  if (!d.ev_start || !d.ev_valid) return -1.0f;
+  float ms = -1.0f;
+  if (hipEventSynchronize(d.ev) != hipSuccess) return -1.0f;
+  if (hipEventElapsedTime(&ms, d.ev_start, d.ev) != hipSuccess) return -1.0f;
+  return ms;
+}
+
 // a device buffer of at least `bytes`, kept; growing waits for the work that may still use the old one
 static inline int stage_reserve(StageDev &d, void **p, size_t *cap, size_t bytes) {
   if (bytes <= *cap) return 0;
@@ -85,7 +103,7 @@ static inline int stage_reserve(StageDev &d, void **p, size_t *cap, size_t bytes
   return 0;
 }
 
-// waits for the handle's work, then frees its buffers, its event and its stream
+// waits for the handle's work, then frees its buffers, its events and its stream
 static inline void stage_close(StageDev &d, std::initializer_list<void *> buffers) {
   if (d.device == ASDR_NO_DEVICE) return;
   hipSetDevice(d.device);
@@ -94,6 +112,7 @@ static inline void stage_close(StageDev &d, std::initializer_list<void *> buffer
   for (void *p : buffers)
     if (p) hipFree(p);
   if (d.ev) hipEventDestroy(d.ev);
+  if (d.ev_start) hipEventDestroy(d.ev_start);
   if (d.stream) hipStreamDestroy(d.stream);
 }
 

@@ -133,8 +133,8 @@ std::string resampler_error(int U, const int16_t *h2, int n_taps, int g2) {
 }
 }  // namespace
 
-struct asdr_tuner_bank {
-  int n = 0, n_src = 0, D = 1, device = ASDR_NO_DEVICE;
+struct asdr_tuner_bank : StageDev {
+  int n_src = 0, D = 1;
   int fmt = ASDR_TUNER_IN_CS16;       // input format of the next call's rows
   long long pos = 0;
   // rate bank (stage 2): Fs_in, U / M, the prototype [U K] and g2, output samples written
@@ -196,10 +196,7 @@ struct asdr_tuner_bank {
   int32_t *d_order = nullptr, *d_taps = nullptr, *d_hist[2] = {nullptr, nullptr};
   int cur = 0;                        // d_hist[cur] holds the samples before pos
   int n_rows = 1, n_pairs = 1;        // A, DP2 of the pushed taps
-  hipStream_t stream = nullptr, last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool ev_valid = false;
-  void *d_io = nullptr;               // staging for asdr_tuner_update
+  void *d_io = nullptr;               // staging for the host-pointer entry points
   size_t io_cap = 0;
   // stage 2: taps [U][KP] + the lane table, the carry rows (double-buffered, allocated by the first stage-2 call), the intermediate
   int16_t *d_rs_taps = nullptr;
@@ -217,7 +214,7 @@ struct asdr_tuner_bank {
 };
 
 namespace {
-asdr_tuner_t *open_device(asdr_tuner_bank *t);
+asdr_tuner_t *open_device(asdr_tuner_bank *t, int device);
 
 asdr_tuner_state_t fresh_state() {
   asdr_tuner_state_t s;
@@ -392,14 +389,7 @@ int run_condition(asdr_tuner_t *t, const void *&in, long &in_stride, int &fmt, l
   if (t->n_cond == 0 && !t->iq_stats_on) return 0;
   const bool write = t->n_cond > 0, real = fmt == ASDR_TUNER_IN_RS16;
   if (write) {
-    const size_t bytes = (size_t)t->n_src * n_in * (real ? 2 : 4);
-    if (bytes > t->cond_cap) {   // grow the scratch: nothing of ours may be in flight
-      if (asdr_tuner_synchronize(t) != 0) return -1;
-      if (t->d_cond) HIPCHK(hipFree(t->d_cond));
-      t->d_cond = nullptr; t->cond_cap = 0;
-      HIPCHK(hipMalloc(&t->d_cond, bytes));
-      t->cond_cap = bytes;
-    }
+    if (stage_reserve(*t, &t->d_cond, &t->cond_cap, (size_t)t->n_src * n_in * (real ? 2 : 4)) != 0) return -1;
     if (t->corr_dirty || !t->d_corr) {
       if (!t->d_corr) HIPCHK(hipMalloc(&t->d_corr, (size_t)t->n_src * sizeof(asdr_tuner_iq_t)));
       HIPCHK(hipMemcpyAsync(t->d_corr, t->corr.data(), (size_t)t->n_src * sizeof(asdr_tuner_iq_t), hipMemcpyHostToDevice, stream));
@@ -424,21 +414,10 @@ int run_fastconv(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int f
   const int log2n = t->log2n, N = 1 << log2n, H = N / 2;
   const size_t x_floats = (size_t)t->n_src * n_frames * N * 2;
   const size_t x_bytes = (log2n > 12 ? 2 : 1) * x_floats * sizeof(float);
-  if (x_bytes > t->fc_x_cap) {   // grow X (and the scratch): nothing of ours may be in flight
-    if (asdr_tuner_synchronize(t) != 0) return -1;
-    if (t->d_fc_x) HIPCHK(hipFree(t->d_fc_x));
-    t->d_fc_x = nullptr; t->fc_x_cap = 0;
-    HIPCHK(hipMalloc(&t->d_fc_x, x_bytes));
-    t->fc_x_cap = x_bytes;
-  }
   const size_t part_bytes = t->lev_on ? (size_t)t->n * n_frames * sizeof(float) : 0;
-  if (part_bytes > t->lev_part_cap) {   // grow the levels' partials, likewise
-    if (asdr_tuner_synchronize(t) != 0) return -1;
-    if (t->d_lev_part) HIPCHK(hipFree(t->d_lev_part));
-    t->d_lev_part = nullptr; t->lev_part_cap = 0;
-    HIPCHK(hipMalloc(&t->d_lev_part, part_bytes));
-    t->lev_part_cap = part_bytes;
-  }
+  if (stage_reserve(*t, (void **)&t->d_fc_x, &t->fc_x_cap, x_bytes) != 0 ||   // X and the scratch; the levels' partials
+      stage_reserve(*t, (void **)&t->d_lev_part, &t->lev_part_cap, part_bytes) != 0)
+    return -1;
   FcForwardArgs f;
   f.in = (const int32_t *)dIQ; f.hist_rd = t->d_hist[t->cur]; f.hist_wr = t->d_hist[t->cur ^ 1];
   f.tw = t->d_fc_tab; f.x = t->d_fc_x; f.scratch = t->d_fc_x + x_floats;
@@ -510,9 +489,24 @@ int check_io(const asdr_tuner_t *t, const void *dIQ, long in_stride_samples, con
   return 0;
 }
 
+// the checks every create starts with
+int check_create(int n_channels, int n_sources) {
+  if (stage_check_create(n_channels) != 0) return -1;
+  return n_sources <= 0 || n_sources > 65535 ? fail("n_sources must be in 1..65535") : 0;
+}
+
+// a bank of either kind before its filters: geometry, ratio U / M, channels and sources in creation state
+asdr_tuner_bank *new_bank(int n_channels, int n_sources, long long fs_in, int dr, long long up, long long down) {
+  asdr_tuner_bank *t = new asdr_tuner_bank();
+  t->n = n_channels; t->n_src = n_sources; t->D = dr;
+  t->fs_in = fs_in; t->up = (int)up; t->down = (int)down;
+  t->chan.assign(n_channels, fresh_state());
+  t->corr.assign(n_sources, kIdentity);
+  return t;
+}
+
 asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int decimation, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
-  if (n_sources <= 0 || n_sources > 65535) { fail("n_sources must be in 1..65535"); return nullptr; }
+  if (check_create(n_channels, n_sources) != 0) return nullptr;
   if (decimation < 1 || decimation > ASDR_TUNER_MAX_DECIMATION) { fail("decimation must be in 1..64"); return nullptr; }
   if (fs_in <= 0) { fail("input rate Fs_in must be positive"); return nullptr; }
   if (fs_in % decimation != 0) { fail("input rate Fs_in is not a multiple of the decimation D"); return nullptr; }
@@ -520,25 +514,20 @@ asdr_tuner_t *create_bank(int n_channels, int n_sources, long long fs_in, int de
   if (fs_mid < 44100 || fs_mid > 4 * 44100) { fail("Fs_in / D must lie in [44100, 176400] Hz"); return nullptr; }
   const long long gd = gcd_ll(44100, fs_mid);
   if (44100 / gd > ASDR_TUNER_MAX_UP) { fail("44100 / (Fs_in / D) in lowest terms needs U > 2048"); return nullptr; }
-  asdr_tuner_bank *t = new asdr_tuner_bank();
-  t->n = n_channels; t->n_src = n_sources; t->D = decimation; t->device = device;
-  t->fs_in = fs_in; t->up = (int)(44100 / gd); t->down = (int)(fs_mid / gd);
-  t->chan.assign(n_channels, fresh_state());
-  t->corr.assign(n_sources, kIdentity);
+  asdr_tuner_bank *t = new_bank(n_channels, n_sources, fs_in, decimation, 44100 / gd, fs_mid / gd);
   default_rate_filter(decimation, fs_mid, t->h, t->g);
   default_resampler(t->up, t->down, fs_mid, t->h2, t->g2);
   t->k2 = (int)t->h2.size() / t->up;
-  return open_device(t);
+  return open_device(t, device);
 }
 
-// The device side of a new bank (nothing for ASDR_NO_DEVICE); deletes the bank and returns NULL on failure.
-asdr_tuner_t *open_device(asdr_tuner_bank *t) {
-  const int device = t->device, n_sources = t->n_src, n_channels = t->n;
+// The device side of a new bank (nothing for ASDR_NO_DEVICE); destroys the bank and returns NULL on failure.
+asdr_tuner_t *open_device(asdr_tuner_bank *t, int device) {
+  const int n_sources = t->n_src, n_channels = t->n;
   if (device == ASDR_NO_DEVICE) return t;
-  if (stage_check_device(device) != 0) { delete t; return nullptr; }
+  if (stage_open(*t, device, "tuner bank", true) != 0) { asdr_tuner_destroy(t); return nullptr; }
   const size_t hist = (size_t)n_sources * t->hist_slots * sizeof(int32_t);
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&t->stream) != hipSuccess || hipEventCreate(&t->ev0) != hipSuccess ||
-      hipEventCreate(&t->ev1) != hipSuccess || hipMalloc(&t->d_chan, n_channels * sizeof(asdr_tuner_state_t)) != hipSuccess ||
+  if (hipMalloc(&t->d_chan, n_channels * sizeof(asdr_tuner_state_t)) != hipSuccess ||
       hipMalloc(&t->d_order, n_channels * sizeof(int32_t)) != hipSuccess || hipMalloc(&t->d_taps, kTapWords * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&t->d_hist[0], hist) != hipSuccess || hipMalloc(&t->d_hist[1], hist) != hipSuccess ||
       hipMalloc(&t->d_rs_taps, (size_t)t->up * ASDR_TUNER_MAX_RESAMPLER_TAPS * sizeof(int16_t)) != hipSuccess ||
@@ -567,28 +556,23 @@ asdr_tuner_t *open_device(asdr_tuner_bank *t) {
 }
 
 asdr_tuner_t *create_fastconv(int n_channels, int n_sources, long long fs_in, int R, int device) {
-  if (n_channels <= 0 || n_channels > (1 << 20)) { fail("n_channels must be in 1..1048576"); return nullptr; }
-  if (n_sources <= 0 || n_sources > 65535) { fail("n_sources must be in 1..65535"); return nullptr; }
+  if (check_create(n_channels, n_sources) != 0) return nullptr;
   if (R < 2 || R > ASDR_TUNER_FC_MAX_R || (R & (R - 1)) != 0) { fail("R must be a power of two in 2..1024"); return nullptr; }
   if (fs_in <= 0) { fail("input rate Fs_in must be positive"); return nullptr; }
   if (fs_in < 44100LL * R || fs_in > 176400LL * R) { fail("Fs_in / R must lie in [44100, 176400] Hz"); return nullptr; }
   const long long gd = gcd_ll(44100LL * R, fs_in);
   if (44100LL * R / gd > ASDR_TUNER_MAX_UP) { fail("44100 R / Fs_in in lowest terms needs U > 2048"); return nullptr; }
-  asdr_tuner_bank *t = new asdr_tuner_bank();
-  t->n = n_channels; t->n_src = n_sources; t->D = R; t->device = device;
-  t->fs_in = fs_in; t->up = (int)(44100LL * R / gd); t->down = (int)(fs_in / gd);
+  asdr_tuner_bank *t = new_bank(n_channels, n_sources, fs_in, R, 44100LL * R / gd, fs_in / gd);
   t->fc = true;
   for (t->log2n = 0; (1 << t->log2n) < 256 * R; t->log2n++) {}
   t->hist_slots = 128 * R;
-  t->chan.assign(n_channels, fresh_state());
-  t->corr.assign(n_sources, kIdentity);
   t->pal.resize(ASDR_TUNER_FC_MAX_FILTERS);
   t->slot.assign(n_channels, 0);
   t->gain.assign(n_channels, 1.0f);
   default_channel_filter((double)fs_in / R, t->gch);
   default_fastconv_resampler(t->up, t->down, fs_in, R, t->h2, t->g2);
   t->k2 = (int)t->h2.size() / t->up;
-  return open_device(t);
+  return open_device(t, device);
 }
 
 // the int16 entry points on a bank of another format: fail before anything is read
@@ -597,6 +581,26 @@ bool wrong_format(const asdr_tuner_t *t, const char *entry) {
   fail(std::string(entry) + " takes CS16 rows and this bank's input format is " + kFormatNames[t->fmt] +
        ": use asdr_tuner_update_samples_device / asdr_tuner_update_samples");
   return true;
+}
+
+// The staging of the host-pointer entry points, one kept buffer: the call's input rows at its front, on their way there on the bank's
+// stream when this returns; the output rows *dI and *dQ, out_bytes each, behind them from a 256-byte boundary ...
+int io_in(asdr_tuner_t *t, const void *in, size_t in_bytes, size_t out_bytes, int16_t **dI, int16_t **dQ) {
+  const size_t in_pad = (in_bytes + 255) & ~(size_t)255;
+  HIPCHK(hipSetDevice(t->device));
+  if (stage_reserve(*t, &t->d_io, &t->io_cap, in_pad + 2 * out_bytes) != 0) return -1;
+  *dI = (int16_t *)((char *)t->d_io + in_pad); *dQ = (int16_t *)((char *)t->d_io + in_pad + out_bytes);
+  HIPCHK(hipMemcpyAsync(t->d_io, in, in_bytes, hipMemcpyHostToDevice, t->stream));
+  return 0;
+}
+// ... and back to the host behind the call's launches; waits for them
+int io_out(asdr_tuner_t *t, int16_t *I, int16_t *Q, const int16_t *dI, const int16_t *dQ, size_t out_bytes) {
+  if (out_bytes) {
+    HIPCHK(hipMemcpyAsync(I, dI, out_bytes, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipMemcpyAsync(Q, dQ, out_bytes, hipMemcpyDeviceToHost, t->stream));
+  }
+  HIPCHK(hipStreamSynchronize(t->stream));
+  return 0;
 }
 
 int pass_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_t *dI, int16_t *dQ, int n_blocks,
@@ -646,21 +650,11 @@ int asdr_tuner_get_channel_filter(const asdr_tuner_t *t, float *g, int cap) {
 
 void asdr_tuner_destroy(asdr_tuner_t *t) {
   if (!t) return;
-  if (t->device != ASDR_NO_DEVICE) {
-    hipSetDevice(t->device);
-    hipDeviceSynchronize();
-    hipFree(t->d_chan); hipFree(t->d_order); hipFree(t->d_taps); hipFree(t->d_hist[0]); hipFree(t->d_hist[1]); hipFree(t->d_io);
-    hipFree(t->d_rs_taps); hipFree(t->d_lane_qr); hipFree(t->d_carry[0]); hipFree(t->d_carry[1]); hipFree(t->d_mid);
-    hipFree(t->d_fc_tab); hipFree(t->d_fc_x); hipFree(t->d_spec); hipFree(t->d_lev); hipFree(t->d_lev_part);
-    hipFree(t->d_pal_tab); hipFree(t->d_slot); hipFree(t->d_gain);
-    hipFree(t->d_corr); hipFree(t->d_cond); hipFree(t->d_iq_stats);
-    hipFree(t->st_d);
-    if (t->st_h) hipHostFree(t->st_h);
-    if (t->st_ev) hipEventDestroy(t->st_ev);
-    if (t->ev0) hipEventDestroy(t->ev0);
-    if (t->ev1) hipEventDestroy(t->ev1);
-    if (t->stream) hipStreamDestroy(t->stream);
-  }
+  stage_close(*t, {t->d_chan, t->d_order, t->d_taps, t->d_hist[0], t->d_hist[1], t->d_io, t->d_rs_taps, t->d_lane_qr, t->d_carry[0],
+                   t->d_carry[1], t->d_mid, t->d_fc_tab, t->d_fc_x, t->d_spec, t->d_lev, t->d_lev_part, t->d_pal_tab, t->d_slot,
+                   t->d_gain, t->d_corr, t->d_cond, t->d_iq_stats, t->st_d});
+  if (t->st_h) hipHostFree(t->st_h);   // (both exist on a device bank only, and nothing uses them behind stage_close's wait)
+  if (t->st_ev) hipEventDestroy(t->st_ev);
   delete t;
 }
 
@@ -768,13 +762,9 @@ int pass_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int16_
   if (n_blocks <= 0) return 0;
   if (check_io(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, n_blocks) != 0) return -1;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(t->device));
-  if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
-  if (push(t, stream) != 0) return -1;
-  HIPCHK(hipEventRecord(t->ev0, stream));
+  if (stage_before_launch(*t, stream) != 0 || push(t, stream) != 0 || stage_mark_start(*t, stream) != 0) return -1;
   if (run_stage1(t, dIQ, in_stride_samples, dI, dQ, n_blocks, out_stride_blocks, stream) != 0) return -1;
-  HIPCHK(hipEventRecord(t->ev1, stream));
-  t->ev_valid = true; t->last_stream = stream;
+  if (stage_after_launch(*t, stream) != 0) return -1;
   t->out_pos += (long long)n_blocks * 128;   // a pass-through stage 2 writes every u sample at once
   t->carry_stale = true;                      // and keeps no history
   return 0;
@@ -791,24 +781,11 @@ int asdr_tuner_update(asdr_tuner_t *t, const int16_t *IQ, int16_t *I, int16_t *Q
   if (!IQ || !I || !Q) return fail("null host pointer");
   if (n_blocks <= 0) return 0;
   if (n_blocks > 65535) return fail("too many blocks in one call");
-  const size_t n_in = (size_t)n_blocks * 128 * t->D, in_bytes = (size_t)t->n_src * n_in * 4;
-  const size_t out_bytes = (size_t)t->n * n_blocks * 128 * 2, in_pad = (in_bytes + 255) & ~(size_t)255;
-  HIPCHK(hipSetDevice(t->device));
-  if (in_pad + 2 * out_bytes > t->io_cap) {
-    if (asdr_tuner_synchronize(t) != 0) return -1;
-    if (t->d_io) HIPCHK(hipFree(t->d_io));
-    t->d_io = nullptr; t->io_cap = 0;
-    HIPCHK(hipMalloc(&t->d_io, in_pad + 2 * out_bytes));
-    t->io_cap = in_pad + 2 * out_bytes;
-  }
-  char *base = (char *)t->d_io;
-  int16_t *dI = (int16_t *)(base + in_pad), *dQ = (int16_t *)(base + in_pad + out_bytes);
-  HIPCHK(hipMemcpyAsync(base, IQ, in_bytes, hipMemcpyHostToDevice, t->stream));
-  if (asdr_tuner_update_device(t, (const int16_t *)base, (long)n_in, dI, dQ, n_blocks, n_blocks, t->stream) != 0) return -1;
-  HIPCHK(hipMemcpyAsync(I, dI, out_bytes, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipMemcpyAsync(Q, dQ, out_bytes, hipMemcpyDeviceToHost, t->stream));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return 0;
+  const size_t n_in = (size_t)n_blocks * 128 * t->D, out_bytes = (size_t)t->n * n_blocks * 128 * 2;
+  int16_t *dI, *dQ;
+  if (io_in(t, IQ, (size_t)t->n_src * n_in * 4, out_bytes, &dI, &dQ) != 0) return -1;
+  if (asdr_tuner_update_device(t, (const int16_t *)t->d_io, (long)n_in, dI, dQ, n_blocks, n_blocks, t->stream) != 0) return -1;
+  return io_out(t, I, Q, dI, dQ, out_bytes);
 }
 
 long long asdr_tuner_rate(const asdr_tuner_t *t) { return t ? t->fs_in : 0; }
@@ -904,28 +881,20 @@ int rate_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int n_
   if (pass_through(t))
     return pass_device(t, dIQ, in_stride_samples, dI, dQ, n_frames, out_stride_blocks, stream_) == 0 ? n_frames : -1;
   hipStream_t stream = (hipStream_t)stream_;
-  HIPCHK(hipSetDevice(t->device));
   const size_t row = (size_t)n_frames * 128, mid_bytes = 2 * (size_t)t->n * row * sizeof(int16_t);
-  if (mid_bytes > t->mid_cap || !t->d_carry[0]) {   // grow the intermediate / allocate the carry: nothing of ours may be in flight
-    if (asdr_tuner_synchronize(t) != 0) return -1;
-    if (mid_bytes > t->mid_cap) {
-      if (t->d_mid) HIPCHK(hipFree(t->d_mid));
-      t->d_mid = nullptr; t->mid_cap = 0;
-      HIPCHK(hipMalloc(&t->d_mid, mid_bytes));
-      t->mid_cap = mid_bytes;
-    }
-    if (!t->d_carry[0]) {
-      const size_t cb = (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t);
-      HIPCHK(hipMalloc(&t->d_carry[0], cb));
-      HIPCHK(hipMalloc(&t->d_carry[1], cb));
-      HIPCHK(hipMemset(t->d_carry[t->ccur], 0, cb));
-      HIPCHK(hipDeviceSynchronize());
-      t->carry_stale = false;
-    }
+  if (stage_reserve(*t, (void **)&t->d_mid, &t->mid_cap, mid_bytes) != 0) return -1;
+  if (!t->d_carry[0]) {   // the first stage-2 call allocates the carry: nothing of ours may be in flight
+    const size_t cb = (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t);
+    if (stage_quiesce(*t) != 0) return -1;
+    HIPCHK(hipMalloc(&t->d_carry[0], cb));
+    HIPCHK(hipMalloc(&t->d_carry[1], cb));
+    HIPCHK(hipMemset(t->d_carry[t->ccur], 0, cb));
+    HIPCHK(hipDeviceSynchronize());
+    t->carry_stale = false;
   }
-  if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
-  if (push(t, stream) != 0 || push_resampler(t, stream) != 0) return -1;
-  HIPCHK(hipEventRecord(t->ev0, stream));
+  if (stage_before_launch(*t, stream) != 0 || push(t, stream) != 0 || push_resampler(t, stream) != 0 ||
+      stage_mark_start(*t, stream) != 0)
+    return -1;
   if (t->carry_stale) {   // the pass-through calls before this one kept no stage-2 history (asdr_tuner.h)
     HIPCHK(hipMemsetAsync(t->d_carry[t->ccur], 0, (size_t)t->n * ASDR_TUNER_CARRY * sizeof(int32_t), stream));
     t->carry_stale = false;
@@ -947,8 +916,7 @@ int rate_device(asdr_tuner_t *t, const void *dIQ, long in_stride_samples, int n_
   r.shift = 15 - t->g2; r.round = r.shift ? 1 << (r.shift - 1) : 0;
   if (r.q0 - (r.k - 1) < 0) return fail("internal: stage-2 window starts before the carry");
   if (asdr_launch_tuner_resample(&r, stream) != 0) return fail("tuner resampler kernel launch failed");
-  HIPCHK(hipEventRecord(t->ev1, stream));
-  t->ev_valid = true; t->last_stream = stream;
+  if (stage_after_launch(*t, stream) != 0) return -1;
   t->ccur ^= 1;
   t->out_pos += nb * 128;
   return (int)nb;
@@ -963,48 +931,21 @@ int rate_host(asdr_tuner_t *t, const void *IQ, int n_frames, int16_t *I, int16_t
   const long long nb = blocks_after(t, n_frames);
   if (nb > out_capacity_blocks)
     return fail("output capacity of " + std::to_string(out_capacity_blocks) + " blocks: this call writes " + std::to_string(nb));
-  const size_t n_in = (size_t)n_frames * 128 * t->D, in_bytes = (size_t)t->n_src * n_in * ASDR_TUNER_FMT_BYTES(t->fmt);
-  const size_t out_bytes = (size_t)t->n * nb * 128 * 2, in_pad = (in_bytes + 255) & ~(size_t)255;
-  HIPCHK(hipSetDevice(t->device));
-  if (in_pad + 2 * out_bytes > t->io_cap) {
-    if (asdr_tuner_synchronize(t) != 0) return -1;
-    if (t->d_io) HIPCHK(hipFree(t->d_io));
-    t->d_io = nullptr; t->io_cap = 0;
-    HIPCHK(hipMalloc(&t->d_io, in_pad + 2 * out_bytes));
-    t->io_cap = in_pad + 2 * out_bytes;
-  }
-  char *base = (char *)t->d_io;
-  int16_t *dI = (int16_t *)(base + in_pad), *dQ = (int16_t *)(base + in_pad + out_bytes);
-  HIPCHK(hipMemcpyAsync(base, IQ, in_bytes, hipMemcpyHostToDevice, t->stream));
-  const int got = rate_device(t, base, (long)n_in, n_frames, dI, dQ, (int)nb, (long)nb, t->stream);
-  if (got < 0) return -1;
-  if (out_bytes) {
-    HIPCHK(hipMemcpyAsync(I, dI, out_bytes, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipMemcpyAsync(Q, dQ, out_bytes, hipMemcpyDeviceToHost, t->stream));
-  }
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return got;
+  const size_t n_in = (size_t)n_frames * 128 * t->D, out_bytes = (size_t)t->n * nb * 128 * 2;
+  int16_t *dI, *dQ;
+  if (io_in(t, IQ, (size_t)t->n_src * n_in * ASDR_TUNER_FMT_BYTES(t->fmt), out_bytes, &dI, &dQ) != 0) return -1;
+  const int got = rate_device(t, t->d_io, (long)n_in, n_frames, dI, dQ, (int)nb, (long)nb, t->stream);
+  return got < 0 || io_out(t, I, Q, dI, dQ, out_bytes) != 0 ? -1 : got;
 }
 }  // namespace
 
 extern "C" {
 
 int asdr_tuner_synchronize(asdr_tuner_t *t) {
-  if (!t) return fail("null tuner bank");
-  if (t->device == ASDR_NO_DEVICE) return 0;
-  HIPCHK(hipSetDevice(t->device));
-  if (t->ev_valid) HIPCHK(hipEventSynchronize(t->ev1));
-  HIPCHK(hipStreamSynchronize(t->stream));
-  return 0;
+  return t ? stage_quiesce(*t) : fail("null tuner bank");
 }
 
-float asdr_tuner_last_kernel_ms(asdr_tuner_t *t) {
-  if (!t || !t->ev_valid) return -1.0f;
-  float ms = -1.0f;
-  if (hipEventSynchronize(t->ev1) != hipSuccess) return -1.0f;
-  if (hipEventElapsedTime(&ms, t->ev0, t->ev1) != hipSuccess) return -1.0f;
-  return ms;
-}
+float asdr_tuner_last_kernel_ms(asdr_tuner_t *t) { return t ? stage_last_ms(*t) : -1.0f; }
 
 }  // extern "C"
 
@@ -1481,25 +1422,14 @@ int rec_stage_reserve(asdr_tuner_t *t, size_t h_bytes, size_t d_bytes) {
     HIPCHK(hipHostMalloc((void **)&t->st_h, h_bytes, hipHostMallocDefault));
     t->st_h_cap = h_bytes;
   }
-  if (d_bytes > t->st_d_cap) {
-    if (t->st_d) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(t->st_d)); t->st_d = nullptr; t->st_d_cap = 0; }
-    HIPCHK(hipMalloc((void **)&t->st_d, d_bytes));
-    t->st_d_cap = d_bytes;
-  }
-  return 0;
+  return stage_reserve(*t, (void **)&t->st_d, &t->st_d_cap, d_bytes);
 }
 
-// `stream` joins the bank's stream order (the rule of pass_device / rate_device) ...
-int rec_order_in(asdr_tuner_t *t, hipStream_t stream) {
-  if (t->ev_valid && stream != t->last_stream) HIPCHK(hipStreamWaitEvent(stream, t->ev1, 0));
-  return 0;
-}
-// ... and the next call on any stream is ordered after what it was given
+// behind a device form's work on `stream`, which stage_before_launch put in the bank's stream order: the next call on any stream is
+// ordered after it.  On a bank that never launched this records the start event too (asdr_tuner_last_kernel_ms reads both)
 int rec_order_out(asdr_tuner_t *t, hipStream_t stream) {
-  if (!t->ev_valid) HIPCHK(hipEventRecord(t->ev0, stream));   // (asdr_tuner_last_kernel_ms reads both)
-  HIPCHK(hipEventRecord(t->ev1, stream));
-  t->ev_valid = true; t->last_stream = stream;
-  return 0;
+  if (!t->ev_valid && stage_mark_start(*t, stream) != 0) return -1;
+  return stage_after_launch(*t, stream);
 }
 
 // the carry the gather reads: the current rows, or none while they are logically zero or do not exist
@@ -1729,7 +1659,7 @@ int asdr_tuner_export_channels_device(asdr_tuner_t *t, const int *channels, int 
   hipStream_t stream = (hipStream_t)stream_;
   HIPCHK(hipSetDevice(t->device));
   if (rec_stage_reserve(t, (size_t)n * (kHead + 2 * sizeof(int)), (size_t)n * (kHead + 2 * sizeof(int))) != 0) return -1;
-  if (rec_order_in(t, stream) != 0) return -1;
+  if (stage_before_launch(*t, stream) != 0) return -1;
   if (rec_gather(t, channels, 0, n, 0, d_records, stream) != 0) return -1;
   return rec_order_out(t, stream);
 }
@@ -1772,7 +1702,7 @@ int asdr_tuner_import_channels_device(asdr_tuner_t *t, const int *channels, int 
   HIPCHK(hipStreamSynchronize(stream));
   if (rec_check_all(t, channels, n, t->st_h, kHead) != 0) return -1;
   if (!pass_through(t) || t->lev_on) {
-    if (rec_order_in(t, stream) != 0) return -1;
+    if (stage_before_launch(*t, stream) != 0) return -1;
     if (!pass_through(t) && rec_carry_ready(t, stream) != 0) return -1;
     if (rec_scatter(t, channels, 0, n, 0, d_records, head_bytes, stream) != 0) return -1;
     if (rec_order_out(t, stream) != 0) return -1;

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 FM_EXPORTS = ["asdr_fm_create", "asdr_fm_destroy", "asdr_fm_n_channels", "asdr_fm_set_gain", "asdr_fm_get_gain", "asdr_fm_set_deemphasis",
@@ -63,7 +63,7 @@ def _c_int(v, what):
     return v
 
 
-class FmDemodulator(Stage):
+class FmDemodulator(ResetStage):
     """FM demodulators of n_channels tuner channels (include/asdr_fm.h).  device = NO_DEVICE (-1) gives the control plane and the
     state records only."""
     _prefix = "asdr_fm_"

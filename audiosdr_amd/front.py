@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import ALL, BLOCK, AsdrError, load_library
+from ._stage import Stage, i, lg, typed_library, vp
+from .binding import ALL, BLOCK
 
 NO_DEVICE = -1
 
@@ -32,78 +33,32 @@ PRE_STATE_DTYPE = np.dtype([("correction", "<i2"), ("saved_sample", "<i2"), ("fa
                             ("max_power", "<f4"), ("avg_power", "<f4"), ("ratio", "<f4")])
 assert PRE_STATE_DTYPE.itemsize == C.sizeof(PreState) == 36
 
-_typed = False
-
-
-def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, lg, f, i16p = C.c_void_p, C.c_int, C.c_long, C.c_float, C.POINTER(C.c_int16)
-    for pre in ("pre", "iqgen", "grab"):
-        getattr(L, "asdr_%s_create" % pre).argtypes = [i, i]; getattr(L, "asdr_%s_create" % pre).restype = vp
-        getattr(L, "asdr_%s_destroy" % pre).argtypes = [vp]; getattr(L, "asdr_%s_destroy" % pre).restype = None
-        getattr(L, "asdr_%s_n_channels" % pre).argtypes = [vp]; getattr(L, "asdr_%s_n_channels" % pre).restype = i
-        getattr(L, "asdr_%s_synchronize" % pre).argtypes = [vp]; getattr(L, "asdr_%s_synchronize" % pre).restype = i
-    L.asdr_pre_update.argtypes = [vp, i16p, i16p, i]; L.asdr_pre_update.restype = i
-    L.asdr_pre_update_device.argtypes = [vp, vp, vp, vp, vp, i, lg, lg, vp]; L.asdr_pre_update_device.restype = i
-    for n in ("startAutoI2SerrorDetection", "stopAutoI2SerrorDetection"):
-        getattr(L, "asdr_pre_" + n).argtypes = [vp, i]; getattr(L, "asdr_pre_" + n).restype = None
-    L.asdr_pre_getAutoI2SerrorDetectionStatus.argtypes = [vp, i]; L.asdr_pre_getAutoI2SerrorDetectionStatus.restype = i
-    L.asdr_pre_setI2SerrorCompensation.argtypes = [vp, i, i]; L.asdr_pre_setI2SerrorCompensation.restype = None
-    L.asdr_pre_getI2SerrorCompensation.argtypes = [vp, i]; L.asdr_pre_getI2SerrorCompensation.restype = C.c_int16
-    L.asdr_pre_swapIQ.argtypes = [vp, i, i]; L.asdr_pre_swapIQ.restype = None
-    L.asdr_pre_read_state.argtypes = [vp, vp]; L.asdr_pre_read_state.restype = i
-    L.asdr_pre_last_kernel_ms.argtypes = [vp]; L.asdr_pre_last_kernel_ms.restype = f
-    L.asdr_iqgen_update.argtypes = [vp, i16p, i16p, i16p, i]; L.asdr_iqgen_update.restype = i
-    L.asdr_iqgen_update_device.argtypes = [vp, vp, vp, vp, i, lg, lg, vp]; L.asdr_iqgen_update_device.restype = i
-    L.asdr_iqgen_setGainBalance.argtypes = [vp, i, f]; L.asdr_iqgen_setGainBalance.restype = None
-    L.asdr_iqgen_last_kernel_ms.argtypes = [vp]; L.asdr_iqgen_last_kernel_ms.restype = f
-    L.asdr_grab_update.argtypes = [vp, i16p, i16p, i]; L.asdr_grab_update.restype = i
-    L.asdr_grab_update_device.argtypes = [vp, vp, vp, i, lg, vp]; L.asdr_grab_update_device.restype = i
-    L.asdr_grab_newDataAvailable.argtypes = [vp, i]; L.asdr_grab_newDataAvailable.restype = i
-    L.asdr_grab_grab.argtypes = [vp, i, i16p]; L.asdr_grab_grab.restype = i
-    L.asdr_grab_grab_all.argtypes = [vp, i16p]; L.asdr_grab_grab_all.restype = i
-    L.asdr_grab_device_ptr.argtypes = [vp]; L.asdr_grab_device_ptr.restype = vp
-    L.asdr_grab_power_spectrum.argtypes = [vp, C.POINTER(C.c_float)]; L.asdr_grab_power_spectrum.restype = i
-    L.asdr_grab_power_spectrum_device.argtypes = [vp, vp, vp]; L.asdr_grab_power_spectrum_device.restype = i
-    _typed = True
-    return L
+_f, _i16p, _fp = C.c_float, C.POINTER(C.c_int16), C.POINTER(C.c_float)
+_LIFE = {"create": ([i, i], vp), "destroy": ([vp], None), "n_channels": ([vp], i), "synchronize": ([vp], i)}
+_API = {"asdr_pre_": dict(_LIFE, **{
+            "update": ([vp, _i16p, _i16p, i], i), "update_device": ([vp, vp, vp, vp, vp, i, lg, lg, vp], i),
+            "startAutoI2SerrorDetection": ([vp, i], None), "stopAutoI2SerrorDetection": ([vp, i], None),
+            "getAutoI2SerrorDetectionStatus": ([vp, i], i), "setI2SerrorCompensation": ([vp, i, i], None),
+            "getI2SerrorCompensation": ([vp, i], C.c_int16), "swapIQ": ([vp, i, i], None), "read_state": ([vp, vp], i),
+            "last_kernel_ms": ([vp], _f)}),
+        "asdr_iqgen_": dict(_LIFE, **{
+            "update": ([vp, _i16p, _i16p, _i16p, i], i), "update_device": ([vp, vp, vp, vp, i, lg, lg, vp], i),
+            "setGainBalance": ([vp, i, _f], None), "last_kernel_ms": ([vp], _f)}),
+        "asdr_grab_": dict(_LIFE, **{
+            "update": ([vp, _i16p, _i16p, i], i), "update_device": ([vp, vp, vp, i, lg, vp], i), "newDataAvailable": ([vp, i], i),
+            "grab": ([vp, i, _i16p], i), "grab_all": ([vp, _i16p], i), "device_ptr": ([vp], vp),
+            "power_spectrum": ([vp, _fp], i), "power_spectrum_device": ([vp, vp, vp], i)})}
 
 
 def _p16(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int16))
+    return a.ctypes.data_as(_i16p)
 
 
-class _Batch:
-    _prefix = ""
-
+class _Batch(Stage):
     def __init__(self, n_channels, device=0):
-        self._L = _lib()
-        self._h = getattr(self._L, "asdr_%s_create" % self._prefix)(int(n_channels), int(device))
-        if not self._h:
-            raise AsdrError("asdr_%s_create failed: %s" % (self._prefix, self._L.asdr_last_error().decode()))
+        self._L = typed_library(self._prefix, _API[self._prefix])
+        self._create(self._prefix + "create", getattr(self._L, self._prefix + "create")(int(n_channels), int(device)))
         self.n_channels = int(n_channels)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            getattr(self._L, "asdr_%s_destroy" % self._prefix)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
-
-    def synchronize(self):
-        self._chk(getattr(self._L, "asdr_%s_synchronize" % self._prefix)(self._h))
 
     def _blocks(self, a):
         a = np.ascontiguousarray(a, dtype=np.int16)
@@ -113,7 +68,7 @@ class _Batch:
 
 class AudioSDRpreProcessorBatch(_Batch):
     """N independent AudioSDRpreProcessor instances (AudioSDRpreProcessor.h:49-70)."""
-    _prefix = "pre"
+    _prefix = "asdr_pre_"
 
     def update(self, I, Q):
         """I, Q: int16 [channels][blocks][128] (host).  Returns the conditioned (I, Q); inputs are not modified."""
@@ -157,7 +112,7 @@ class AudioSDRpreProcessorBatch(_Batch):
 
 class AudioIQgeneratorBatch(_Batch):
     """N independent AudioIQgenerator instances (AudioIQgenerator.h:48-59)."""
-    _prefix = "iqgen"
+    _prefix = "asdr_iqgen_"
 
     def update(self, x):
         """x: int16 [channels][blocks][128] real input (host).  Returns (I, Q) of the same shape."""
@@ -179,7 +134,7 @@ class AudioIQgeneratorBatch(_Batch):
 
 class AudioGrabberComplex256Batch(_Batch):
     """N independent AudioGrabberComplex256 instances (AudioGrabberComplex256.h:44-52)."""
-    _prefix = "grab"
+    _prefix = "asdr_grab_"
 
     def update(self, I, Q):
         I, Q = self._blocks(I), self._blocks(Q)
@@ -208,7 +163,7 @@ class AudioGrabberComplex256Batch(_Batch):
     def power_spectrum(self):
         """(valid, float32 [n_channels][256]): |FFT256|^2 of every channel's buffer, natural bin order (panadapter)."""
         d = np.zeros((self.n_channels, 256), dtype=np.float32)
-        return self._chk(self._L.asdr_grab_power_spectrum(self._h, d.ctypes.data_as(C.POINTER(C.c_float)))), d
+        return self._chk(self._L.asdr_grab_power_spectrum(self._h, d.ctypes.data_as(_fp))), d
 
     def power_spectrum_device(self, dDst, stream=0):
         return self._chk(self._L.asdr_grab_power_spectrum_device(self._h, C.c_void_p(dDst), C.c_void_p(stream)))

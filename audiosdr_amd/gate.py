@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
 from .binding import ALL, BLOCK, AsdrError
 
 GATE_EXPORTS = ["asdr_gate_create", "asdr_gate_destroy", "asdr_gate_n_channels", "asdr_gate_set_squelch", "asdr_gate_get_squelch",
@@ -43,7 +43,7 @@ class _DeviceInts:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
-class AudioGate(Stage):
+class AudioGate(ResetStage):
     """Audio meters and squelch of n_channels receivers over the chain's int16 audio rows (include/asdr_gate.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
     _prefix = "asdr_gate_"

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, ll, typed_library, vp
 from .binding import AsdrError
 
 RESAMPLE_EXPORTS = ["asdr_resampler_create", "asdr_resampler_create_custom", "asdr_resampler_destroy", "asdr_resampler_n_channels",
@@ -36,7 +36,7 @@ def _taps_array(taps, up):
     return t.astype(np.int16)
 
 
-class AudioResampler(Stage):
+class AudioResampler(ResetStage):
     """Resampler of n_channels receivers' audio rows from 44.1 kHz to fs_out (include/asdr_resample.h).  Either fs_out (the default
     filter of that rate) or up, down, taps [up * K] as h[k * up + phi] and shift (a custom filter).  device = NO_DEVICE (-1) gives
     the control plane and the state records only."""

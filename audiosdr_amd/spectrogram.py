@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, ll, typed_library, vp
 from .binding import AsdrError
 
 SPECTROGRAM_EXPORTS = ["asdr_spectrogram_create", "asdr_spectrogram_destroy", "asdr_spectrogram_n_channels", "asdr_spectrogram_n_fft",
@@ -32,7 +32,7 @@ def _lib():
     return typed_library("asdr_spectrogram_", _API)
 
 
-class AudioSpectrogram(Stage):
+class AudioSpectrogram(ResetStage):
     """Spectrogram of n_channels receivers' int16 audio rows (include/asdr_spectrogram.h): frames of n_fft samples (a power of two in
     128 .. 8192) every hop samples (n_fft / 16 .. n_fft, default n_fft / 2), of which the bins first_bin .. first_bin + n_bins - 1
     (default: all n_fft / 2 + 1) are written per frame, as |X|^2 (kind "power") or (re, im) (kind "complex"), float32, scaled by

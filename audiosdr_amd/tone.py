@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import Stage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 TONE_EXPORTS = ["asdr_tone_create", "asdr_tone_destroy", "asdr_tone_n_channels", "asdr_tone_set_tones", "asdr_tone_get_tones",
@@ -74,7 +74,7 @@ def tone_min_power(amplitude, window_blocks):
     return v
 
 
-class ToneSquelch(Stage):
+class ToneSquelch(ResetStage):
     """Tone squelches of n_channels audio rows (include/asdr_tone.h).  device = NO_DEVICE (-1) gives the control plane and the state
     records only."""
     _prefix = "asdr_tone_"

@@ -5,7 +5,8 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import ALL, BLOCK, AsdrError, load_library
+from ._stage import ResetStage, i, ip, lg, ll, typed_library, vp
+from .binding import ALL, BLOCK, AsdrError
 
 TUNER_EXPORTS = ["asdr_tuner_create", "asdr_tuner_destroy", "asdr_tuner_reset", "asdr_tuner_position", "asdr_tuner_n_channels",
                  "asdr_tuner_n_sources", "asdr_tuner_decimation", "asdr_tuner_set_source", "asdr_tuner_set_frequency",
@@ -57,90 +58,42 @@ assert TUNER_STATE_DTYPE.itemsize == 24
 CHANNEL_RECORD_BYTES = 2560
 _FIELD_TYPES = {"u32": "<u4", "i32": "<i4", "i64": "<i8", "f32": "<f4", "f64": "<f8"}
 
-_typed = False
+_u32, _sz, _d, _f, _i16p, _fp = C.c_uint32, C.c_size_t, C.c_double, C.c_float, C.POINTER(C.c_int16), C.POINTER(C.c_float)
+_dp, _llp, _i32p = C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_int32)
+_API = {"create": ([i, i, i, i], vp), "create_rate": ([i, i, ll, i, i], vp), "create_fastconv": ([i, i, ll, i, i], vp),
+        "create_from_bank_state": ([vp, _sz, i, i], vp), "destroy": ([vp], None), "reset": ([vp], i), "synchronize": ([vp], i),
+        "n_channels": ([vp], i), "n_sources": ([vp], i), "decimation": ([vp], i), "position": ([vp], ll), "rate": ([vp], ll),
+        "ratio": ([vp, ip, ip], i), "output_position": ([vp], ll), "fft_size": ([vp], i), "last_kernel_ms": ([vp], _f),
+        "set_source": ([vp, i, i], i), "set_frequency": ([vp, i, _d], i), "set_frequency_word": ([vp, i, _u32], i),
+        "set_phase": ([vp, i, _u32], i), "set_filter": ([vp, _i16p, i, i], i), "get_filter": ([vp, _i16p, i, ip], i),
+        "set_resampler": ([vp, _i16p, i, i], i), "get_resampler": ([vp, _i16p, i, ip], i),
+        "set_channel_filter": ([vp, _fp, i], i), "get_channel_filter": ([vp, _fp, i], i), "read_state": ([vp, vp], i),
+        "set_input_format": ([vp, i], i), "input_format": ([vp], i), "out_blocks": ([vp, i], i),
+        "update": ([vp, _i16p, _i16p, _i16p, i], i), "update_device": ([vp, vp, lg, vp, vp, i, lg, vp], i),
+        "update_rate": ([vp, _i16p, i, _i16p, _i16p, i], i), "update_rate_device": ([vp, vp, lg, i, vp, vp, i, lg, vp], i),
+        "update_samples": ([vp, vp, i, _i16p, _i16p, i], i), "update_samples_device": ([vp, vp, lg, i, vp, vp, i, lg, vp], i),
+        "spectrum_enable": ([vp, i, i, i], i), "spectrum_bins": ([vp], i), "spectrum_window": ([vp], i), "spectrum_mode": ([vp], i),
+        "spectrum_read": ([vp, _dp, _llp, i], i), "spectrum_device": ([vp], vp), "spectrum_frames": ([vp], ll), "spectrum_clear": ([vp], i),
+        "levels_enable": ([vp, i], i), "levels_enabled": ([vp], i), "levels_read": ([vp, _dp, _llp, i], i), "levels_device": ([vp], vp),
+        "levels_frames": ([vp], ll), "levels_clear": ([vp], i),
+        "palette_set": ([vp, i, _fp, i, i], i), "palette_get": ([vp, i, _fp, i, ip], i), "palette_clear": ([vp, i], i),
+        "set_channel_slot": ([vp, i, i], i), "read_slots": ([vp, _i32p], i), "set_channel_gain": ([vp, i, _f], i), "read_gains": ([vp, _fp], i),
+        "set_iq_correction": ([vp, i, vp], i), "get_iq_correction": ([vp, i, vp], i), "iq_stats_enable": ([vp, i], i),
+        "iq_stats_enabled": ([vp], i), "iq_stats_read": ([vp, vp, i], i), "iq_stats_clear": ([vp], i), "iq_estimate": ([vp, vp], i),
+        "iq_track": ([vp, i], i), "condition_launches": ([vp], ll),
+        "channel_record_bytes": ([], _sz), "channel_record_field": ([i, ip, ip], C.c_char_p),
+        "export_channels": ([vp, ip, i, vp], i), "import_channels": ([vp, ip, i, vp], i),
+        "export_channels_device": ([vp, ip, i, vp, vp], i), "import_channels_device": ([vp, ip, i, vp, vp], i),
+        "bank_state_bytes": ([vp], _sz), "export_bank_state": ([vp, vp, _sz], i), "import_bank_state": ([vp, vp, _sz], i)}
+assert sorted("asdr_tuner_" + k for k in _API) == sorted(TUNER_EXPORTS)
 
 
 def _lib():
-    global _typed
-    L = load_library()
-    if _typed:
-        return L
-    vp, i, u32, lg, i16p = C.c_void_p, C.c_int, C.c_uint32, C.c_long, C.POINTER(C.c_int16)
-    L.asdr_tuner_create.argtypes = [i, i, i, i]; L.asdr_tuner_create.restype = vp
-    L.asdr_tuner_destroy.argtypes = [vp]; L.asdr_tuner_destroy.restype = None
-    for n in ("reset", "n_channels", "n_sources", "decimation", "synchronize"):
-        getattr(L, "asdr_tuner_" + n).argtypes = [vp]; getattr(L, "asdr_tuner_" + n).restype = i
-    L.asdr_tuner_position.argtypes = [vp]; L.asdr_tuner_position.restype = C.c_longlong
-    L.asdr_tuner_set_source.argtypes = [vp, i, i]; L.asdr_tuner_set_source.restype = i
-    L.asdr_tuner_set_frequency.argtypes = [vp, i, C.c_double]; L.asdr_tuner_set_frequency.restype = i
-    L.asdr_tuner_set_frequency_word.argtypes = [vp, i, u32]; L.asdr_tuner_set_frequency_word.restype = i
-    L.asdr_tuner_set_phase.argtypes = [vp, i, u32]; L.asdr_tuner_set_phase.restype = i
-    L.asdr_tuner_set_filter.argtypes = [vp, i16p, i, i]; L.asdr_tuner_set_filter.restype = i
-    L.asdr_tuner_get_filter.argtypes = [vp, i16p, i, C.POINTER(C.c_int)]; L.asdr_tuner_get_filter.restype = i
-    L.asdr_tuner_read_state.argtypes = [vp, vp]; L.asdr_tuner_read_state.restype = i
-    L.asdr_tuner_update_device.argtypes = [vp, vp, lg, vp, vp, i, lg, vp]; L.asdr_tuner_update_device.restype = i
-    L.asdr_tuner_update.argtypes = [vp, i16p, i16p, i16p, i]; L.asdr_tuner_update.restype = i
-    L.asdr_tuner_last_kernel_ms.argtypes = [vp]; L.asdr_tuner_last_kernel_ms.restype = C.c_float
-    ll, ip = C.c_longlong, C.POINTER(C.c_int)
-    L.asdr_tuner_create_rate.argtypes = [i, i, ll, i, i]; L.asdr_tuner_create_rate.restype = vp
-    L.asdr_tuner_rate.argtypes = [vp]; L.asdr_tuner_rate.restype = ll
-    L.asdr_tuner_ratio.argtypes = [vp, ip, ip]; L.asdr_tuner_ratio.restype = i
-    L.asdr_tuner_output_position.argtypes = [vp]; L.asdr_tuner_output_position.restype = ll
-    L.asdr_tuner_set_resampler.argtypes = [vp, i16p, i, i]; L.asdr_tuner_set_resampler.restype = i
-    L.asdr_tuner_get_resampler.argtypes = [vp, i16p, i, ip]; L.asdr_tuner_get_resampler.restype = i
-    L.asdr_tuner_out_blocks.argtypes = [vp, i]; L.asdr_tuner_out_blocks.restype = i
-    L.asdr_tuner_update_rate_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_rate_device.restype = i
-    L.asdr_tuner_update_rate.argtypes = [vp, i16p, i, i16p, i16p, i]; L.asdr_tuner_update_rate.restype = i
-    fp = C.POINTER(C.c_float)
-    L.asdr_tuner_create_fastconv.argtypes = [i, i, ll, i, i]; L.asdr_tuner_create_fastconv.restype = vp
-    L.asdr_tuner_fft_size.argtypes = [vp]; L.asdr_tuner_fft_size.restype = i
-    L.asdr_tuner_set_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_set_channel_filter.restype = i
-    L.asdr_tuner_get_channel_filter.argtypes = [vp, fp, i]; L.asdr_tuner_get_channel_filter.restype = i
-    L.asdr_tuner_set_input_format.argtypes = [vp, i]; L.asdr_tuner_set_input_format.restype = i
-    L.asdr_tuner_input_format.argtypes = [vp]; L.asdr_tuner_input_format.restype = i
-    L.asdr_tuner_update_samples_device.argtypes = [vp, vp, lg, i, vp, vp, i, lg, vp]; L.asdr_tuner_update_samples_device.restype = i
-    L.asdr_tuner_update_samples.argtypes = [vp, vp, i, i16p, i16p, i]; L.asdr_tuner_update_samples.restype = i
-    dp, llp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
-    L.asdr_tuner_spectrum_enable.argtypes = [vp, i, i, i]; L.asdr_tuner_spectrum_enable.restype = i
-    for n in ("spectrum_bins", "spectrum_window", "spectrum_mode", "spectrum_clear", "levels_enabled", "levels_clear"):
-        getattr(L, "asdr_tuner_" + n).argtypes = [vp]; getattr(L, "asdr_tuner_" + n).restype = i
-    for n in ("spectrum", "levels"):
-        getattr(L, "asdr_tuner_%s_read" % n).argtypes = [vp, dp, llp, i]; getattr(L, "asdr_tuner_%s_read" % n).restype = i
-        getattr(L, "asdr_tuner_%s_device" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_device" % n).restype = vp
-        getattr(L, "asdr_tuner_%s_frames" % n).argtypes = [vp]; getattr(L, "asdr_tuner_%s_frames" % n).restype = ll
-    L.asdr_tuner_levels_enable.argtypes = [vp, i]; L.asdr_tuner_levels_enable.restype = i
-    L.asdr_tuner_palette_set.argtypes = [vp, i, fp, i, i]; L.asdr_tuner_palette_set.restype = i
-    L.asdr_tuner_palette_get.argtypes = [vp, i, fp, i, ip]; L.asdr_tuner_palette_get.restype = i
-    L.asdr_tuner_palette_clear.argtypes = [vp, i]; L.asdr_tuner_palette_clear.restype = i
-    L.asdr_tuner_set_channel_slot.argtypes = [vp, i, i]; L.asdr_tuner_set_channel_slot.restype = i
-    L.asdr_tuner_read_slots.argtypes = [vp, C.POINTER(C.c_int32)]; L.asdr_tuner_read_slots.restype = i
-    L.asdr_tuner_set_channel_gain.argtypes = [vp, i, C.c_float]; L.asdr_tuner_set_channel_gain.restype = i
-    L.asdr_tuner_read_gains.argtypes = [vp, fp]; L.asdr_tuner_read_gains.restype = i
-    L.asdr_tuner_set_iq_correction.argtypes = [vp, i, vp]; L.asdr_tuner_set_iq_correction.restype = i
-    L.asdr_tuner_get_iq_correction.argtypes = [vp, i, vp]; L.asdr_tuner_get_iq_correction.restype = i
-    L.asdr_tuner_iq_stats_enable.argtypes = [vp, i]; L.asdr_tuner_iq_stats_enable.restype = i
-    L.asdr_tuner_iq_stats_enabled.argtypes = [vp]; L.asdr_tuner_iq_stats_enabled.restype = i
-    L.asdr_tuner_iq_stats_read.argtypes = [vp, vp, i]; L.asdr_tuner_iq_stats_read.restype = i
-    L.asdr_tuner_iq_stats_clear.argtypes = [vp]; L.asdr_tuner_iq_stats_clear.restype = i
-    L.asdr_tuner_iq_estimate.argtypes = [vp, vp]; L.asdr_tuner_iq_estimate.restype = i
-    L.asdr_tuner_iq_track.argtypes = [vp, i]; L.asdr_tuner_iq_track.restype = i
-    L.asdr_tuner_condition_launches.argtypes = [vp]; L.asdr_tuner_condition_launches.restype = ll
-    sz, ip = C.c_size_t, C.POINTER(C.c_int)
-    L.asdr_tuner_channel_record_bytes.argtypes = []; L.asdr_tuner_channel_record_bytes.restype = sz
-    L.asdr_tuner_channel_record_field.argtypes = [i, ip, ip]; L.asdr_tuner_channel_record_field.restype = C.c_char_p
-    for n in ("export_channels", "import_channels"):
-        getattr(L, "asdr_tuner_" + n).argtypes = [vp, ip, i, vp]; getattr(L, "asdr_tuner_" + n).restype = i
-        getattr(L, "asdr_tuner_%s_device" % n).argtypes = [vp, ip, i, vp, vp]; getattr(L, "asdr_tuner_%s_device" % n).restype = i
-    L.asdr_tuner_bank_state_bytes.argtypes = [vp]; L.asdr_tuner_bank_state_bytes.restype = sz
-    L.asdr_tuner_export_bank_state.argtypes = [vp, vp, sz]; L.asdr_tuner_export_bank_state.restype = i
-    L.asdr_tuner_import_bank_state.argtypes = [vp, vp, sz]; L.asdr_tuner_import_bank_state.restype = i
-    L.asdr_tuner_create_from_bank_state.argtypes = [vp, sz, i, i]; L.asdr_tuner_create_from_bank_state.restype = vp
-    _typed = True
-    return L
+    return typed_library("asdr_tuner_", _API)
 
 
 def _p16(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int16))
+    return a.ctypes.data_as(_i16p)
 
 
 def rate_ratio(fs_in, decimation):
@@ -286,21 +239,24 @@ class _DeviceRows:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
 
 
-class TunerBank:
+class TunerBank(ResetStage):
     """n_channels digital tuners over n_sources shared CS16 rows at decimation D (include/asdr_tuner.h).  fs_in (Hz) makes a rate
     bank: any integer input rate with fs_in / D in [44100, 176400], resampled to 44.1 kHz after the decimator.  device = NO_DEVICE
     (-1) gives the control plane only."""
+    _prefix = "asdr_tuner_"
 
     def __init__(self, n_channels, n_sources=1, decimation=1, fs_in=None, device=0):
         self._L = _lib()
         if fs_in is None:
-            self._h = self._L.asdr_tuner_create(int(n_channels), int(n_sources), int(decimation), int(device))
+            self._create("asdr_tuner_create", self._L.asdr_tuner_create(int(n_channels), int(n_sources), int(decimation), int(device)))
         else:
-            self._h = self._L.asdr_tuner_create_rate(int(n_channels), int(n_sources), int(fs_in), int(decimation), int(device))
-        if not self._h:
-            raise AsdrError("asdr_tuner_create%s failed: %s" % ("" if fs_in is None else "_rate", self._L.asdr_last_error().decode()))
-        self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(decimation)
-        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+            self._create("asdr_tuner_create_rate",
+                         self._L.asdr_tuner_create_rate(int(n_channels), int(n_sources), int(fs_in), int(decimation), int(device)))
+        self._geometry()
+
+    def _geometry(self):
+        self.n_channels, self.n_sources = int(self._L.asdr_tuner_n_channels(self._h)), int(self._L.asdr_tuner_n_sources(self._h))
+        self.decimation, self.fs_in = int(self._L.asdr_tuner_decimation(self._h)), int(self._L.asdr_tuner_rate(self._h))
 
     @classmethod
     def fastconv(cls, n_channels, n_sources, fs_in, R, device=0):
@@ -308,11 +264,9 @@ class TunerBank:
         points per source and frame, fs_in / R in [44100, 176400], then the rate-bank stage 2.  `decimation` is R."""
         self = cls.__new__(cls)
         self._L = _lib()
-        self._h = self._L.asdr_tuner_create_fastconv(int(n_channels), int(n_sources), int(fs_in), int(R), int(device))
-        if not self._h:
-            raise AsdrError("asdr_tuner_create_fastconv failed: %s" % self._L.asdr_last_error().decode())
-        self.n_channels, self.n_sources, self.decimation = int(n_channels), int(n_sources), int(R)
-        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+        self._create("asdr_tuner_create_fastconv",
+                     self._L.asdr_tuner_create_fastconv(int(n_channels), int(n_sources), int(fs_in), int(R), int(device)))
+        self._geometry()
         return self
 
     # state records (include/asdr_tuner.h, "State records")
@@ -323,12 +277,9 @@ class TunerBank:
         blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
         self = cls.__new__(cls)
         self._L = _lib()
-        self._h = self._L.asdr_tuner_create_from_bank_state(blob.ctypes.data_as(C.c_void_p), int(blob.size), int(n_channels), int(device))
-        if not self._h:
-            raise AsdrError("asdr_tuner_create_from_bank_state failed: %s" % self._L.asdr_last_error().decode())
-        self.n_channels, self.n_sources = int(n_channels), int(self._L.asdr_tuner_n_sources(self._h))
-        self.decimation = int(self._L.asdr_tuner_decimation(self._h))
-        self.fs_in = int(self._L.asdr_tuner_rate(self._h))
+        self._create("asdr_tuner_create_from_bank_state",
+                     self._L.asdr_tuner_create_from_bank_state(blob.ctypes.data_as(C.c_void_p), int(blob.size), int(n_channels), int(device)))
+        self._geometry()
         return self
 
     def bank_state_bytes(self):
@@ -378,13 +329,13 @@ class TunerBank:
     def set_channel_filter(self, g):
         """Real taps (float32, 1..129) at Fs_mid of a fast-convolution bank."""
         g = np.ascontiguousarray(g, dtype=np.float32)
-        self._chk(self._L.asdr_tuner_set_channel_filter(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), int(g.size)))
+        self._chk(self._L.asdr_tuner_set_channel_filter(self._h, g.ctypes.data_as(_fp), int(g.size)))
 
     def get_channel_filter(self):
         """float32 [Lg]."""
         n = self._chk(self._L.asdr_tuner_get_channel_filter(self._h, None, 0))
         g = np.zeros(n, dtype=np.float32)
-        self._chk(self._L.asdr_tuner_get_channel_filter(self._h, g.ctypes.data_as(C.POINTER(C.c_float)), n))
+        self._chk(self._L.asdr_tuner_get_channel_filter(self._h, g.ctypes.data_as(_fp), n))
         return g
 
     # filter palette and gain of a fast-convolution bank (include/asdr_tuner.h, "Filter palette and gain")
@@ -394,7 +345,7 @@ class TunerBank:
         taps = np.asarray(taps)
         cx = np.iscomplexobj(taps)
         taps = np.ascontiguousarray(taps, dtype=np.complex64 if cx else np.float32).reshape(-1)
-        self._chk(self._L.asdr_tuner_palette_set(self._h, int(slot), taps.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)),
+        self._chk(self._L.asdr_tuner_palette_set(self._h, int(slot), taps.view(np.float32).ctypes.data_as(_fp),
                                                  int(taps.size), int(cx)))
 
     def get_palette_filter(self, slot):
@@ -404,7 +355,7 @@ class TunerBank:
         if n == 0:
             return None
         g = np.zeros(n, dtype=np.complex64 if cx.value else np.float32)
-        self._chk(self._L.asdr_tuner_palette_get(self._h, int(slot), g.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)), n, None))
+        self._chk(self._L.asdr_tuner_palette_get(self._h, int(slot), g.view(np.float32).ctypes.data_as(_fp), n, None))
         return g
 
     def clear_palette_filter(self, slot):
@@ -429,27 +380,8 @@ class TunerBank:
     def gains(self):
         """float32 [n_channels]."""
         out = np.zeros(self.n_channels, dtype=np.float32)
-        self._chk(self._L.asdr_tuner_read_gains(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(self._L.asdr_tuner_read_gains(self._h, out.ctypes.data_as(_fp)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.asdr_tuner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc):
-        if rc < 0:
-            raise AsdrError(self._L.asdr_last_error().decode())
-        return rc
-
-    def reset(self):
-        self._chk(self._L.asdr_tuner_reset(self._h))
 
     def position(self):
         return int(self._L.asdr_tuner_position(self._h))
@@ -591,9 +523,6 @@ class TunerBank:
         return self._chk(self._L.asdr_tuner_update_samples_device(
             self._h, C.c_void_p(dIn), int(ins), int(n_frames), C.c_void_p(dI), C.c_void_p(dQ), int(out_capacity_blocks),
             int(out_stride_blocks or out_capacity_blocks), C.c_void_p(stream)))
-
-    def synchronize(self):
-        self._chk(self._L.asdr_tuner_synchronize(self._h))
 
     def last_kernel_ms(self):
         return float(self._L.asdr_tuner_last_kernel_ms(self._h))

@@ -46,7 +46,8 @@ int asdr_pre_n_channels(const asdr_pre_t *p);
  *  _update        : host pointers, in place, synchronous.
  *  _update_device : device pointers, asynchronous on `stream`; I/Q rows in_stride_blocks*128 samples apart,
  *                   output rows out_stride_blocks*128.  NULL dI or dQ = the missing-input guard (.cpp:50-52):
- *                   nothing happens, return 0. */
+ *                   nothing happens, return 0.
+ * A device call (of any of the three blocks) on another stream than the handle's last first waits for that last call. */
 int asdr_pre_update(asdr_pre_t *p, int16_t *I, int16_t *Q, int n_blocks);
 int asdr_pre_update_device(asdr_pre_t *p, const int16_t *dI, const int16_t *dQ, int16_t *dIout, int16_t *dQout,
                            int n_blocks, long in_stride_blocks, long out_stride_blocks, void *stream);

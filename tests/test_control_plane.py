@@ -268,3 +268,55 @@ def test_schedule_layout_kinds_and_remainders(A):
     # kind (its launch then uses the long-row ALS kernel, which carries the PLL)
     assert not lay4["sam_three_launches"] and lay4["sam"] == 96 and lay4["sam_als"] == 8
     b.close()
+
+
+def test_tuner_and_front_end_creates_refuse_a_bad_device_and_leave_nothing_behind(A):
+    """device = 99: every create of the tuner bank and of the front end returns NULL with the device check's text ("bad device
+    index"; on a machine without a GPU the check's first half speaks, "no HIP device"), and a control-plane create right behind
+    it succeeds."""
+    L = A.tuner._lib()
+    for cls in (A.AudioSDRpreProcessorBatch, A.AudioIQgeneratorBatch, A.AudioGrabberComplex256Batch):
+        cls(1, device=A.NO_DEVICE).close()                            # types the front end's entry points
+    blob = A.TunerBank.fastconv(2, 1, 88200, 2, device=A.NO_DEVICE).export_bank_state()
+    creates = [("asdr_tuner_create", (3, 2, 2)), ("asdr_tuner_create_rate", (3, 2, 96000, 2)), ("asdr_tuner_create_fastconv", (3, 2, 88200, 2)),
+               ("asdr_tuner_create_from_bank_state", (blob.ctypes.data, blob.size, 3)),
+               ("asdr_pre_create", (5,)), ("asdr_iqgen_create", (5,)), ("asdr_grab_create", (5,))]
+    for name, args in creates:
+        assert not getattr(L, name)(*args, 99), name
+        text = L.asdr_last_error().decode()
+        assert text in ("bad device index", "no HIP device: this library has no CPU fallback"), (name, text)
+        h = getattr(L, name)(*args, A.NO_DEVICE)
+        assert h, (name, L.asdr_last_error().decode())
+        getattr(L, name[:name.index("create")] + "destroy")(h)
+    for make in (lambda d: A.TunerBank(3, 2, 2, device=d), lambda d: A.TunerBank.fastconv(3, 2, 88200, 2, device=d),
+                 lambda d: A.AudioIQgeneratorBatch(5, device=d)):
+        with pytest.raises(A.AsdrError, match="create.* failed: (bad device index|no HIP device)"):
+            make(99)
+        make(A.NO_DEVICE).close()
+
+
+# dir() without the names that start with an underscore, as the classes stood before they moved onto _stage.Stage
+PUBLIC_NAMES = {
+    "TunerBank": [
+        'bank_state_bytes', 'clear_iq_stats', 'clear_levels', 'clear_palette_filter', 'clear_spectrum', 'close', 'condition_launches',
+        'enable_iq_stats', 'enable_levels', 'enable_spectrum', 'export_bank_state', 'export_channels', 'export_channels_device', 'fastconv',
+        'fft_size', 'from_bank_state', 'gains', 'get_channel_filter', 'get_filter', 'get_palette_filter', 'get_resampler',
+        'import_bank_state', 'import_channels', 'import_channels_device', 'input_format', 'iq_correction', 'iq_stats', 'iq_stats_enabled',
+        'last_kernel_ms', 'levels', 'levels_enabled', 'levels_frames', 'levels_tensor', 'out_blocks', 'output_position', 'position',
+        'ratio', 'read_state', 'reset', 'set_channel_filter', 'set_channel_slot', 'set_filter', 'set_frequency', 'set_frequency_word',
+        'set_gain', 'set_input_format', 'set_iq_correction', 'set_palette_filter', 'set_phase', 'set_resampler', 'set_source', 'slots',
+        'spectrum', 'spectrum_bins', 'spectrum_config', 'spectrum_frames', 'spectrum_tensor', 'synchronize', 'track_iq', 'update',
+        'update_device', 'update_rate', 'update_rate_device', 'update_samples', 'update_samples_device'],
+    "AudioSDRpreProcessorBatch": [
+        'close', 'getAutoI2SerrorDetectionStatus', 'getI2SerrorCompensation', 'last_kernel_ms', 'read_state', 'setI2SerrorCompensation',
+        'startAutoI2SerrorDetection', 'stopAutoI2SerrorDetection', 'swapIQ', 'synchronize', 'update', 'update_device'],
+    "AudioIQgeneratorBatch": ['close', 'last_kernel_ms', 'setGainBalance', 'synchronize', 'update', 'update_device'],
+    "AudioGrabberComplex256Batch": [
+        'close', 'device_ptr', 'grab', 'grab_all', 'newDataAvailable', 'power_spectrum', 'power_spectrum_device', 'synchronize', 'update',
+        'update_device'],
+}
+
+
+@pytest.mark.parametrize("cls", sorted(PUBLIC_NAMES))
+def test_public_names_of_the_tuner_bank_and_the_front_end_stay(A, cls):
+    assert [n for n in dir(getattr(A, cls)) if not n.startswith("_")] == PUBLIC_NAMES[cls]

@@ -368,3 +368,68 @@ def test_grabber_power_spectrum_parity(gpu, ao):
     g.synchronize(); hip.sync()
     assert np.array_equal(f32_bits(hip.download(dS, (n_ch, 256), np.float32)), f32_bits(spec))
     hip.free_all(); g.close()
+
+
+def test_host_forms_grow_their_staging_and_reuse_it(gpu, ao):
+    """Host-form calls of 1, 3, 1 blocks on 5 channels: the staging grows for the second call and is reused, larger than needed, by
+    the third; every stream, the pre-processor's state and the grabber's buffers bit for bit against the oracle objects."""
+    n_ch, calls = 5, (1, 3, 1)
+    n_blk = sum(calls)
+    I, Q = _streams(n_ch, n_blk, [0, 1, 2, 3, 0], seed=21)
+    pre, gen, grab = gpu.AudioSDRpreProcessorBatch(n_ch), gpu.AudioIQgeneratorBatch(n_ch), gpu.AudioGrabberComplex256Batch(n_ch)
+    o_pre = [ao.OraclePreProcessor() for _ in range(n_ch)]
+    o_gen = [ao.OracleIQgenerator() for _ in range(n_ch)]
+    o_grab = [ao.OracleGrabber() for _ in range(n_ch)]
+    pre.startAutoI2SerrorDetection()
+    for c in range(n_ch):
+        o_pre[c].startAutoI2SerrorDetection()
+        gen.setGainBalance(1.0 + 0.01 * c, ch=c); o_gen[c].setGainBalance(1.0 + 0.01 * c)
+    k0 = 0
+    for T in calls:
+        sl = slice(k0, k0 + T)
+        pi, pq = pre.update(I[:, sl], Q[:, sl])
+        gi, gq = gen.update(I[:, sl])
+        grab.update(I[:, sl], Q[:, sl])
+        for c in range(n_ch):
+            wi, wq = o_pre[c].update(I[c, sl], Q[c, sl])
+            assert np.array_equal(pi[c].reshape(-1), wi) and np.array_equal(pq[c].reshape(-1), wq), ("pre", k0, c)
+            wi, wq = o_gen[c].update(I[c, sl])
+            assert np.array_equal(gi[c].reshape(-1), wi) and np.array_equal(gq[c].reshape(-1), wq), ("iqgen", k0, c)
+            o_grab[c].update(I[c, sl], Q[c, sl])
+            assert grab.newDataAvailable(c) == o_grab[c].newDataAvailable(), ("grab", k0, c)
+        _cmp_state(pre, o_pre)
+        k0 += T
+    copied, allbuf = grab.grab_all()
+    assert copied == 1
+    for c, o in enumerate(o_grab):
+        assert np.array_equal(allbuf[c], o.grab()), c
+    pre.close(); gen.close(); grab.close()
+
+
+def test_pre_calls_alternating_between_two_streams(gpu, ao):
+    """Detector on, 5 channels, ten one-block update_device calls that alternate between two streams with no host synchronisation:
+    every call reads and rewrites the state rows the one before it wrote, so the batch has to order them itself (include/asdr_front.h:
+    a call on another stream than the batch's last waits for that last call).  Streams, counters and the float32 measurements after
+    the last call against the oracle."""
+    n_ch, n_blk = 5, 10
+    I, Q = _streams(n_ch, n_blk, [0, 1, 2, 3, 4], seed=5)
+    b = gpu.AudioSDRpreProcessorBatch(n_ch)
+    orcs = [ao.OraclePreProcessor() for _ in range(n_ch)]
+    b.startAutoI2SerrorDetection()
+    for o in orcs:
+        o.startAutoI2SerrorDetection()
+    hip = Hip()
+    ss = [hip.stream(), hip.stream()]
+    dI, dQ = hip.upload(I), hip.upload(Q)
+    dOi, dOq = hip.malloc(I.nbytes), hip.malloc(Q.nbytes)
+    hip.sync()
+    for k in range(n_blk):
+        b.update_device(dI + 256 * k, dQ + 256 * k, dOi + 256 * k, dOq + 256 * k, 1, n_blk, n_blk, stream=ss[k % 2])
+    b.synchronize()
+    gi, gq = hip.download(dOi, I.shape, np.int16), hip.download(dOq, Q.shape, np.int16)
+    for c, o in enumerate(orcs):
+        wi, wq = o.update(I[c], Q[c])
+        assert np.array_equal(gi[c].reshape(-1), wi) and np.array_equal(gq[c].reshape(-1), wq), c
+    _cmp_state(b, orcs)
+    hip.free_all()
+    b.close()

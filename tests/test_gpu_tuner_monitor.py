@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import test_gpu_tuner_fastconv as T
+import tuner_condition_ref as CR
 import tuner_fastconv_ref as F
 import tuner_formats_ref as FM
 import tuner_monitor_ref as M
@@ -421,3 +422,40 @@ if __name__ == "__main__":                                    # the EPS_A table:
         for R in Rs:
             worst, peak = measure(recipe, R)
             print('    ("%s", %d): %.3g,   # measured %.3g at peak amplitude %.0f' % (recipe, R, 8 * worst, worst, peak), flush=True)
+
+
+def test_kept_buffers_grow_and_are_reused(gpu):
+    """R = 2, 3 channels on 2 sources, source 1 with a correction off the identity, levels on, fed through the host form
+    update_samples in calls of 1, 3, 1 and 2 frames: the host staging, X, the conditioning scratch and the level partials all grow for
+    the second call and are reused, larger than needed, by the two behind it.  The outputs against test_gpu_tuner_condition.py's
+    yardstick, tolerance 0 (a bank without a correction, fed tuner_condition_ref's corrected rows); the levels against the
+    restatement as test_levels_match_the_restatement holds them, the inputs being the edge recipe's (noise in +-20000, the default
+    filter, edge_words)."""
+    R, n_ch, n_src = 2, 3, 2
+    fs = 44100 * R
+    rng = np.random.default_rng(2)
+    srcs, fws = [0, 1, 1], T.edge_words(R)[4:4 + n_ch]
+    bank, plain = (gpu.TunerBank.fastconv(n_ch, n_src, fs, R) for _ in range(2))
+    ref = F.TunerFastconvRef(n_ch, n_src, fs, R, g=bank.get_channel_filter())
+    for o in (bank, plain, ref):
+        T.setup(o, srcs, fws)
+    mon = M.MonitorRef(ref, levels=True)
+    bank.set_iq_correction(words=CR.KA_WORDS, source=1)
+    bank.enable_levels(); plain.enable_levels()
+    hip = Hip()
+    for k, nf in enumerate((1, 3, 1, 2)):
+        raw = T.cs16(rng, n_src, nf * 128 * R)
+        fixed = raw.copy()
+        fixed[1] = CR.condition(raw[1], CR.KA_WORDS)
+        got = bank.update_samples(raw)
+        dIn, dI, dQ = hip.upload(fixed), hip.malloc(n_ch * nf * 256), hip.malloc(n_ch * nf * 256)
+        assert plain.update_samples_device(dIn, dI, dQ, nf, nf) == nf
+        plain.synchronize()
+        want = [hip.download(p, (n_ch, nf, 128), np.int16) for p in (dI, dQ)]
+        assert got[0].shape == want[0].shape and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), k
+        assert got[0].any()
+        mon.update(fixed); ref.update(fixed)
+        check_levels(bank, mon, T.EPS["edge", R], ("grow", k))
+    assert bank.condition_launches() == 4 and plain.condition_launches() == 0
+    hip.free_all()
+    bank.close(); plain.close()

@@ -362,3 +362,59 @@ def test_tone_lands_in_its_bin_and_the_alias_is_rejected(gpu):
     alias = spec[np.abs(f + 5000.0) < 30.0].max()
     assert 20 * np.log10(spec.max() / alias) >= 60.0, 20 * np.log10(spec.max() / alias)
     bank.close()
+
+
+def tuned(bank):
+    for c in range(bank.n_channels):
+        bank.set_source(c % bank.n_sources, ch=c); bank.set_frequency_word(FWS[c % len(FWS)], ch=c)
+    return bank
+
+
+def test_direct_and_rate_banks_alternating_between_two_streams(gpu):
+    """A direct-form bank (D = 2) and a rate bank (96 kHz, D = 2: 48 kHz intermediate, 147 / 160), 7 channels on 2 sources: calls of
+    2, 2, 4, 1, 3 frames alternate between two streams with no host synchronisation (the third is the largest, so the rate bank's
+    intermediate grows between calls); outputs and positions equal a twin's that runs on one stream, bit for bit."""
+    n_ch, n_src, D = 7, 2, 2
+    rng = np.random.default_rng(96)
+    hip = Hip()
+    ss, s1 = [hip.stream(), hip.stream()], hip.stream()
+    splits = [2, 2, 4, 1, 3]
+    ins = [hip.upload(random_iq(rng, n_src, nf * 128 * D)) for nf in splits]
+    caps = [nf + 1 for nf in splits]
+    for make_bank in (lambda: gpu.TunerBank(n_ch, n_src, D), lambda: gpu.TunerBank(n_ch, n_src, D, fs_in=96000)):
+        two, one = tuned(make_bank()), tuned(make_bank())
+        rate = two.ratio() != (1, 1)
+        assert two.ratio() == ((147, 160) if rate else (1, 1))
+        bufs = [[hip.malloc(n_ch * c * 256) for _ in range(4)] for c in caps]
+        hip.sync()
+        ns = []
+        for k, nf in enumerate(splits):
+            if rate:
+                a = two.update_rate_device(ins[k], bufs[k][0], bufs[k][1], nf, caps[k], stream=ss[k % 2])
+                assert a == one.update_rate_device(ins[k], bufs[k][2], bufs[k][3], nf, caps[k], stream=s1)
+            else:
+                a = nf
+                two.update_device(ins[k], bufs[k][0], bufs[k][1], nf, out_stride_blocks=caps[k], stream=ss[k % 2])
+                one.update_device(ins[k], bufs[k][2], bufs[k][3], nf, out_stride_blocks=caps[k], stream=s1)
+            ns.append(a)
+        hip.sync()
+        assert two.position() == one.position() == sum(splits) * 128 * D and two.output_position() == one.output_position() > 0
+        for k, n in enumerate(ns):
+            g = [hip.download(p, (n_ch, caps[k], 128), np.int16)[:, :n] for p in bufs[k]]
+            assert np.array_equal(g[0], g[2]) and np.array_equal(g[1], g[3]), (rate, k)
+            assert n == 0 or g[0].any()
+        two.close(); one.close()
+    hip.free_all()
+
+
+def test_kept_buffers_grow_and_are_reused(gpu):
+    """The rate bank above through the host form in calls of 1, 3, 1 and 2 frames: the host staging and the intermediate grow for
+    the second call and are reused, larger than needed, by the calls behind it; every call against tuner_rate_ref."""
+    rng = np.random.default_rng(147)
+    bank, ref = make(gpu, 96000, 2, rng, n_ch=7, n_src=2, L=25, K=12)
+    assert bank.ratio() == (147, 160)
+    total = 0
+    for nf in (1, 3, 1, 2):
+        total += check(bank, ref, random_iq(rng, 2, nf * 128 * 2))[0].shape[1]
+    assert total > 0
+    bank.close()
