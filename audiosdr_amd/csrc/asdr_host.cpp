@@ -330,6 +330,7 @@ struct asdr_batch {
   size_t xch_sam_slots = 0;         // ... TWO sets of tiles (and of lock words behind them): consecutive blocks of a multi-block call alternate
   hipEvent_t ev_role[6] = {};       // SAM role streams: [0..1] pre done, [2..3] PLL done, [4..5] post done, by block parity
   bool sam_role_streams = true;     // (ASDR_NO_SAM_ROLE_STREAMS: off, for measurements)
+  bool sam_chunks = true;           // ... in chunks where the rule allows (ASDR_NO_SAM_CHUNKS: the per-block form, for measurements)
   long stat_sam_role_calls = 0;
   // ALS role streams: a SMALL bank of channels with a short ALS filter (one uniform sub-range, below the one-launch-per-block size) runs a
   // multi-block call as chain | filter launches on two event-chained streams, a chunk of blocks per launch -- the filter of a chunk (a
@@ -925,6 +926,18 @@ int lanes_join_into(asdr_batch *b, hipStream_t stream) {
   }
   return 0;
 }
+// ... and the batch's last call (on another stream than `stream`) happens before whatever is enqueued on `stream` from now on.  The event is recorded now, on
+// that call's stream -- behind everything it enqueued there -- rather than after every call: one packet less per launch for the common single-stream caller.
+int wait_for_last(asdr_batch *b, hipStream_t stream) { HIPCHK(hipEventRecord(b->ev_last, b->last_stream)); HIPCHK(hipStreamWaitEvent(stream, b->ev_last, 0)); return 0; }
+int sync_all(asdr_batch *b);
+// an ordinary call on `stream` after calls on the lanes: behind them -- on the host when a flush is due, which rewrites rows the lanes' kernels read
+int leave_lanes(asdr_batch *b, hipStream_t stream) {
+  if (!b->lanes_pending) return 0;
+  if (needs_flush(b)) { if (sync_all(b) != 0) return -1; }
+  else { if (lanes_join_into(b, stream) != 0) return -1; b->lanes_pending = false; }
+  b->last_stream = stream; b->last_was_lanes = false;
+  return 0;
+}
 // host-side: every launch of the batch so far is complete
 int sync_all(asdr_batch *b) {
   HIPCHK(hipStreamSynchronize(b->last_stream));   // nullptr = the null stream
@@ -1016,8 +1029,9 @@ asdr_batch_t *asdr_create(int n_channels, int device) {
     if (ok && hipStreamSynchronize(nullptr) != hipSuccess) ok = false;
     for (int i = 0; i < ASDR_LANES + 1 && ok; i++)
       if (hipEventCreateWithFlags(&b->ev_lane[i], hipEventDisableTiming) != hipSuccess) ok = false;
-    b->lanes_enabled = getenv("ASDR_NO_LANES") == nullptr;   // (the overlap probe runs at the first call that would use the lanes: update_device_part)
+    b->lanes_enabled = getenv("ASDR_NO_LANES") == nullptr;   // (the overlap probe runs at the first call that would use the lanes: plan_enter)
     b->sam_role_streams = getenv("ASDR_NO_SAM_ROLE_STREAMS") == nullptr;
+    b->sam_chunks = getenv("ASDR_NO_SAM_CHUNKS") == nullptr;
     b->als_role_streams = getenv("ASDR_NO_ALS_ROLE_STREAMS") == nullptr;
     if (getenv("ASDR_ALS_ROLE_STAGES")) b->als_role_stages = atoi(getenv("ASDR_ALS_ROLE_STAGES")) == 2 ? 2 : 3;
     if (ok && (b->stream = pool_stream(device, 0)) == nullptr) ok = false;   // the pool's first stream (= lane 0: a batch runs on the lanes or on its own stream, never both at once)
@@ -1156,13 +1170,127 @@ void asdr_destroy(asdr_batch_t *b) {
 int asdr_n_channels(const asdr_batch_t *b) { return b ? b->n : 0; }
 
 }  // extern "C"
-// One call, or one PART of a call: with parts > 1 only the waves [w part / parts, w (part + 1) / parts) of every sub-range of the
-// schedule are launched, and the batch's block counters advance with the last part.  The parts of a call touch disjoint channels
-// (every schedule slot is launched exactly once) and are enqueued on one stream: the overlapped host-pointer path (asdr_update)
-// starts part p as soon as the input rows of ITS channels have arrived and copies a channel range out as soon as the parts that
-// hold its channels are done.
-static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t *dQ, int16_t *dOut, int n_blocks,
-                              long in_stride_blocks, long out_stride_blocks, void *stream_, int part, int parts) {
+// ---- the device-call dispatcher --------------------------------------------------------------------------------
+// One call, or one PART of a call: with parts > 1 only the waves [w part / parts, w (part + 1) / parts) of every sub-range of the schedule are launched, and the
+// batch's block counters advance with the last part.  The parts of a call touch disjoint channels (every schedule slot is launched exactly once:
+// tests/test_launch_plan.py) and are enqueued on one stream: the overlapped host-pointer path (asdr_update) starts part p as soon as the input rows of ITS channels
+// have arrived and copies a channel range out as soon as the parts that hold its channels are done.
+// A call is planned once (CallPlan: every decision taken in front of the first launch) and issued by ONE launch form: the block pipeline, the lanes, SAM role
+// streams in chunks, ALS role streams, or the item loop.  The order of HIP calls inside a form is the behaviour: tools/host_trace.py holds it against a revision.
+namespace {
+struct Sub { int kind, uniform, first, slots; };   // a sub-range of the sorted schedule: the slots of one kernel instantiation
+struct Item { int sub, first, slots; };            // (a piece of) this part's waves of a sub-range: one launch of the item loop
+struct CallPlan {
+  const int16_t *dI, *dQ; int16_t *dOut; int n_blocks, part, parts; long in_stride, out_stride;
+  hipStream_t stream; bool batch_stream, use_lanes;
+  hipEvent_t e0, e1;                               // timing markers around the call's launches, or null
+  Sub subs[ASDR_KERNEL_KINDS + 2]; int n_sub;      // heaviest instantiation first
+  bool sam_split, als_split;                       // SAM channels as pre | PLL | post launches, short ALS filters as chain | filter
+  bool per_block; int n_launch;                    // one launch per block: n_launch = n_blocks, else 1
+  bool take_pipeline; int pipe_sub, other_waves;   // the block pipeline takes subs[pipe_sub]; other_waves run beside it
+  Item items[ASDR_AUX_STREAMS + 1]; int n_items, main_item;   // (not filled for the pipeline and the lanes)
+  bool sam_roles, sam_chunks, als_roles; int n_chunks;        // role streams; sam_chunks: by the rule -- the tile sets are reserved at the launch
+};
+// (a piece of) sub-range `su` into the launch arguments: the slots [first, first + slots) of the schedule, and a direct group -- one key group of consecutive
+// channels: no schedule reads in the waves -- as launch constants.  lo_write: the first wave of every settings group fills the group's entry of the other half of
+// the local-oscillator cache; a direct launch's wave 0 is its group's writer, so of the pieces of a direct group only the one that holds the group's first wave may
+// write -- unless every piece has a writer bit and an entry set of its own (`own_writers`: the lanes).
+void select_slots(asdr_batch *b, UpdateArgs &a, const Sub &su, int first, int slots, bool own_writers) {
+  a.sched = b->d_sched + first; a.n_sched = slots; a.direct_ch0 = -1; a.uni_valid = 0u; a.lo_write = 1u;
+  if (su.uniform && b->kind_direct[su.kind]) {
+    const SlotInfo &s0 = b->sched[su.first];
+    a.direct_ch0 = s0.ch + (first - su.first); a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch);
+    if (first != su.first && !own_writers) a.lo_write = 0u;
+  }
+}
+// the launch works on the blocks [b0, b0 + count) of the call; `flips` launches of the call have flipped the oscillator cache's halves before it
+void point_at_blocks(const asdr_batch *b, const CallPlan &p, UpdateArgs &a, int b0, int count, int flips) {
+  a.in_i = p.dI + (size_t)b0 * ASDR_N; a.in_q = p.dQ + (size_t)b0 * ASDR_N; a.out = p.dOut + (size_t)b0 * ASDR_N; a.n_blocks = count;
+  a.nb_phase = (b->nb_phase + (uint32_t)(b0 % 3)) % 3u; a.als_phase = (b->als_phase + (uint32_t)b0) & 1u; a.lo_parity = b->lo_parity ^ (uint32_t)(flips & 1);
+}
+// tiles / lock words of the slots [first, ..) of a SAM kind's sub-range, set `parity` (0 everywhere but in the role streams per block)
+void set_sam_rows(const asdr_batch *b, UpdateArgs &a, int kind, int first, int parity) {
+  const size_t at = (size_t)(first - b->kind_first[kind]) + (kind == ASDR_KERNEL_SAM_ALS ? (size_t)b->kind_slots[ASDR_KERNEL_SAM] : 0);
+  a.xch_sam = b->d_xch_sam + ((size_t)parity * b->xch_sam_slots + at) * 2 * ASDR_N;
+  a.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam + 2 * b->xch_sam_slots * 2 * ASDR_N) + (size_t)parity * b->xch_sam_slots + at;
+}
+// the chunked forms' tile sets: ASDR_SAM_CHUNK_SETS sets of tiles, the lock words behind them (the launch's first set: a.sam_set)
+void set_chunk_tiles(const asdr_batch *b, UpdateArgs &a) {
+  const size_t slots = b->xch_sam_chunk_slots;
+  a.xch_sam = b->d_xch_sam_chunk; a.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam_chunk + (size_t)ASDR_SAM_CHUNK_SETS * slots * 2 * ASDR_N);
+  a.sam_sets = (uint32_t)ASDR_SAM_CHUNK_SETS; a.sam_set_stride = (uint32_t)(slots * 2 * ASDR_N); a.sam_lock_stride = (uint32_t)slots;
+}
+// The exchange tiles grow on demand: `sets` sets of tiles for `slots` schedule slots and the sets' lock words behind them (d_xch_sam: two sets, consecutive blocks
+// alternate; d_xch_sam_chunk: ASDR_SAM_CHUNK_SETS).  Pointer and size change only once the allocation succeeded; false: no memory.
+bool reserve_tiles(float *&tiles, size_t &have, int slots, int sets, hipStream_t stream) {
+  if ((size_t)slots <= have) return true;
+  float *grown = nullptr;
+  const size_t per_set = (size_t)slots * 2 * ASDR_N * sizeof(float) + (size_t)slots * sizeof(uint32_t);
+  if (hipStreamSynchronize(stream) != hipSuccess || hipMalloc(&grown, sets * per_set) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (tiles) hipFree(tiles);
+  tiles = grown; have = (size_t)slots;
+  return true;
+}
+bool reserve_chunk_tiles(asdr_batch *b, int slots, hipStream_t stream) { return reserve_tiles(b->d_xch_sam_chunk, b->xch_sam_chunk_slots, slots, ASDR_SAM_CHUNK_SETS, stream); }
+// the pipeline's buffers at its first use: every one, or none (false: the batch stays on the other launch forms for good)
+bool reserve_pipeline(asdr_batch *b, hipStream_t stream) {
+  if (b->d_xch_a) return true;
+  float *xa = nullptr, *xb = nullptr; uint32_t *prog = nullptr; LoEntry *ring = nullptr; void *snap = nullptr;
+  const size_t n_prog = (size_t)(3 * ((b->n + 7) / 8) + 3);   // [.. + 1] = the error word, [.. + 2] = the recovery counter
+  const bool ok = hipMalloc(&xa, (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * 2 * ASDR_N * sizeof(float)) == hipSuccess &&
+                  hipMalloc(&xb, (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * (ASDR_N + 1) * sizeof(float)) == hipSuccess &&   // + the AM carrier words (xch_c) behind the rows
+                  hipMalloc(&prog, n_prog * sizeof(uint32_t)) == hipSuccess &&
+                  hipMalloc(&ring, ASDR_LO_RING * sizeof(LoEntry)) == hipSuccess &&
+                  hipMalloc(&snap, (size_t)(((b->n + 7) / 8) * 8) * ASDR_SNAP_BYTES) == hipSuccess &&
+                  hipMemsetAsync(prog, 0, n_prog * sizeof(uint32_t), stream) == hipSuccess;
+  if (!ok) {   // (asdr_stream_pipeline_alloc_failures() counts this)
+    for (void *q : {(void *)xa, (void *)xb, (void *)prog, (void *)ring, snap}) if (q) hipFree(q);
+    (void)hipGetLastError();
+    b->stream_pipeline = false; b->stat_stream_alloc_failures++;
+    return false;
+  }
+  b->d_xch_a = xa; b->d_xch_b = xb; b->d_stream_prog = prog; b->d_lo_ring = ring; b->d_stream_snap = snap;
+  return true;
+}
+// do the call's output rows overlap its I or Q rows?
+bool rows_overlap(const asdr_batch *b, const CallPlan &p) {
+  const uintptr_t in_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)p.in_stride + (uintptr_t)p.n_blocks) * ASDR_N * sizeof(int16_t);
+  const uintptr_t out_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)p.out_stride + (uintptr_t)p.n_blocks) * ASDR_N * sizeof(int16_t);
+  const uintptr_t o0 = (uintptr_t)p.dOut, o1 = o0 + out_bytes, i = (uintptr_t)p.dI, q = (uintptr_t)p.dQ;
+  return (o0 < i + in_bytes && i < o1) || (o0 < q + in_bytes && q < o1);
+}
+// the lanes in use, and the stream of the uncut sub-ranges behind them, wait for `ev`
+int lanes_fork(asdr_batch *b, hipEvent_t ev) {
+  for (int i = 0; i <= b->sched_lanes; i++) {
+    hipStream_t ls = lane_stream(b, i == b->sched_lanes ? ASDR_LANES : i);
+    if (!ls) return fail("stream creation failed");
+    HIPCHK(hipStreamWaitEvent(ls, ev, 0));
+  }
+  return 0;
+}
+// the order of launched block lb of this call, for a sub-range that may take it: a direct group of the plain kind, one block per launch (the launcher has the last
+// word: asdr_launch_update_ordered reports whether the kernel it chose honours the field)
+uint32_t order_bit(const asdr_batch *b, const CallPlan &p, const Sub &su, int direct_ch0, int lb) {
+  const bool may = b->alternate_order && su.kind == ASDR_KERNEL_PLAIN && su.uniform && direct_ch0 >= 0 && (p.per_block || p.n_blocks == 1);
+  return may ? (b->wg_parity ^ (uint32_t)lb) & 1u : 0u;
+}
+// The end of every call: what the next call and the timing getters read, and the batch's block counters.  lo_flips: the launches that flipped the oscillator
+// cache's halves; order_flips: the launched blocks the alternating order counts; on_lanes: the call stays on the lanes, with nothing ordered behind it yet
+// (last_stream is then still the last ordinary call's).
+int end_call(asdr_batch *b, const CallPlan &p, int lo_flips, int order_flips, bool on_lanes) {
+  if (p.e1) HIPCHK(hipEventRecord(p.e1, p.stream));
+  b->ev_last_valid = true; b->ev_valid = (p.e0 != nullptr && p.e0 == b->ev0);
+  if (b->region_calls >= 0) b->region_calls++;
+  if (!on_lanes) b->last_stream = p.stream;
+  b->lanes_pending = on_lanes; b->last_was_lanes = on_lanes;
+  b->nb_phase = (b->nb_phase + (uint32_t)(p.n_blocks % 3)) % 3u; b->als_phase = (b->als_phase + (uint32_t)p.n_blocks) & 1u;
+  b->lo_parity ^= (uint32_t)(lo_flips & 1); b->wg_parity ^= (uint32_t)(order_flips & 1);
+  return 0;
+}
+// The call's arguments, its stream, whether it runs on the lanes, and its place behind the batch's earlier calls; setters and resets are applied here, so that what
+// follows plans from the schedule as it will be launched.  1: go on, 0: nothing to do, -1: error.
+int plan_enter(asdr_batch *b, CallPlan &p, const int16_t *dI, const int16_t *dQ, int16_t *dOut, int n_blocks, long in_stride_blocks,
+               long out_stride_blocks, void *stream_, int part, int parts) {
   if (!b) return fail("null batch");
   if (b->device == ASDR_NO_DEVICE) return fail("control-plane-only batch (ASDR_NO_DEVICE): the signal path needs a HIP device");
   if (!dI || !dQ) return 0;  // missing-input guard, AudioSDR.cpp:48-56
@@ -1171,61 +1299,52 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
   if (in_stride_blocks < n_blocks || out_stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
   if (in_stride_blocks > 0x7fffffffL || out_stride_blocks > 0x7fffffffL) return fail("row stride too large");
   if ((((uintptr_t)dI | (uintptr_t)dQ | (uintptr_t)dOut) & 15u) != 0) return fail("I/Q/out device pointers must be 16-byte aligned");
-  const bool batch_stream = (stream_ == ASDR_STREAM_BATCH);
-  hipStream_t stream = batch_stream ? b->stream : (hipStream_t)stream_;
+  p.dI = dI; p.dQ = dQ; p.dOut = dOut; p.n_blocks = n_blocks; p.part = part; p.parts = parts; p.in_stride = in_stride_blocks; p.out_stride = out_stride_blocks;
+  p.batch_stream = (stream_ == ASDR_STREAM_BATCH);
+  hipStream_t stream = p.stream = p.batch_stream ? b->stream : (hipStream_t)stream_;
   HIPCHK(hipSetDevice(b->device));
-  // Lanes (see asdr_batch): decided from the schedule as it stands -- a call that has setters or resets to apply runs the ordinary
-  // way (it synchronises anyway), the next one is back on the lanes.
-  bool use_lanes = false;
-  if (parts == 1 && b->lanes_enabled && !needs_flush(b) && (batch_stream || n_blocks >= 2) && !b->taps_on && b->tev.empty() && !b->time_calls) {
+  // Lanes (see asdr_batch): decided from the schedule as it stands -- a call that has setters or resets to apply runs the ordinary way (it synchronises anyway),
+  // the next one is back on the lanes.
+  p.use_lanes = false;
+  if (parts == 1 && b->lanes_enabled && !needs_flush(b) && (p.batch_stream || n_blocks >= 2) && !b->taps_on && b->tev.empty() && !b->time_calls) {
     int total = b->left_slots;
     for (int k = 0; k < ASDR_KERNEL_KINDS; k++) total += b->kind_slots[k];
     // (a call the block pipeline may take is not a lane call: the pipeline runs on `stream` and needs that stream's ordering)
     const bool pipeline_candidate = b->stream_pipeline && n_blocks >= ASDR_STREAM_MIN_BLOCKS && b->plain_uniform_ssb &&
                                     b->kind_uniform_slots[ASDR_KERNEL_PLAIN] > 0 && b->kind_uniform_slots[ASDR_KERNEL_PLAIN] / 8 <= b->stream_max_waves;
     bool lanes_ok = !pipeline_candidate && total / 8 >= b->lanes_min_waves;
-    // The first call that would take the lanes PROBES the pool on this device (once per device and process; not at asdr_create: a
-    // process that only ever calls on its own streams never creates the pool's lane streams -- every stream a process creates can push
-    // its other streams onto a shared hardware queue).  Serialised pool streams: the batch stays on the ordinary path unless the caller
-    // asked for the lanes explicitly (asdr_set_lanes).
+    // The first call that would take the lanes PROBES the pool on this device (once per device and process; not at asdr_create: a process that only ever calls on
+    // its own streams never creates the pool's lane streams -- every stream a process creates can push its other streams onto a shared hardware queue).  Serialised
+    // pool streams: the batch stays on the ordinary path unless the caller asked for the lanes explicitly (asdr_set_lanes).
     if (lanes_ok && !b->lanes_forced && lanes_overlap_probe(b->device) == 0) { b->lanes_enabled = false; lanes_ok = false; }
-    use_lanes = lanes_ok &&
-                (batch_stream || total >= 8 * ASDR_PER_BLOCK_LAUNCH_WAVES || (b->sam_split && b->kind_slots[ASDR_KERNEL_SAM] + b->kind_slots[ASDR_KERNEL_SAM_ALS] > 0) ||
-                 (b->als_split && b->kind_uniform_slots[ASDR_KERNEL_ALS_SMALL] > 0));   // (a strict call: only in its one-launch-per-block form)
+    p.use_lanes = lanes_ok &&
+                  (p.batch_stream || total >= 8 * ASDR_PER_BLOCK_LAUNCH_WAVES || (b->sam_split && b->kind_slots[ASDR_KERNEL_SAM] + b->kind_slots[ASDR_KERNEL_SAM_ALS] > 0) ||
+                   (b->als_split && b->kind_uniform_slots[ASDR_KERNEL_ALS_SMALL] > 0));   // (a strict call: only in its one-launch-per-block form)
   }
-  if (!use_lanes && b->lanes_pending) {   // an ordinary call after calls on the lanes: behind them
-    if (needs_flush(b)) { if (sync_all(b) != 0) return -1; }   // (the flush rewrites rows the lanes' kernels read)
-    else { if (lanes_join_into(b, stream) != 0) return -1; b->lanes_pending = false; }
-    b->last_stream = stream; b->last_was_lanes = false;
-  }
-  // one stream at a time per batch: a call on another stream first waits for the previous call's kernels (state in HBM is
-  // read-modify-written by every launch)
-  // (The event is recorded now, on the previous call's stream -- behind everything that call enqueued there -- rather than after
-  // every call: one packet less per launch for the common single-stream caller.)
-  if (part == 0 && b->ev_last_valid && stream != b->last_stream && !(use_lanes && batch_stream)) {
-    HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
-    HIPCHK(hipStreamWaitEvent(stream, b->ev_last, 0));
-  }
-  if (part == 0 && !use_lanes) {
+  if (!p.use_lanes && leave_lanes(b, stream) != 0) return -1;
+  // one stream at a time per batch: a call on another stream first waits for the previous call's kernels (state in HBM is read-modify-written by every launch)
+  if (part == 0 && b->ev_last_valid && stream != b->last_stream && !(p.use_lanes && p.batch_stream) && wait_for_last(b, stream) != 0) return -1;
+  if (part == 0 && !p.use_lanes) {
     if (flush(b, stream) != 0) return -1;
     if (apply_resets(b, stream) != 0) return -1;
   }
-  UpdateArgs a;
-  fill_args(b, a);
-  a.in_i = dI; a.in_q = dQ; a.out = dOut; a.n_blocks = n_blocks;
-  a.in_stride = (int32_t)in_stride_blocks; a.out_stride = (int32_t)out_stride_blocks;
-  // Timing markers are opt-in: every event record is a packet the GPU's command processor handles between two kernels
-  // (tools/launch_gap.py: 0.134 ms per back-to-back C2 call with a pair per call, 0.127 ms without).
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (parts == 1 && b->tev_used + 2 <= b->tev.size()) { e0 = b->tev[b->tev_used]; e1 = b->tev[b->tev_used + 1]; b->tev_used += 2; }
-  else if (b->time_calls) { e0 = b->ev0; e1 = b->ev1; }   // (around all parts of a call)
-  // Up to seven sub-ranges of the sorted schedule (the whole waves of 5 kernel kinds, the fused SAM kernel's general waves, the remainders).  They touch disjoint channels,
-  // so they run CONCURRENTLY: the first on the caller's stream, the others on the batch's helper streams, forked behind an
-  // event and joined before the call's end marker -- launched back to back on one stream the short ones (a handful of waves of
-  // the slowest instantiation) would each add a whole wave lifetime to the step.  Heaviest instantiation first.
-  struct Sub { int kind, uniform, first, slots; };
-  Sub subs[ASDR_KERNEL_KINDS + 2]; int n_sub = 0;
+  return 1;
+}
+// Everything else that is decided in front of the first launch, from the flushed schedule; the buffers a form needs are reserved here (a form whose buffers cannot
+// be had steps aside).
+int plan_launches(asdr_batch *b, CallPlan &p) {
+  const int n_blocks = p.n_blocks, parts = p.parts;
+  // Timing markers are opt-in: every event record is a packet the GPU's command processor handles between two kernels (tools/launch_gap.py: 0.134 ms per
+  // back-to-back C2 call with a pair per call, 0.127 ms without).
+  p.e0 = p.e1 = nullptr;
+  if (parts == 1 && b->tev_used + 2 <= b->tev.size()) { p.e0 = b->tev[b->tev_used]; p.e1 = b->tev[b->tev_used + 1]; b->tev_used += 2; }
+  else if (b->time_calls) { p.e0 = b->ev0; p.e1 = b->ev1; }   // (around all parts of a call)
+  // Up to seven sub-ranges of the sorted schedule (the whole waves of 5 kernel kinds, the fused SAM kernel's general waves, the remainders).  They touch disjoint
+  // channels, so they run CONCURRENTLY: the first on the caller's stream, the others on the batch's helper streams, forked behind an event and joined before the
+  // call's end marker -- launched back to back on one stream the short ones (a handful of waves of the slowest instantiation) would each add a whole wave lifetime
+  // to the step.  Heaviest instantiation first.
   static const int heaviest_first[ASDR_KERNEL_KINDS] = {ASDR_KERNEL_ALS, ASDR_KERNEL_SAM_ALS, ASDR_KERNEL_ALS_SMALL, ASDR_KERNEL_SAM, ASDR_KERNEL_PLAIN};
+  Sub *const subs = p.subs; int &n_sub = p.n_sub = 0;
   if (b->left_slots > 0) subs[n_sub++] = Sub{b->left_kind, 0, b->left_first, b->left_slots};   // a few long-lived waves: started first
   for (int kk = 0; kk < ASDR_KERNEL_KINDS; kk++) {
     const int k = heaviest_first[kk];
@@ -1234,231 +1353,65 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
     if (nu > 0) subs[n_sub++] = Sub{k, 1, b->kind_first[k], nu};
     if (nm > 0) subs[n_sub++] = Sub{k, 0, b->kind_first[k] + nu, nm};
   }
-  // A multi-block call on a LARGE batch is issued as one launch per block: only the first block of a launch can read the
-  // local-oscillator cache (wave 0 leaves the next LAUNCH's pairs), launches of >= 1024 waves follow each other without a gap
-  // (tools/launch_gap.py), and C2 x 64 blocks ran at 0.157 ms per block inside one launch against 0.129 ms as 64 launches.  Small
-  // batches (C5: 64 waves, 646 blocks) keep the in-kernel block loop: there a launch per 19-us block would be all overhead.
   int total_slots = 0;
   for (int i = 0; i < n_sub; i++) total_slots += subs[i].slots;
-  // SAM channels (no ALS) run as three launches per block -- everything in front of the PLL | the PLL with one LANE per channel |
-  // everything behind it -- through a 1 KB-per-slot exchange buffer: as a phase of one fused kernel the PLL's 128-step dependent
-  // chain kept a workgroup's other waves waiting (ASDR_SAM_FUSED=1 selects that kernel, for comparison).
+  // SAM channels (no ALS) run as three launches per block -- everything in front of the PLL | the PLL with one LANE per channel | everything behind it -- through a
+  // 1 KB-per-slot exchange buffer: as a phase of one fused kernel the PLL's 128-step dependent chain kept a workgroup's other waves waiting (ASDR_SAM_FUSED=1
+  // selects that kernel, for comparison).
   const int sam_slots = b->kind_slots[ASDR_KERNEL_SAM] + b->kind_slots[ASDR_KERNEL_SAM_ALS];
-  const bool sam_split = b->sam_split && sam_slots > 0;
-  if (sam_split && (size_t)sam_slots > b->xch_sam_slots) {
-    HIPCHK(hipStreamSynchronize(stream));
-    float *grown = nullptr;
-    HIPCHK(hipMalloc(&grown, 2 * ((size_t)sam_slots * 2 * ASDR_N * sizeof(float) + (size_t)sam_slots * sizeof(uint32_t))));   // two sets: tiles | tiles | lock words | lock words (pointer and size change only once this succeeded)
-    if (b->d_xch_sam) hipFree(b->d_xch_sam);
-    b->d_xch_sam = grown; b->xch_sam_slots = (size_t)sam_slots;
-  }
-  // tiles / lock words of the slots [first, ..) of a SAM kind's sub-range, set `parity` (0 everywhere but in the role streams below)
-  auto set_sam_rows = [&](UpdateArgs &x, int kind, int first, int parity) {
-    const size_t at = (size_t)(first - b->kind_first[kind]) + (kind == ASDR_KERNEL_SAM_ALS ? (size_t)b->kind_slots[ASDR_KERNEL_SAM] : 0);
-    x.xch_sam = b->d_xch_sam + ((size_t)parity * b->xch_sam_slots + at) * 2 * ASDR_N;
-    x.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam + 2 * b->xch_sam_slots * 2 * ASDR_N) + (size_t)parity * b->xch_sam_slots + at;
-  };
-  a.xch_sam = sam_split ? b->d_xch_sam : nullptr;
-  a.sam_lock = sam_split ? reinterpret_cast<uint32_t *>(b->d_xch_sam + 2 * b->xch_sam_slots * 2 * ASDR_N) : nullptr;
-  // ... and channels with a short ALS filter as two: the chain up to the AGC | the filter and the output stage (stage taps off: the taps
-  // of the last two stages are the fused kernel's)
-  const bool als_split = b->als_split && !b->taps_on && b->kind_uniform_slots[ASDR_KERNEL_ALS_SMALL] > 0;
-  // ALS role streams (asdr_batch::d_als_stage): the whole schedule is ONE uniform sub-range of short-filter channels of a known mode, small
-  // enough to be on the in-kernel block loop otherwise; not for in-place calls (the filter of a chunk writes output rows while the chain of
-  // the next one reads input rows), not with stage taps.
-  bool als_roles = b->als_role_streams && n_blocks >= 2 && parts == 1 && !use_lanes && !b->taps_on && !sam_split && !als_split && n_sub == 1 &&
+  p.sam_split = b->sam_split && sam_slots > 0;
+  if (p.sam_split && !reserve_tiles(b->d_xch_sam, b->xch_sam_slots, sam_slots, 2, p.stream)) return fail("SAM exchange tiles: out of device memory");
+  // ... and channels with a short ALS filter as two: the chain up to the AGC | the filter and the output stage (stage taps off: the taps of the last two stages are
+  // the fused kernel's)
+  p.als_split = b->als_split && !b->taps_on && b->kind_uniform_slots[ASDR_KERNEL_ALS_SMALL] > 0;
+  const bool io_alias = rows_overlap(b, p);
+  // ALS role streams (asdr_batch::d_als_stage): the whole schedule is ONE uniform sub-range of short-filter channels of a known mode, small enough to be on the
+  // in-kernel block loop otherwise; not for in-place calls (the filter of a chunk writes output rows while the chain of the next one reads input rows), not with
+  // stage taps.
+  bool als_roles = b->als_role_streams && n_blocks >= 2 && parts == 1 && !p.use_lanes && !b->taps_on && !p.sam_split && !p.als_split && n_sub == 1 &&
                    subs[0].kind == ASDR_KERNEL_ALS_SMALL && subs[0].uniform && total_slots <= 8 * ASDR_ALS_ROLE_MAX_WAVES &&
-                   b->sched[subs[0].first].mode <= 6u;
-  if (als_roles) {
-    const uintptr_t in_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)in_stride_blocks + (uintptr_t)n_blocks) * ASDR_N * sizeof(int16_t);
-    const uintptr_t out_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)out_stride_blocks + (uintptr_t)n_blocks) * ASDR_N * sizeof(int16_t);
-    const uintptr_t o0 = (uintptr_t)dOut, o1 = o0 + out_bytes;
-    for (uintptr_t i0 : {(uintptr_t)dI, (uintptr_t)dQ}) if (o0 < i0 + in_bytes && i0 < o1) als_roles = false;
-  }
+                   b->sched[subs[0].first].mode <= 6u && !io_alias;
   if (als_roles && !b->d_als_stage) {   // first use (a failed allocation leaves the batch on the block loop)
     float *st = nullptr;
     if (hipMalloc(&st, (size_t)(b->n + 1) * ASDR_ALS_STAGE_SLOTS * ASDR_N * sizeof(float)) == hipSuccess) b->d_als_stage = st; else { (void)hipGetLastError(); als_roles = false; }
   }
-  const bool per_block = n_blocks > 1 && (sam_split || als_split || total_slots >= 8 * ASDR_PER_BLOCK_LAUNCH_WAVES);
-  // Small batch, many blocks, one sub-range of uniform SSB-class waves, no taps: the block pipeline -- as a transaction: a snapshot of
-  // the state in front of it, and behind it the launches that put the state back and run the call on the in-kernel block loop if a
-  // role's bounded wait fired (asdr_kernels.hip).  3 w + 1 workgroups must be co-resident: w <= stream_max_waves (occupancy query at
-  // asdr_create, at most one workgroup per compute unit).
-  // The transaction restores channel STATE, not the caller's buffers: when the output rows alias an input row (the reference's own
-  // convention -- blockI is overwritten, AudioSDR.cpp:158-165) role 3 has overwritten input blocks by the time a wait runs out and the
-  // re-run would read them.  Such calls keep the in-kernel block loop, which is in-place safe.
-  bool io_alias = false;
-  {
-    const uintptr_t in_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)in_stride_blocks + (uintptr_t)n_blocks) * ASDR_N * sizeof(int16_t);
-    const uintptr_t out_bytes = ((uintptr_t)(b->n - 1) * (uintptr_t)out_stride_blocks + (uintptr_t)n_blocks) * ASDR_N * sizeof(int16_t);
-    const uintptr_t o0 = (uintptr_t)dOut, o1 = o0 + out_bytes;
-    for (uintptr_t i0 : {(uintptr_t)dI, (uintptr_t)dQ}) io_alias = io_alias || (o0 < i0 + in_bytes && i0 < o1);
-  }
-  // The pipeline takes the plain kind's uniform waves (SSB-class and AM groups).  What else the schedule holds -- the remainders' general
-  // waves, a few SAM or ALS channels among 4,000 receivers -- no longer disqualifies the call (round 3: n_sub == 1): while those
-  // sub-ranges are small they run the same call on the in-kernel block loop beside the pipeline, on helper streams.
-  int pipe_sub = -1, other_waves = 0;
-  for (int i = 0; i < n_sub; i++) { if (subs[i].kind == ASDR_KERNEL_PLAIN && subs[i].uniform) pipe_sub = i; else other_waves += subs[i].slots / 8; }
-  bool take_pipeline = parts == 1 && b->stream_pipeline && !io_alias && n_blocks >= ASDR_STREAM_MIN_BLOCKS && pipe_sub >= 0 && b->plain_uniform_ssb &&
-                       other_waves <= ASDR_STREAM_SIDE_WAVES && !sam_split && !als_split &&
+  // A multi-block call on a LARGE batch is issued as one launch per block: only the first block of a launch can read the local-oscillator cache (wave 0 leaves the
+  // next LAUNCH's pairs), launches of >= 1024 waves follow each other without a gap (tools/launch_gap.py), and C2 x 64 blocks ran at 0.157 ms per block inside one
+  // launch against 0.129 ms as 64 launches.  Small batches (C5: 64 waves, 646 blocks) keep the in-kernel block loop: there a launch per 19-us block would be all
+  // overhead.
+  p.per_block = n_blocks > 1 && (p.sam_split || p.als_split || total_slots >= 8 * ASDR_PER_BLOCK_LAUNCH_WAVES); p.n_launch = p.per_block ? n_blocks : 1;
+  // Small batch, many blocks, one sub-range of uniform SSB-class waves, no taps: the block pipeline -- as a transaction: a snapshot of the state in front of it,
+  // and behind it the launches that put the state back and run the call on the in-kernel block loop if a role's bounded wait fired (asdr_kernels.hip).  3 w + 1
+  // workgroups must be co-resident: w <= stream_max_waves (occupancy query at asdr_create, at most one workgroup per compute unit).
+  // The transaction restores channel STATE, not the caller's buffers: when the output rows alias an input row (the reference's own convention -- blockI is
+  // overwritten, AudioSDR.cpp:158-165) role 3 has overwritten input blocks by the time a wait runs out and the re-run would read them.  Such calls keep the
+  // in-kernel block loop, which is in-place safe.
+  // The pipeline takes the plain kind's uniform waves (SSB-class and AM groups).  What else the schedule holds -- the remainders' general waves, a few SAM or ALS
+  // channels among 4,000 receivers -- no longer disqualifies the call (round 3: n_sub == 1): while those sub-ranges are small they run the same call on the
+  // in-kernel block loop beside the pipeline, on helper streams.
+  p.pipe_sub = -1; p.other_waves = 0;
+  for (int i = 0; i < n_sub; i++) { if (subs[i].kind == ASDR_KERNEL_PLAIN && subs[i].uniform) p.pipe_sub = i; else p.other_waves += subs[i].slots / 8; }
+  p.take_pipeline = parts == 1 && b->stream_pipeline && !io_alias && n_blocks >= ASDR_STREAM_MIN_BLOCKS && p.pipe_sub >= 0 && b->plain_uniform_ssb &&
+                    p.other_waves <= ASDR_STREAM_SIDE_WAVES && !p.sam_split && !p.als_split &&
 #ifndef ASDR_TIMELINE   /* (the profiling build writes its timestamps through the taps buffer: tools/timeline.py stream) */
-                       !b->taps_on &&
+                    !b->taps_on &&
 #endif
-                       subs[pipe_sub].slots / 8 <= b->stream_max_waves;
-  // All 3 w pipeline workgroups must be RESIDENT together (the roles wait for each other).  The sub-ranges beside the pipeline are
-  // long-running kernels on helper streams started at the same fork: every one of their waves may hold a slot a role-3 workgroup needs
-  // (then roles 1 and 2 spin out their polls and the call is re-run from the snapshot: exact, but several times slower).  With side
-  // waves the pipeline therefore keeps headroom for them plus a margin; alone it may fill the device.
-  if (take_pipeline && other_waves > 0 && b->stream_cap_workgroups > 0 &&
-      3 * (subs[pipe_sub].slots / 8) + other_waves + ASDR_STREAM_SIDE_MARGIN > b->stream_cap_workgroups) { take_pipeline = false; b->stat_stream_headroom_refusals++; }
-  if (take_pipeline) {
-    if (!b->d_xch_a) {   // first use: every buffer, or none (a failed allocation leaves the batch on the other launch forms)
-      float *xa = nullptr, *xb = nullptr; uint32_t *prog = nullptr; LoEntry *ring = nullptr; void *snap = nullptr;
-      const size_t n_prog = (size_t)(3 * ((b->n + 7) / 8) + 3);   // [.. + 1] = the error word, [.. + 2] = the recovery counter
-      bool ok = hipMalloc(&xa, (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * 2 * ASDR_N * sizeof(float)) == hipSuccess &&
-                hipMalloc(&xb, (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * (ASDR_N + 1) * sizeof(float)) == hipSuccess &&   // + the AM carrier words (xch_c) behind the rows
-                hipMalloc(&prog, n_prog * sizeof(uint32_t)) == hipSuccess &&
-                hipMalloc(&ring, ASDR_LO_RING * sizeof(LoEntry)) == hipSuccess &&
-                hipMalloc(&snap, (size_t)(((b->n + 7) / 8) * 8) * ASDR_SNAP_BYTES) == hipSuccess &&
-                hipMemsetAsync(prog, 0, n_prog * sizeof(uint32_t), stream) == hipSuccess;
-      if (!ok) {   // the batch stays on the other launch forms (asdr_stream_pipeline_alloc_failures() counts this)
-        for (void *p : {(void *)xa, (void *)xb, (void *)prog, (void *)ring, snap}) if (p) hipFree(p);
-        (void)hipGetLastError();
-        b->stream_pipeline = false; b->stat_stream_alloc_failures++; take_pipeline = false;
-      } else {
-        b->d_xch_a = xa; b->d_xch_b = xb; b->d_stream_prog = prog; b->d_lo_ring = ring; b->d_stream_snap = snap;
-      }
-    }
-  }
-  if (take_pipeline) {
-    const UpdateArgs a_side = a;   // (for the sub-ranges beside the pipeline: before the pipeline's own fields are set)
-    const int w = subs[pipe_sub].slots / 8;
-    HIPCHK(hipMemsetAsync(b->d_stream_prog, 0, (size_t)(3 * w + 1) * sizeof(uint32_t), stream));   // stream-ordered behind the previous launch
-    if (n_sub > 1) HIPCHK(hipEventRecord(b->ev_fork, stream));
-    a.sched = b->d_sched + subs[pipe_sub].first; a.n_sched = subs[pipe_sub].slots;
-    a.direct_ch0 = -1; a.uni_valid = 0u;
-    if (b->kind_direct[ASDR_KERNEL_PLAIN]) { const SlotInfo &s0 = b->sched[subs[pipe_sub].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
-    a.lo_write = 0u;
-    a.xch_a = b->d_xch_a; a.xch_b = b->d_xch_b; a.xch_c = b->d_xch_b + (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * ASDR_N; a.stream_prog = b->d_stream_prog; a.stream_err = b->d_stream_prog + 3 * ((b->n + 7) / 8) + 1;
-    a.stream_waves = w; a.lo_ring = b->d_lo_ring; a.stream_spin_limit = b->stream_spin_limit;
-    if (e0) HIPCHK(hipEventRecord(e0, stream));
-    if (asdr_launch_stream_snapshot(&a, b->d_stream_snap, 0, stream) != 0) return fail("stream snapshot launch failed");
-    // three FIR helper waves per role-2 workgroup while every pipeline workgroup has a compute unit to itself (and the residency arithmetic above holds
-    // for the 256-thread form too); otherwise the two-wave form
-    const bool h3 = b->stream_h3 != 0 && b->stream_cap_h3 > 0 && 3 * w + other_waves + ASDR_STREAM_SIDE_MARGIN <= b->stream_cap_h3 &&
-                    (b->stream_h3 == 1 || 3 * w <= b->stream_cus);
-    if (h3) b->stat_stream_h3_calls++;
-    if (asdr_launch_stream(&a, stream, h3 ? 3 : 1) != 0) return fail("stream kernel launch failed");
-    if (asdr_launch_stream_snapshot(&a, b->d_stream_snap, 1, stream) != 0) return fail("stream restore launch failed");
-    {   // the same call on the in-kernel block loop, gated on the error word: its waves return at once when the pipeline completed
-      UpdateArgs f = a;
-      f.run_if = a.stream_err; f.stream_waves = 0; f.xch_a = nullptr; f.xch_b = nullptr; f.xch_c = nullptr; f.stream_prog = nullptr; f.lo_ring = nullptr;
-      if (asdr_launch_update(&f, ASDR_KERNEL_PLAIN, 1, stream) != 0) return fail("stream fallback launch failed");
-    }
-    if (asdr_launch_stream_ack(a.stream_err, stream) != 0) return fail("stream acknowledge launch failed");
-    {   // the other sub-ranges: the whole call on the in-kernel block loop, each on a helper stream beside the pipeline
-      int n_aux = 0;
-      for (int i = 0; i < n_sub; i++) {
-        if (i == pipe_sub) continue;
-        hipStream_t s = aux_stream(b, n_aux++);
-        if (!s) return fail("stream creation failed");
-        HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
-        UpdateArgs o = a_side;
-        o.sched = b->d_sched + subs[i].first; o.n_sched = subs[i].slots; o.direct_ch0 = -1; o.uni_valid = 0u; o.lo_write = 1u;
-        if (subs[i].uniform && b->kind_direct[subs[i].kind]) { const SlotInfo &s0 = b->sched[subs[i].first]; o.direct_ch0 = s0.ch; o.direct_mode = s0.mode; o.direct_flags = s0.flags; o.direct_lo = s0.lo; set_uni(b, o, s0.ch); }
-        if (asdr_launch_update(&o, subs[i].kind, subs[i].uniform, s) != 0) return fail("update kernel launch failed");
-        HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
-      }
-      for (int j = 0; j < n_aux; j++) HIPCHK(hipStreamWaitEvent(stream, b->ev_join[j], 0));
-    }
-    if (e1) HIPCHK(hipEventRecord(e1, stream));
-    b->stream_launched = true; b->stat_stream_launches++;
-    b->ev_last_valid = true;
-    b->ev_valid = (e0 != nullptr && e0 == b->ev0);
-    if (b->region_calls >= 0) b->region_calls++;
-    b->last_stream = stream; b->last_was_lanes = false;
-    b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
-    b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
-    b->lo_parity ^= 1u;
-    b->wg_parity ^= (uint32_t)(n_blocks & 1);
-    return 0;
-  }
-  // The largest sub-range runs on the caller's stream: back-to-back calls then follow each other there without a gap, the helper
-  // streams' joins (shorter kernels) are already satisfied when it ends, and only their starts pay the fork event's latency
-  // (C4: 28 us per call with the remainders' launch on the caller's stream).
-  const int n_launch = per_block ? n_blocks : 1;
-  // the order of launched block lb of this call, for a sub-range that may take it: a direct group of the plain kind, one block per launch
-  // (the launcher has the last word: asdr_launch_update_ordered reports whether the kernel it chose honours the field)
-  auto order_bit = [&](int kind, int uniform, int direct_ch0, int lb) -> uint32_t {
-    if (!b->alternate_order || kind != ASDR_KERNEL_PLAIN || !uniform || direct_ch0 < 0 || !(per_block || n_blocks == 1)) return 0u;
-    return (b->wg_parity ^ (uint32_t)lb) & 1u;
-  };
-  float *const taps = a.taps;
-  if (e0 && part == 0) HIPCHK(hipEventRecord(e0, stream));   // timing marker: right before the first launch
-  if (use_lanes) {
-    // fork: the lanes start behind the previous ordinary call (ASDR_STREAM_BATCH) / behind everything on the caller's stream so far
-    if (batch_stream) {
-      if (b->ev_last_valid && !b->last_was_lanes) {
-        HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
-        for (int i = 0; i <= b->sched_lanes; i++) { hipStream_t ls = lane_stream(b, i == b->sched_lanes ? ASDR_LANES : i); if (!ls) return fail("stream creation failed"); HIPCHK(hipStreamWaitEvent(ls, b->ev_last, 0)); }
-      }
-    } else {
-      HIPCHK(hipEventRecord(b->ev_fork, stream));
-      for (int i = 0; i <= b->sched_lanes; i++) { hipStream_t ls = lane_stream(b, i == b->sched_lanes ? ASDR_LANES : i); if (!ls) return fail("stream creation failed"); HIPCHK(hipStreamWaitEvent(ls, b->ev_fork, 0)); }
-    }
-    const int NL = b->sched_lanes;
-    for (int l = 0; l <= NL; l++) {   // l == NL: the sub-ranges that are not cut, on the stream behind the lanes (lane[ASDR_LANES])
-      hipStream_t ls = lane_stream(b, (l == NL) ? ASDR_LANES : l);
-      if (!ls) return fail("stream creation failed");
-      for (int lb = 0; lb < n_launch; lb++) {
-        for (int i = 0; i < n_sub; i++) {   // this lane's half of every uniform sub-range, one kernel after the other on the lane's stream;
-          const Sub &su = subs[i];          // the general-kernel sub-ranges (the remainders: a few long-lived waves) whole, on the stream behind the lanes
-          const long w = su.slots / 8;
-          int lo = (int)(w * l / NL) * 8, cnt = (int)(w * (l + 1) / NL) * 8 - lo;
-          if (l == NL) { lo = 0; cnt = su.uniform ? 0 : su.slots; } else if (!su.uniform) cnt = 0;
-          const int first = su.first + lo;
-          if (cnt == 0) continue;
-          UpdateArgs al = a;
-          al.sched = b->d_sched + first; al.n_sched = cnt;
-          al.direct_ch0 = -1; al.uni_valid = 0u;
-          if (su.uniform && b->kind_direct[su.kind]) { const SlotInfo &s0 = b->sched[su.first]; al.direct_ch0 = s0.ch + lo; al.direct_mode = s0.mode; al.direct_flags = s0.flags; al.direct_lo = s0.lo; set_uni(b, al, s0.ch); }
-          al.lo_cache = b->d_lo + (size_t)(1 + (l % ASDR_LANES)) * 2 * ASDR_LO_ENTRIES;   // this lane's own set: its writers fill it, its waves read it (general-kernel waves have no entry)
-          al.lo_write = 1u;
-          al.wg_reverse = order_bit(su.kind, su.uniform, al.direct_ch0, 0);
-          al.lo_writer_bit = ASDR_LO_WRITER_LANE(l % ASDR_LANES);   // (lane 0: ASDR_LO_WRITER; a direct launch: its wave 0, under any name)
-          if (sam_split && (su.kind == ASDR_KERNEL_SAM || su.kind == ASDR_KERNEL_SAM_ALS)) set_sam_rows(al, su.kind, first, 0);
-          const int form = (als_split && su.kind == ASDR_KERNEL_ALS_SMALL && su.uniform) ? 2 : su.uniform;
-          if (per_block) {
-            al.in_i = dI + (size_t)lb * ASDR_N; al.in_q = dQ + (size_t)lb * ASDR_N; al.out = dOut + (size_t)lb * ASDR_N; al.n_blocks = 1;
-            al.nb_phase = (b->nb_phase + (uint32_t)(lb % 3)) % 3u;
-            al.als_phase = (b->als_phase + (uint32_t)lb) & 1u;
-            al.lo_parity = b->lo_parity ^ (uint32_t)(lb & 1);
-            al.wg_reverse = order_bit(su.kind, su.uniform, al.direct_ch0, lb);
-          }
-          int rev = 0;
-          if (asdr_launch_update_ordered(&al, su.kind, form, ls, &rev) != 0) return fail("update kernel launch failed");
-          b->stat_reversed_launches += rev;
-        }
-      }
-    }
-    if (!batch_stream) { if (lanes_join_into(b, stream) != 0) return -1; b->lanes_pending = false; b->last_was_lanes = false; b->last_stream = stream; }
-    else { b->lanes_pending = true; b->last_was_lanes = true; }
-    b->ev_last_valid = true; b->ev_valid = false; b->stat_lane_calls++;
-    if (b->region_calls >= 0) b->region_calls++;
-    b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
-    b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
-    b->lo_parity ^= (uint32_t)(n_launch & 1);
-    b->wg_parity ^= (uint32_t)(n_launch & 1);
-    return 0;
-  }
-  // This part's waves of every sub-range, as launch items.  A large item is cut into `launch_split` pieces on as many streams
-  // (asdr_set_launch_split): kernels of one stream run one after the other, each draining its last waves before the next starts;
-  // pieces on different streams fill each other's tails.
-  struct Item { int sub, first, slots; };
-  Item items[ASDR_AUX_STREAMS + 1]; int n_items = 0;
+                    subs[p.pipe_sub].slots / 8 <= b->stream_max_waves;
+  // All 3 w pipeline workgroups must be RESIDENT together (the roles wait for each other).  The sub-ranges beside the pipeline are long-running kernels on helper
+  // streams started at the same fork: every one of their waves may hold a slot a role-3 workgroup needs (then roles 1 and 2 spin out their polls and the call is
+  // re-run from the snapshot: exact, but several times slower).  With side waves the pipeline therefore keeps headroom for them plus a margin; alone it may fill
+  // the device.
+  if (p.take_pipeline && p.other_waves > 0 && b->stream_cap_workgroups > 0 &&
+      3 * (subs[p.pipe_sub].slots / 8) + p.other_waves + ASDR_STREAM_SIDE_MARGIN > b->stream_cap_workgroups) { p.take_pipeline = false; b->stat_stream_headroom_refusals++; }
+  if (p.take_pipeline && !reserve_pipeline(b, p.stream)) p.take_pipeline = false;
+  p.n_items = 0; p.main_item = 0; p.sam_roles = p.sam_chunks = p.als_roles = false; p.n_chunks = 0;
+  if (p.take_pipeline || p.use_lanes) return 0;
+  // This part's waves of every sub-range, as launch items.  A large item is cut into `launch_split` pieces on as many streams (asdr_set_launch_split): kernels of
+  // one stream run one after the other, each draining its last waves before the next starts; pieces on different streams fill each other's tails.
+  Item *const items = p.items; int &n_items = p.n_items;
   for (int i = 0; i < n_sub; i++) {
     const long w = subs[i].slots / 8;
-    const int lo = (int)(w * part / parts) * 8, cnt = (int)(w * (part + 1) / parts) * 8 - lo;
+    const int lo = (int)(w * p.part / parts) * 8, cnt = (int)(w * (p.part + 1) / parts) * 8 - lo;
     if (cnt == 0) continue;
     int pieces = 1;
     if (b->launch_split > 1 && cnt / 8 >= b->launch_split_min_waves) pieces = std::min(b->launch_split, ASDR_AUX_STREAMS + 1 - n_items - (n_sub - 1 - i));
@@ -1468,197 +1421,255 @@ static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t 
       if (qhi > qlo && n_items < ASDR_AUX_STREAMS + 1) items[n_items++] = Item{i, subs[i].first + lo + qlo, qhi - qlo};
     }
   }
-  int main_item = 0;
-  for (int i = 1; i < n_items; i++) if (items[i].slots > items[main_item].slots) main_item = i;
-  // SAM role streams (see the launch below): a multi-block call whose schedule is ONE sub-range of SAM channels run as three launches
-  const bool sam_roles = b->sam_role_streams && per_block && n_launch >= 2 && parts == 1 && n_items == 1 && taps == nullptr && sam_split &&
-                         (subs[items[0].sub].kind == ASDR_KERNEL_SAM || subs[items[0].sub].kind == ASDR_KERNEL_SAM_ALS);
-  hipStream_t s_pre = nullptr, s_pll = nullptr;
-  if (sam_roles) {
-    s_pre = aux_stream(b, 0); s_pll = aux_stream(b, 1);
-    if (!s_pre || !s_pll) return fail("stream creation failed");
-    for (int i = 0; i < 6; i++) if (!b->ev_role[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_role[i], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(b->ev_fork, stream));
-    HIPCHK(hipStreamWaitEvent(s_pre, b->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(s_pll, b->ev_fork, 0));
-    b->stat_sam_role_calls++;
-  }
+  // The largest item runs on the caller's stream: back-to-back calls then follow each other there without a gap, the helper streams' joins (shorter kernels) are
+  // already satisfied when it ends, and only their starts pay the fork event's latency (C4: 28 us per call with the remainders' launch on the caller's stream).
+  for (int i = 1; i < n_items; i++) if (items[i].slots > items[p.main_item].slots) p.main_item = i;
+  const bool taps = b->taps_on && b->d_taps != nullptr;
+  // SAM role streams (launch_items): a multi-block call whose schedule is ONE sub-range of SAM channels run as three launches ...
+  p.sam_roles = b->sam_role_streams && p.per_block && p.n_launch >= 2 && parts == 1 && n_items == 1 && !taps && p.sam_split &&
+                (subs[items[0].sub].kind == ASDR_KERNEL_SAM || subs[items[0].sub].kind == ASDR_KERNEL_SAM_ALS);
   // ... in chunks when the sub-range is uniform, plain SAM (no ALS) and small: see asdr_batch::d_xch_sam_chunk
-  bool sam_chunks = sam_roles && subs[items[0].sub].kind == ASDR_KERNEL_SAM && subs[items[0].sub].uniform && n_blocks >= 2 * ASDR_SAM_CHUNK &&
-                    items[0].slots <= 8 * ASDR_SAM_CHUNK_MAX_WAVES && getenv("ASDR_NO_SAM_CHUNKS") == nullptr;
-  auto chunk_tiles = [&](int slots) -> bool {   // ASDR_SAM_CHUNK_SETS tile sets (+ lock words) for `slots` schedule slots; false: no memory
-    if ((size_t)slots <= b->xch_sam_chunk_slots) return true;
-    if (hipStreamSynchronize(stream) != hipSuccess) return false;
-    float *grown = nullptr;
-    const size_t per_set = (size_t)slots * 2 * ASDR_N * sizeof(float) + (size_t)slots * sizeof(uint32_t);
-    if (hipMalloc(&grown, ASDR_SAM_CHUNK_SETS * per_set) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (b->d_xch_sam_chunk) hipFree(b->d_xch_sam_chunk);
-    b->d_xch_sam_chunk = grown; b->xch_sam_chunk_slots = (size_t)slots;
-    return true;
-  };
-  if (sam_chunks && !chunk_tiles(items[0].slots)) sam_chunks = false;
-  int parity_launches_sam = -1;
-  if (sam_chunks) {
-    constexpr int S = ASDR_SAM_CHUNK_SETS, G = ASDR_SAM_CHUNK, R = S / G;
-    static_assert(S % G == 0 && R >= 4, "tile sets for four chunks");
-    for (int i = 0; i < 3 * R; i++) if (!b->ev_samc[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_samc[i], hipEventDisableTiming));
-    const int i0 = items[0].sub, first0 = items[0].first;
-    const size_t slots = b->xch_sam_chunk_slots;
-    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.uni_valid = 0u; a.lo_write = 1u;
-    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
-    a.xch_sam = b->d_xch_sam_chunk; a.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam_chunk + (size_t)S * slots * 2 * ASDR_N);
-    a.sam_sets = (uint32_t)S; a.sam_set_stride = (uint32_t)(slots * 2 * ASDR_N); a.sam_lock_stride = (uint32_t)slots;
-    a.taps = nullptr;
-    const int n_chunks = (n_blocks + G - 1) / G;
-    // TWO streams: the pre and post roles share the caller's stream -- pre(k + 1), then post(k) -- and the PLL has the helper stream to itself:
-    // its 32 us per block bound the call either way (pre + post are ~24), and a third stream is one too many for a process whose caller
-    // has a stream of its own (HIP's four hardware queues: 49 instead of 37 us per block measured with three, asdr.h "what the lanes rest on").
-    // Tile sets: pre(k) overwrites those of chunk k - R, whose post role is earlier in the same stream.
-    auto chunk_args = [&](int k) {
-      const int b0 = k * G, g = (n_blocks - b0 < G) ? n_blocks - b0 : G;
-      a.in_i = dI + (size_t)b0 * ASDR_N; a.in_q = dQ + (size_t)b0 * ASDR_N; a.out = dOut + (size_t)b0 * ASDR_N; a.n_blocks = g;
-      a.nb_phase = (b->nb_phase + (uint32_t)(b0 % 3)) % 3u;
-      a.als_phase = (b->als_phase + (uint32_t)b0) & 1u;
-      a.lo_parity = b->lo_parity ^ (uint32_t)(k & 1);
-      a.sam_set = (uint32_t)(b0 % S);
-    };
-    for (int k = 0; k <= n_chunks; k++) {
-      if (k < n_chunks) {
-        const int kr = k % R;
-        chunk_args(k);
-        if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 0, stream) != 0) return fail("update kernel launch failed");
-        HIPCHK(hipEventRecord(b->ev_samc[kr], stream)); HIPCHK(hipStreamWaitEvent(s_pll, b->ev_samc[kr], 0));
-        if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 1, s_pll) != 0) return fail("update kernel launch failed");
-        HIPCHK(hipEventRecord(b->ev_samc[R + kr], s_pll));
-      }
-      if (k >= 1) {
-        chunk_args(k - 1);
-        HIPCHK(hipStreamWaitEvent(stream, b->ev_samc[R + (k - 1) % R], 0));
-        if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 2, stream) != 0) return fail("update kernel launch failed");
-      }
-    }
-    parity_launches_sam = n_chunks;
-    b->stat_sam_chunk_calls++;
+  p.sam_chunks = p.sam_roles && b->sam_chunks && subs[items[0].sub].kind == ASDR_KERNEL_SAM && subs[items[0].sub].uniform && n_blocks >= 2 * ASDR_SAM_CHUNK &&
+                 items[0].slots <= 8 * ASDR_SAM_CHUNK_MAX_WAVES;
+  p.als_roles = als_roles && n_items == 1 && !taps;
+  static_assert(ASDR_SAM_CHUNK == ASDR_ALS_CHUNK, "the two chunked forms share the tile sets");
+  p.n_chunks = (n_blocks + ASDR_SAM_CHUNK - 1) / ASDR_SAM_CHUNK;
+  return 0;
+}
+// The block pipeline, as a transaction, with the other sub-ranges beside it on helper streams.
+int launch_pipeline(asdr_batch *b, const CallPlan &p, UpdateArgs &a) {
+  hipStream_t stream = p.stream;
+  const Sub &ps = p.subs[p.pipe_sub];
+  const UpdateArgs a_side = a;   // (for the sub-ranges beside the pipeline: before the pipeline's own fields are set)
+  const int w = ps.slots / 8;
+  HIPCHK(hipMemsetAsync(b->d_stream_prog, 0, (size_t)(3 * w + 1) * sizeof(uint32_t), stream));   // stream-ordered behind the previous launch
+  if (p.n_sub > 1) HIPCHK(hipEventRecord(b->ev_fork, stream));
+  select_slots(b, a, ps, ps.first, ps.slots, false);
+  a.lo_write = 0u;   // (the pipeline's oscillator role serves its own ring)
+  a.xch_a = b->d_xch_a; a.xch_b = b->d_xch_b; a.xch_c = b->d_xch_b + (size_t)(b->n + 1) * ASDR_STREAM_DEPTH * ASDR_N; a.stream_prog = b->d_stream_prog; a.stream_err = b->d_stream_prog + 3 * ((b->n + 7) / 8) + 1;
+  a.stream_waves = w; a.lo_ring = b->d_lo_ring; a.stream_spin_limit = b->stream_spin_limit;
+  if (p.e0) HIPCHK(hipEventRecord(p.e0, stream));
+  if (asdr_launch_stream_snapshot(&a, b->d_stream_snap, 0, stream) != 0) return fail("stream snapshot launch failed");
+  // three FIR helper waves per role-2 workgroup while every pipeline workgroup has a compute unit to itself (and the residency arithmetic of plan_launches holds
+  // for the 256-thread form too); otherwise the two-wave form
+  const bool h3 = b->stream_h3 != 0 && b->stream_cap_h3 > 0 && 3 * w + p.other_waves + ASDR_STREAM_SIDE_MARGIN <= b->stream_cap_h3 &&
+                  (b->stream_h3 == 1 || 3 * w <= b->stream_cus);
+  if (h3) b->stat_stream_h3_calls++;
+  if (asdr_launch_stream(&a, stream, h3 ? 3 : 1) != 0) return fail("stream kernel launch failed");
+  if (asdr_launch_stream_snapshot(&a, b->d_stream_snap, 1, stream) != 0) return fail("stream restore launch failed");
+  UpdateArgs f = a;   // the same call on the in-kernel block loop, gated on the error word: its waves return at once when the pipeline completed
+  f.run_if = a.stream_err; f.stream_waves = 0; f.xch_a = nullptr; f.xch_b = nullptr; f.xch_c = nullptr; f.stream_prog = nullptr; f.lo_ring = nullptr;
+  if (asdr_launch_update(&f, ASDR_KERNEL_PLAIN, 1, stream) != 0) return fail("stream fallback launch failed");
+  if (asdr_launch_stream_ack(a.stream_err, stream) != 0) return fail("stream acknowledge launch failed");
+  int n_aux = 0;   // the other sub-ranges: the whole call on the in-kernel block loop, each on a helper stream beside the pipeline
+  for (int i = 0; i < p.n_sub; i++) {
+    if (i == p.pipe_sub) continue;
+    hipStream_t s = aux_stream(b, n_aux++);
+    if (!s) return fail("stream creation failed");
+    HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
+    UpdateArgs o = a_side;
+    select_slots(b, o, p.subs[i], p.subs[i].first, p.subs[i].slots, false);
+    if (asdr_launch_update(&o, p.subs[i].kind, p.subs[i].uniform, s) != 0) return fail("update kernel launch failed");
+    HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
   }
-  const bool als_role_call = als_roles && n_items == 1 && taps == nullptr;
-  int parity_launches = n_launch;   // launches that flipped the oscillator cache's halves
-  if (als_role_call) {
-    // ALS role streams: chunks of ASDR_ALS_CHUNK blocks -- the chain up to the AGC (its block loop kept) on the helper stream, the filter + output
-    // on the caller's, chained by one event pair per chunk.  The chain's rows wait in the stage (slot = block % S); chain chunk k overwrites
-    // the slots filter chunk k - S / G + 1 reads its "previous block" from, so it waits for that launch -- the only back-pressure.  The two
-    // launches touch disjoint rows otherwise (the chain: filter states, rings, status; the filter: taps, output, the kept audio row).
-    constexpr int S = ASDR_ALS_STAGE_SLOTS, G = ASDR_ALS_CHUNK, R = S / G;
-    static_assert(S % G == 0 && R >= 3, "the stage holds at least three chunks");
-    hipStream_t s_chain = aux_stream(b, 0);
-    if (!s_chain) return fail("stream creation failed");
-    for (int i = 0; i < 2 * R; i++) if (!b->ev_als[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_als[i], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(b->ev_fork, stream));
-    HIPCHK(hipStreamWaitEvent(s_chain, b->ev_fork, 0));
-    const int i0 = items[0].sub, first0 = items[0].first;
-    a.sched = b->d_sched + first0; a.n_sched = items[0].slots; a.direct_ch0 = -1; a.uni_valid = 0u; a.lo_write = 1u;
-    if (b->kind_direct[subs[i0].kind]) { const SlotInfo &s0 = b->sched[subs[i0].first]; a.direct_ch0 = s0.ch; a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch); }
-    // the stage's "previous block" slot of the call's first block: the als_x ring's other slot as the last call left it
-    a.als_stage = b->d_als_stage; a.als_stage_cur = 0u; a.als_stage_prev = (uint32_t)(S - 1); a.als_phase = b->als_phase;
-    if (asdr_launch_als_stage_seed(&a, 0, b->n, s_chain) != 0) return fail("update kernel launch failed");
-    const int n_chunks = (n_blocks + G - 1) / G;
-    // Three stages (default): the chain itself is cut where the SAM roles cut it -- front half (scale, blanker, IF band-pass: the looped SAM
-    // pre role, into tile sets) | back half (mixer .. AGC, ROLE 10, from the tiles into the stage) | filter -- on three streams: the chain as
-    // ONE stage is 23 us per block for a lone wave and bounds the two-stage form; its halves are ~11 and ~13, the filter 18.
-    static_assert(ASDR_SAM_CHUNK == ASDR_ALS_CHUNK, "the two chunked forms share the tile sets");
-    constexpr int RT = ASDR_SAM_CHUNK_SETS / G;
-    static_assert(RT == R, "the front stage's wait indexes ev_als[(k - RT) % R]: the event of back chunk k - RT only while tile sets and stage slots hold the same number of chunks");
-    hipStream_t s_front = nullptr;
-    bool three = b->als_role_stages == 3 && chunk_tiles(items[0].slots);
-    if (three) { s_front = aux_stream(b, 1); if (!s_front) three = false; }
-    if (three) {
-      for (int i = 2 * R; i < 3 * R; i++) if (!b->ev_als[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_als[i], hipEventDisableTiming));
-      HIPCHK(hipStreamWaitEvent(s_front, b->ev_fork, 0));
-      const size_t slots = b->xch_sam_chunk_slots;
-      a.xch_sam = b->d_xch_sam_chunk; a.sam_lock = reinterpret_cast<uint32_t *>(b->d_xch_sam_chunk + (size_t)ASDR_SAM_CHUNK_SETS * slots * 2 * ASDR_N);
-      a.sam_sets = (uint32_t)ASDR_SAM_CHUNK_SETS; a.sam_set_stride = (uint32_t)(slots * 2 * ASDR_N); a.sam_lock_stride = (uint32_t)slots;
-    }
-    for (int k = 0; k < n_chunks; k++) {
-      const int b0 = k * G, g = (n_blocks - b0 < G) ? n_blocks - b0 : G;
-      a.in_i = dI + (size_t)b0 * ASDR_N; a.in_q = dQ + (size_t)b0 * ASDR_N; a.out = dOut + (size_t)b0 * ASDR_N; a.n_blocks = g;
-      a.nb_phase = (b->nb_phase + (uint32_t)(b0 % 3)) % 3u;
-      a.als_phase = (b->als_phase + (uint32_t)b0) & 1u;
-      a.lo_parity = b->lo_parity ^ (uint32_t)(k & 1);
-      a.als_stage_cur = (uint32_t)(b0 % S); a.als_stage_prev = (uint32_t)((b0 + S - 1) % S);
-      a.sam_set = (uint32_t)(b0 % ASDR_SAM_CHUNK_SETS);
-      if (three) {   // front(k) writes the tile sets back(k - RT) read
-        if (k >= RT) HIPCHK(hipStreamWaitEvent(s_front, b->ev_als[(k - RT) % R], 0));
-        if (asdr_launch_als_role(&a, 2, s_front) != 0) return fail("update kernel launch failed");
-        HIPCHK(hipEventRecord(b->ev_als[2 * R + k % R], s_front)); HIPCHK(hipStreamWaitEvent(s_chain, b->ev_als[2 * R + k % R], 0));
-      }
-      if (k >= R - 1) HIPCHK(hipStreamWaitEvent(s_chain, b->ev_als[R + (k + 1) % R], 0));
-      if (asdr_launch_als_role(&a, three ? 3 : 0, s_chain) != 0) return fail("update kernel launch failed");
-      HIPCHK(hipEventRecord(b->ev_als[k % R], s_chain)); HIPCHK(hipStreamWaitEvent(stream, b->ev_als[k % R], 0));
-      if (asdr_launch_als_role(&a, 1, stream) != 0) return fail("update kernel launch failed");
-      HIPCHK(hipEventRecord(b->ev_als[R + k % R], stream));
-    }
-    parity_launches = n_chunks;
-    b->stat_als_role_calls++;
+  for (int j = 0; j < n_aux; j++) HIPCHK(hipStreamWaitEvent(stream, b->ev_join[j], 0));
+  b->stream_launched = true; b->stat_stream_launches++;
+  return end_call(b, p, 1, p.n_blocks, false);   // (one launch, which counts its blocks for the alternating order)
+}
+// The lanes: every uniform sub-range cut into sched_lanes pieces on as many never-joined streams, the general-kernel sub-ranges (the remainders: a few long-lived
+// waves) whole on the stream behind them.
+int launch_lanes(asdr_batch *b, const CallPlan &p, const UpdateArgs &a) {
+  // fork: the lanes start behind the previous ordinary call (ASDR_STREAM_BATCH) / behind everything on the caller's stream so far
+  hipEvent_t ev = p.batch_stream ? b->ev_last : b->ev_fork;
+  if (!p.batch_stream || (b->ev_last_valid && !b->last_was_lanes)) {
+    HIPCHK(hipEventRecord(ev, p.batch_stream ? b->last_stream : p.stream));
+    if (lanes_fork(b, ev) != 0) return -1;
   }
-  if (parity_launches_sam >= 0) parity_launches = parity_launches_sam;
-  for (int lb = 0; lb < ((als_role_call || sam_chunks) ? 0 : n_launch); lb++) {
-    if (per_block) {
-      a.in_i = dI + (size_t)lb * ASDR_N; a.in_q = dQ + (size_t)lb * ASDR_N; a.out = dOut + (size_t)lb * ASDR_N; a.n_blocks = 1;
-      a.nb_phase = (b->nb_phase + (uint32_t)(lb % 3)) % 3u;
-      a.als_phase = (b->als_phase + (uint32_t)lb) & 1u;
-      a.lo_parity = b->lo_parity ^ (uint32_t)(lb & 1);
-      a.taps = (lb == n_launch - 1) ? taps : nullptr;   // the taps are those of the call's last block
+  const int NL = b->sched_lanes;
+  for (int l = 0; l <= NL; l++) {   // l == NL: the sub-ranges that are not cut, on the stream behind the lanes (lane[ASDR_LANES])
+    hipStream_t ls = lane_stream(b, (l == NL) ? ASDR_LANES : l);
+    if (!ls) return fail("stream creation failed");
+    for (int lb = 0; lb < p.n_launch; lb++) {
+      for (int i = 0; i < p.n_sub; i++) {   // this lane's piece of every uniform sub-range, one kernel after the other on the lane's stream
+        const Sub &su = p.subs[i];
+        const long w = su.slots / 8;
+        int lo = (int)(w * l / NL) * 8, cnt = (int)(w * (l + 1) / NL) * 8 - lo;
+        if (l == NL) { lo = 0; cnt = su.uniform ? 0 : su.slots; } else if (!su.uniform) cnt = 0;
+        if (cnt == 0) continue;
+        UpdateArgs al = a;
+        select_slots(b, al, su, su.first + lo, cnt, true);
+        al.lo_cache = b->d_lo + (size_t)(1 + (l % ASDR_LANES)) * 2 * ASDR_LO_ENTRIES;   // this lane's own set: its writers fill it, its waves read it (general-kernel waves have no entry)
+        al.lo_writer_bit = ASDR_LO_WRITER_LANE(l % ASDR_LANES);   // (lane 0: ASDR_LO_WRITER; a direct launch: its wave 0, under any name)
+        if (p.sam_split && (su.kind == ASDR_KERNEL_SAM || su.kind == ASDR_KERNEL_SAM_ALS)) set_sam_rows(b, al, su.kind, su.first + lo, 0);
+        const int form = (p.als_split && su.kind == ASDR_KERNEL_ALS_SMALL && su.uniform) ? 2 : su.uniform;
+        if (p.per_block) point_at_blocks(b, p, al, lb, 1, lb);
+        al.wg_reverse = order_bit(b, p, su, al.direct_ch0, p.per_block ? lb : 0);   // (a lane reverses within its own piece)
+        int rev = 0;
+        if (asdr_launch_update_ordered(&al, su.kind, form, ls, &rev) != 0) return fail("update kernel launch failed");
+        b->stat_reversed_launches += rev;
+      }
     }
-    if (n_items > 1) HIPCHK(hipEventRecord(b->ev_fork, stream));
+  }
+  if (!p.batch_stream && lanes_join_into(b, p.stream) != 0) return -1;   // a strict call joins at its end; on ASDR_STREAM_BATCH the lanes stay pending
+  b->stat_lane_calls++;
+  return end_call(b, p, p.n_launch, p.n_launch, p.batch_stream);
+}
+// SAM role streams, the fork: the helper streams of the pre and PLL roles behind the caller's stream (both forms below start from it)
+int fork_sam_roles(asdr_batch *b, const CallPlan &p, hipStream_t &s_pre, hipStream_t &s_pll) {
+  s_pre = aux_stream(b, 0); s_pll = aux_stream(b, 1);
+  if (!s_pre || !s_pll) return fail("stream creation failed");
+  for (int i = 0; i < 6; i++) if (!b->ev_role[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_role[i], hipEventDisableTiming));
+  HIPCHK(hipEventRecord(b->ev_fork, p.stream)); HIPCHK(hipStreamWaitEvent(s_pre, b->ev_fork, 0)); HIPCHK(hipStreamWaitEvent(s_pll, b->ev_fork, 0));
+  b->stat_sam_role_calls++;
+  return 0;
+}
+// SAM role streams in chunks (asdr_batch::d_xch_sam_chunk): pre | PLL | post launches of ASDR_SAM_CHUNK blocks each. TWO streams: the pre and post roles share the
+// caller's stream -- pre(k + 1), then post(k) -- and the PLL has the helper stream to itself: its 32 us per block bound the call either way (pre + post are ~24),
+// and a third stream is one too many for a process whose caller has a stream of its own (HIP's four hardware queues: 49 instead of 37 us per block measured with
+// three, asdr.h "what the lanes rest on"). Tile sets: pre(k) overwrites those of chunk k - R, whose post role is earlier in the same stream.
+int launch_sam_chunks(asdr_batch *b, const CallPlan &p, UpdateArgs &a, hipStream_t s_pll) {
+  constexpr int S = ASDR_SAM_CHUNK_SETS, G = ASDR_SAM_CHUNK, R = S / G;
+  static_assert(S % G == 0 && R >= 4, "tile sets for four chunks");
+  hipStream_t stream = p.stream;
+  for (int i = 0; i < 3 * R; i++) if (!b->ev_samc[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_samc[i], hipEventDisableTiming));
+  select_slots(b, a, p.subs[p.items[0].sub], p.items[0].first, p.items[0].slots, false);
+  set_chunk_tiles(b, a);
+  a.taps = nullptr;
+  auto chunk_args = [&](int k) { point_at_blocks(b, p, a, k * G, std::min(G, p.n_blocks - k * G), k); a.sam_set = (uint32_t)(k * G % S); };
+  for (int k = 0; k <= p.n_chunks; k++) {
+    if (k < p.n_chunks) {
+      const int kr = k % R;
+      chunk_args(k);
+      if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 0, stream) != 0) return fail("update kernel launch failed");
+      HIPCHK(hipEventRecord(b->ev_samc[kr], stream)); HIPCHK(hipStreamWaitEvent(s_pll, b->ev_samc[kr], 0));
+      if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 1, s_pll) != 0) return fail("update kernel launch failed");
+      HIPCHK(hipEventRecord(b->ev_samc[R + kr], s_pll));
+    }
+    if (k >= 1) {
+      chunk_args(k - 1);
+      HIPCHK(hipStreamWaitEvent(stream, b->ev_samc[R + (k - 1) % R], 0));
+      if (asdr_launch_sam_role(&a, ASDR_KERNEL_SAM, 1, 2, stream) != 0) return fail("update kernel launch failed");
+    }
+  }
+  b->stat_sam_chunk_calls++;
+  return 0;
+}
+// ALS role streams: chunks of ASDR_ALS_CHUNK blocks -- the chain up to the AGC (its block loop kept) on the helper stream, the filter + output on the caller's,
+// chained by one event pair per chunk.  The chain's rows wait in the stage (slot = block % S); chain chunk k overwrites the slots filter chunk k - S / G + 1 reads
+// its "previous block" from, so it waits for that launch -- the only back-pressure.  The two launches touch disjoint rows otherwise (the chain: filter states,
+// rings, status; the filter: taps, output, the kept audio row).
+int launch_als_roles(asdr_batch *b, const CallPlan &p, UpdateArgs &a) {
+  constexpr int S = ASDR_ALS_STAGE_SLOTS, G = ASDR_ALS_CHUNK, R = S / G;
+  static_assert(S % G == 0 && R >= 3, "the stage holds at least three chunks");
+  hipStream_t stream = p.stream, s_chain = aux_stream(b, 0);
+  if (!s_chain) return fail("stream creation failed");
+  for (int i = 0; i < 2 * R; i++) if (!b->ev_als[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_als[i], hipEventDisableTiming));
+  HIPCHK(hipEventRecord(b->ev_fork, stream)); HIPCHK(hipStreamWaitEvent(s_chain, b->ev_fork, 0));
+  select_slots(b, a, p.subs[p.items[0].sub], p.items[0].first, p.items[0].slots, false);
+  // the stage's "previous block" slot of the call's first block: the als_x ring's other slot as the last call left it
+  a.als_stage = b->d_als_stage; a.als_stage_cur = 0u; a.als_stage_prev = (uint32_t)(S - 1); a.als_phase = b->als_phase;
+  if (asdr_launch_als_stage_seed(&a, 0, b->n, s_chain) != 0) return fail("update kernel launch failed");
+  // Three stages (default): the chain itself is cut where the SAM roles cut it -- front half (scale, blanker, IF band-pass: the looped SAM pre role, into tile
+  // sets) | back half (mixer .. AGC, ROLE 10, from the tiles into the stage) | filter -- on three streams: the chain as ONE stage is 23 us per block for a lone
+  // wave and bounds the two-stage form; its halves are ~11 and ~13, the filter 18.
+  constexpr int RT = ASDR_SAM_CHUNK_SETS / G;
+  static_assert(RT == R, "the front stage's wait indexes ev_als[(k - RT) % R]: the event of back chunk k - RT only while tile sets and stage slots hold the same number of chunks");
+  hipStream_t s_front = nullptr;
+  bool three = b->als_role_stages == 3 && reserve_chunk_tiles(b, p.items[0].slots, stream);
+  if (three) { s_front = aux_stream(b, 1); if (!s_front) three = false; }
+  if (three) {
+    for (int i = 2 * R; i < 3 * R; i++) if (!b->ev_als[i]) HIPCHK(hipEventCreateWithFlags(&b->ev_als[i], hipEventDisableTiming));
+    HIPCHK(hipStreamWaitEvent(s_front, b->ev_fork, 0));
+    set_chunk_tiles(b, a);
+  }
+  for (int k = 0; k < p.n_chunks; k++) {
+    const int b0 = k * G;
+    point_at_blocks(b, p, a, b0, std::min(G, p.n_blocks - b0), k);
+    a.als_stage_cur = (uint32_t)(b0 % S); a.als_stage_prev = (uint32_t)((b0 + S - 1) % S);
+    a.sam_set = (uint32_t)(b0 % ASDR_SAM_CHUNK_SETS);
+    if (three) {   // front(k) writes the tile sets back(k - RT) read
+      if (k >= RT) HIPCHK(hipStreamWaitEvent(s_front, b->ev_als[(k - RT) % R], 0));
+      if (asdr_launch_als_role(&a, 2, s_front) != 0) return fail("update kernel launch failed");
+      HIPCHK(hipEventRecord(b->ev_als[2 * R + k % R], s_front)); HIPCHK(hipStreamWaitEvent(s_chain, b->ev_als[2 * R + k % R], 0));
+    }
+    if (k >= R - 1) HIPCHK(hipStreamWaitEvent(s_chain, b->ev_als[R + (k + 1) % R], 0));
+    if (asdr_launch_als_role(&a, three ? 3 : 0, s_chain) != 0) return fail("update kernel launch failed");
+    HIPCHK(hipEventRecord(b->ev_als[k % R], s_chain)); HIPCHK(hipStreamWaitEvent(stream, b->ev_als[k % R], 0));
+    if (asdr_launch_als_role(&a, 1, stream) != 0) return fail("update kernel launch failed");
+    HIPCHK(hipEventRecord(b->ev_als[R + k % R], stream));
+  }
+  b->stat_als_role_calls++;
+  return 0;
+}
+// The item loop: the part's items side by side -- the largest on the caller's stream, the others on helper streams, forked and joined -- once for the whole call
+// (the in-kernel block loop) or once per block; a lone SAM item's blocks as role streams (s_pre, s_pll: fork_sam_roles).
+int launch_items(asdr_batch *b, const CallPlan &p, UpdateArgs &a, hipStream_t s_pre, hipStream_t s_pll) {
+  hipStream_t stream = p.stream;
+  float *const taps = a.taps;
+  for (int lb = 0; lb < p.n_launch; lb++) {
+    if (p.per_block) {
+      point_at_blocks(b, p, a, lb, 1, lb);
+      a.taps = (lb == p.n_launch - 1) ? taps : nullptr;   // the taps are those of the call's last block
+    }
+    if (p.n_items > 1) HIPCHK(hipEventRecord(b->ev_fork, stream));
     int n_aux = 0;
-    for (int it = 0; it < n_items; it++) {
-      const int i = items[it].sub, first = items[it].first;
-      hipStream_t s = (it == main_item) ? stream : aux_stream(b, n_aux++);
-      if (!s && it != main_item) return fail("stream creation failed");
-      if (it != main_item) HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
-      a.sched = b->d_sched + first; a.n_sched = items[it].slots;
-      a.direct_ch0 = -1; a.uni_valid = 0u;
-      a.lo_write = 1u;   // the first wave of every settings group fills the group's entry of the other half of the local-oscillator cache
-      if (subs[i].uniform && b->kind_direct[subs[i].kind]) {   // one key group of consecutive channels: no schedule reads in the waves
-        const SlotInfo &s0 = b->sched[subs[i].first];
-        a.direct_ch0 = s0.ch + (first - subs[i].first); a.direct_mode = s0.mode; a.direct_flags = s0.flags; a.direct_lo = s0.lo; set_uni(b, a, s0.ch);
-        if (first != subs[i].first) a.lo_write = 0u;   // (a direct launch's wave 0 is the writer: only the piece that holds the group's first wave)
-      }
-      a.wg_reverse = order_bit(subs[i].kind, subs[i].uniform, a.direct_ch0, per_block ? lb : 0);   // (a piece of a split launch reverses within itself)
-      const bool sam3 = sam_split && (subs[i].kind == ASDR_KERNEL_SAM || subs[i].kind == ASDR_KERNEL_SAM_ALS);
-      if (sam3) set_sam_rows(a, subs[i].kind, first, sam_roles ? (lb & 1) : 0);   // this sub-range's tiles (1 KB per slot, 8 slots per tile) and lock words
-      const int form = (als_split && subs[i].kind == ASDR_KERNEL_ALS_SMALL && subs[i].uniform) ? 2 : subs[i].uniform;
-      if (sam_roles) {
-        // SAM role streams: block lb's pre | PLL | post on three streams, chained by events, so that pre(lb + 1) and PLL(lb + 1) run beside
-        // post(lb) -- the PLL's 128-step chain per block (~32 us for any bank size) then bounds the call alone instead of adding to the
-        // other two roles.  The roles of a block touch disjoint state (as the block pipeline's: status bits by atomics, the lock flag
-        // beside the tiles), the tiles alternate between two sets, and pre(lb + 2) waits for post(lb) to have left its set.
+    for (int it = 0; it < p.n_items; it++) {
+      const Sub &su = p.subs[p.items[it].sub]; const int first = p.items[it].first;
+      hipStream_t s = (it == p.main_item) ? stream : aux_stream(b, n_aux++);
+      if (!s && it != p.main_item) return fail("stream creation failed");
+      if (it != p.main_item) HIPCHK(hipStreamWaitEvent(s, b->ev_fork, 0));
+      select_slots(b, a, su, first, p.items[it].slots, false);
+      a.wg_reverse = order_bit(b, p, su, a.direct_ch0, p.per_block ? lb : 0);   // (a piece of a split launch reverses within itself)
+      const bool sam3 = p.sam_split && (su.kind == ASDR_KERNEL_SAM || su.kind == ASDR_KERNEL_SAM_ALS);
+      if (sam3) set_sam_rows(b, a, su.kind, first, p.sam_roles ? (lb & 1) : 0);   // this sub-range's tiles (1 KB per slot, 8 slots per tile) and lock words
+      const int form = (p.als_split && su.kind == ASDR_KERNEL_ALS_SMALL && su.uniform) ? 2 : su.uniform;
+      if (p.sam_roles) {
+        // SAM role streams: block lb's pre | PLL | post on three streams, chained by events, so that pre(lb + 1) and PLL(lb + 1) run beside post(lb) -- the PLL's
+        // 128-step chain per block (~32 us for any bank size) then bounds the call alone instead of adding to the other two roles.  The roles of a block touch
+        // disjoint state (as the block pipeline's: status bits by atomics, the lock flag beside the tiles), the tiles alternate between two sets, and pre(lb + 2)
+        // waits for post(lb) to have left its set.
         const int pa = lb & 1;
         if (lb >= 2) HIPCHK(hipStreamWaitEvent(s_pre, b->ev_role[4 + pa], 0));
-        if (asdr_launch_sam_role(&a, subs[i].kind, form, 0, s_pre) != 0) return fail("update kernel launch failed");
+        if (asdr_launch_sam_role(&a, su.kind, form, 0, s_pre) != 0) return fail("update kernel launch failed");
         HIPCHK(hipEventRecord(b->ev_role[pa], s_pre)); HIPCHK(hipStreamWaitEvent(s_pll, b->ev_role[pa], 0));
-        if (asdr_launch_sam_role(&a, subs[i].kind, form, 1, s_pll) != 0) return fail("update kernel launch failed");
+        if (asdr_launch_sam_role(&a, su.kind, form, 1, s_pll) != 0) return fail("update kernel launch failed");
         HIPCHK(hipEventRecord(b->ev_role[2 + pa], s_pll)); HIPCHK(hipStreamWaitEvent(stream, b->ev_role[2 + pa], 0));
-        if (asdr_launch_sam_role(&a, subs[i].kind, form, 2, stream) != 0) return fail("update kernel launch failed");
+        if (asdr_launch_sam_role(&a, su.kind, form, 2, stream) != 0) return fail("update kernel launch failed");
         HIPCHK(hipEventRecord(b->ev_role[4 + pa], stream));
         continue;
       }
       int rev = 0;
-      if (asdr_launch_update_ordered(&a, subs[i].kind, form, s, &rev) != 0) return fail("update kernel launch failed");
+      if (asdr_launch_update_ordered(&a, su.kind, form, s, &rev) != 0) return fail("update kernel launch failed");
       b->stat_reversed_launches += rev;
-      if (it != main_item) HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
+      if (it != p.main_item) HIPCHK(hipEventRecord(b->ev_join[n_aux - 1], s));
     }
     for (int j = 0; j < n_aux; j++) HIPCHK(hipStreamWaitEvent(stream, b->ev_join[j], 0));   // behind the caller's stream's own launch
   }
-  if (part + 1 < parts) return 0;   // the block counters advance with the call's last part
-  if (e1) HIPCHK(hipEventRecord(e1, stream));
-  b->ev_last_valid = true;
-  b->ev_valid = (e0 != nullptr && e0 == b->ev0);
-  if (b->region_calls >= 0) b->region_calls++;
-  b->last_stream = stream; b->last_was_lanes = false;
-  b->nb_phase = (b->nb_phase + (uint32_t)(n_blocks % 3)) % 3u;
-  b->als_phase = (b->als_phase + (uint32_t)n_blocks) & 1u;
-  b->lo_parity ^= (uint32_t)(parity_launches & 1);
-  b->wg_parity ^= (uint32_t)(n_launch & 1);
   return 0;
+}
+}  // namespace
+static int update_device_part(asdr_batch_t *b, const int16_t *dI, const int16_t *dQ, int16_t *dOut, int n_blocks,
+                              long in_stride_blocks, long out_stride_blocks, void *stream_, int part, int parts) {
+  CallPlan p;
+  const int go = plan_enter(b, p, dI, dQ, dOut, n_blocks, in_stride_blocks, out_stride_blocks, stream_, part, parts);
+  if (go <= 0) return go;
+  if (plan_launches(b, p) != 0) return -1;
+  UpdateArgs a;
+  fill_args(b, a);
+  a.in_i = dI; a.in_q = dQ; a.out = dOut; a.n_blocks = n_blocks; a.in_stride = (int32_t)in_stride_blocks; a.out_stride = (int32_t)out_stride_blocks;
+  a.xch_sam = p.sam_split ? b->d_xch_sam : nullptr;
+  a.sam_lock = p.sam_split ? reinterpret_cast<uint32_t *>(b->d_xch_sam + 2 * b->xch_sam_slots * 2 * ASDR_N) : nullptr;
+  if (p.take_pipeline) return launch_pipeline(b, p, a);
+  if (p.e0 && part == 0) HIPCHK(hipEventRecord(p.e0, p.stream));   // timing marker: right before the first launch
+  if (p.use_lanes) return launch_lanes(b, p, a);
+  hipStream_t s_pre = nullptr, s_pll = nullptr;
+  if (p.sam_roles && fork_sam_roles(b, p, s_pre, s_pll) != 0) return -1;
+  int lo_flips = p.n_launch;   // launches that flip the oscillator cache's halves: the chunked forms flip once per chunk
+  if (p.sam_chunks && reserve_chunk_tiles(b, p.items[0].slots, p.stream)) { if (launch_sam_chunks(b, p, a, s_pll) != 0) return -1; lo_flips = p.n_chunks; }
+  else if (p.als_roles) { if (launch_als_roles(b, p, a) != 0) return -1; lo_flips = p.n_chunks; }
+  else if (launch_items(b, p, a, s_pre, s_pll) != 0) return -1;
+  if (part + 1 < parts) return 0;   // the block counters advance with the call's last part
+  return end_call(b, p, lo_flips, p.n_launch, false);
 }
 
 extern "C" {
@@ -1944,11 +1955,7 @@ int host_update(asdr_batch *b, const int16_t *I, const int16_t *Q, int16_t *out,
   // Behind the lanes first: calls on ASDR_STREAM_BATCH may still be running on them, and what follows rewrites rows their kernels read
   // (the flush: parameters, schedule) and state they write (launch-form fuzz, seed 144: a setter, then this entry point, while lane 2 of a
   // nine-block call was still at block 3 -- its channel ran the rest of that call with the filter the setter had just enabled).
-  if (b->lanes_pending) {
-    if (needs_flush(b)) { if (sync_all(b) != 0) return -1; }
-    else { if (lanes_join_into(b, b->stream) != 0) return -1; b->lanes_pending = false; }
-    b->last_stream = b->stream; b->last_was_lanes = false;
-  }
+  if (leave_lanes(b, b->stream) != 0) return -1;
   // the schedule must exist before the plan can be read off it
   if (b->ev_last_valid && b->stream != b->last_stream) {
     HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
@@ -2147,11 +2154,7 @@ int asdr_order_before(asdr_batch_t *b, void *stream_) {   // everything enqueued
   HIPCHK(hipSetDevice(b->device));
   hipStream_t stream = (hipStream_t)stream_;
   if (b->lanes_pending && lanes_join_into(b, stream) != 0) return -1;
-  if (b->ev_last_valid && b->last_stream != stream && !b->last_was_lanes) {
-    HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
-    HIPCHK(hipStreamWaitEvent(stream, b->ev_last, 0));
-  }
-  return 0;
+  return (b->ev_last_valid && b->last_stream != stream && !b->last_was_lanes) ? wait_for_last(b, stream) : 0;
 }
 int asdr_order_after(asdr_batch_t *b, void *stream_) {   // the batch's calls on ASDR_STREAM_BATCH from now on run after everything enqueued on `stream` so far
   if (!b) return fail("null batch");
@@ -2866,11 +2869,7 @@ int state_stage_reserve(asdr_batch *b, size_t h_bytes, size_t d_bytes) {
 // (the rule of update_device_part)
 int state_order_in(asdr_batch *b, hipStream_t stream) {
   if (b->lanes_pending) { if (lanes_join_into(b, stream) != 0) return -1; b->lanes_pending = false; b->last_stream = stream; b->last_was_lanes = false; }
-  if (b->ev_last_valid && stream != b->last_stream) {
-    HIPCHK(hipEventRecord(b->ev_last, b->last_stream));
-    HIPCHK(hipStreamWaitEvent(stream, b->ev_last, 0));
-  }
-  return 0;
+  return (b->ev_last_valid && stream != b->last_stream) ? wait_for_last(b, stream) : 0;
 }
 void state_order_out(asdr_batch *b, hipStream_t stream) { b->last_stream = stream; b->ev_last_valid = true; b->last_was_lanes = false; }
 

@@ -202,7 +202,7 @@ long asdr_reversed_launches(asdr_batch_t *b);
 long asdr_sam_role_calls(asdr_batch_t *b);
 /* ... of which (round 5) ran the three roles in CHUNKS of 8 blocks per launch (their block loops kept, 32 tile sets): uniform SAM banks
  * without the ALS filter of up to 4,096 channels, calls of 16 blocks or more -- one event pair per chunk and role instead of per block.
- * Environment ASDR_NO_SAM_CHUNKS=1 keeps the per-block form. */
+ * Environment ASDR_NO_SAM_CHUNKS=1 at asdr_create time keeps the per-block form. */
 long asdr_sam_chunk_calls(asdr_batch_t *b);
 /* ALS role streams (round 5): a SMALL bank whose whole schedule is one settings group of channels with a short ALS filter (taps <= 64,
  * delay + taps <= 65; a known mode; below the one-launch-per-block size) runs a multi-block call as launches of 8 blocks per role on
