@@ -26,5 +26,7 @@ from .fm import (FM_CHUNK_BLOCKS, FM_EXPORTS, FM_MAX_NOISE, FM_NARROW_ROWS, FM_R
                  FM_WIDE_CHANNELS, FmDemodulator, fm_deemphasis_from_tau_us, fm_gain_from_deviation)
 from .tone import (CTCSS_TONES, TONE_ANY, TONE_EXPORTS, TONE_MAX_TONES, TONE_PASS, TONE_ROWS, TONE_STATE_DTYPE,  # noqa: E402
                    TONE_WAVE_ROWS, ToneSquelch, tone_highpass_design, tone_min_power)
+from .dcs import (DCS_ANY, DCS_CODES, DCS_EXPORTS, DCS_MAX_CODES, DCS_NARROW_ROWS, DCS_PASS, DCS_ROWS, DCS_STATE_DTYPE,  # noqa: E402
+                  DCS_WIDE_CHANNELS, DcsSquelch, dcs_word)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
