@@ -28,5 +28,7 @@ from .tone import (CTCSS_TONES, TONE_ANY, TONE_EXPORTS, TONE_MAX_TONES, TONE_PAS
                    TONE_WAVE_ROWS, ToneSquelch, tone_highpass_design, tone_min_power)
 from .dcs import (DCS_ANY, DCS_CODES, DCS_EXPORTS, DCS_MAX_CODES, DCS_NARROW_ROWS, DCS_PASS, DCS_ROWS, DCS_STATE_DTYPE,  # noqa: E402
                   DCS_WIDE_CHANNELS, DcsSquelch, dcs_word)
+from .packet import (PACKET_EXPORTS, PACKET_FRAME_DTYPE, PACKET_MAX_PAYLOAD, PACKET_MAX_RING, PACKET_NARROW_ROWS,  # noqa: E402
+                     PACKET_ROWS, PACKET_STATE_DTYPE, PACKET_WIDE_CHANNELS, PacketDecoder, packet_fcs, packet_format_address)
 
 __all__ = [n for n in dir() if not n.startswith("_")]
