@@ -6,7 +6,7 @@
  * loads, fully coalesced within each row):
  *
  *   params   ChanParams  [C+1]            96 B  read-only per launch (row C = dummy channel)
- *   small    ChanSmall   [C+1]           448 B  biquad states, phases, AGC/PLL/NB scalars, ring slots
+ *   small    ChanSmall   [C+1]           512 B  biquad states, phases, AGC/PLL/NB scalars, ring slots (the plain kind's fields in its first 256 B)
  *   nb_hist  int16       [C+1][3][2][128] 1.5 KiB noise-blanker ring of RAW samples: slot x {I,Q} x sample (oldest, middle,
  *                                                 newest); the gains in force at arrival are in ChanSmall.nb_gain
  *   nb_mask  uint8       [C+1][160]        160 B  mask codes of (middle block + 10 look-ahead), 138 used
@@ -21,6 +21,7 @@
 #ifndef ASDR_DEVICE_H_
 #define ASDR_DEVICE_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define ASDR_N 128
@@ -62,22 +63,37 @@ typedef struct {
   uint32_t pad_[4];
 } ChanParams; /* 24 words = 96 B */
 
+/* One 512-byte row = four aligned 128-byte lines.  What the plain kind of the chain kernel reads and writes every block -- the IF and audio biquad
+ * states and sixteen scalar words -- fills the first two lines; the AM image state, the PLL words (SAM only) and the padding lie behind them, so that
+ * a plain-kind wave touches two lines per channel and nothing it does not use.  (As a 448-byte row in declaration order of the reference's members,
+ * the unused image state lay between the two biquad states and the rows started at 0 and 64 modulo 128 in turns: three to four lines per
+ * channel each way.)  Every group the kernels move as 16 bytes starts on a multiple of 16.  A state record (include/asdr.h) keeps the members in
+ * the ORIGINAL order: asdr_state.hip translates, and its piece map names the offsets asserted below. */
 typedef struct {
-  float if_state[2][16];  /* [I,Q][stage][x1,x2,y1,y2]   _IFfilterStateI/Q   AudioSDR.h:191-192 */
-  float img_state[2][16]; /*                             _AMimage_stateI/Q  AudioSDR.h:193-194 */
-  float af_state[16];     /*                             _audio_filter_state AudioSDR.h:195     */
-  float phase_ssb, phase_am;          /* AudioSDR.cpp:43-44 */
+  float if_state[2][16];  /* [I,Q][stage][x1,x2,y1,y2]   _IFfilterStateI/Q   AudioSDR.h:191-192                    bytes   0..127 */
+  float af_state[16];     /*                             _audio_filter_state AudioSDR.h:195                               128..191 */
+  float phase_ssb, phase_am;          /* AudioSDR.cpp:43-44                                                               192..    */
   float nb_avg;                       /* _nb_AvgMag */
-  float am_carrier;                   /* _agc_AMcarrierLevel */
-  float agc_gain, agc_old_abs;        /* _agc_gain, _old_absVal */
+  float am_carrier;                   /* _agc_AMcarrierLevel                                                                 ..207 */
+  float agc_gain, agc_old_abs;        /* _agc_gain, _old_absVal                                                           208..    */
   uint32_t agc_hang_counter;
-  float pll_y_re, pll_y_im, pll_prev_filt;      /* AudioSDR.cpp:690-692 statics */
-  float pll_d0, pll_d1, pll_phase_est, pll_freq; /* delay0, delay1, phase_est, _PLLfreq */
-  uint32_t nb_slot_unused, hil_slot;  /* hil_slot: Hilbert ring parity (the blanker ring position is batch-wide: UpdateArgs.nb_phase) */
-  uint32_t status;                    /* ASDR_S_* bits */
-  float nb_gain[3][2];                /* input gains {I,Q} in force when each noise-blanker ring slot was written */
-  uint32_t pad_[9];
-} ChanSmall; /* 80 + 17 + 15 = 112 words = 448 B */
+  uint32_t nb_slot_unused;            /* (free)                                                                              ..223 */
+  uint32_t status;                    /* ASDR_S_* bits                                                                    224      */
+  float nb_gain[3][2];                /* input gains {I,Q} in force when each noise-blanker ring slot was written         228..251 */
+  uint32_t hil_slot;                  /* Hilbert ring parity (the blanker ring position is batch-wide: UpdateArgs.nb_phase)  252   */
+  float img_state[2][16]; /*                             _AMimage_stateI/Q  AudioSDR.h:193-194                            256..383 */
+  float pll_y_im, pll_prev_filt, pll_d0, pll_d1;   /* AudioSDR.cpp:690-692 statics; delay0, delay1                        384..399 */
+  float pll_phase_est, pll_freq, pll_y_re;         /* phase_est, _PLLfreq; the third static                               400..411 */
+  uint32_t pad_[25];
+} ChanSmall; /* 32 + 16 + 16 | 32 + 7 + 25 = 128 words = 512 B */
+#ifdef __cplusplus
+static_assert(sizeof(ChanSmall) == 512, "ChanSmall: four 128-byte lines");
+static_assert(offsetof(ChanSmall, if_state) == 0 && offsetof(ChanSmall, af_state) == 128 && offsetof(ChanSmall, phase_ssb) == 192 &&
+              offsetof(ChanSmall, agc_gain) == 208 && offsetof(ChanSmall, status) == 224 && offsetof(ChanSmall, nb_gain) == 228 &&
+              offsetof(ChanSmall, hil_slot) == 252, "ChanSmall: the plain kind's fields are the first 256 bytes, 16-byte groups aligned");
+static_assert(offsetof(ChanSmall, img_state) == 256 && offsetof(ChanSmall, pll_y_im) == 384 && offsetof(ChanSmall, pll_phase_est) == 400 &&
+              offsetof(ChanSmall, pll_y_re) == 408 && offsetof(ChanSmall, pad_) == 412, "ChanSmall: image state, PLL words and padding behind them");
+#endif
 
 #define ASDR_S_AGC_ACTIVE  (1u << 0) /* _agc_is_active (in-class initialiser: true) */
 #define ASDR_S_NB_DETECTED (1u << 1) /* _nb_impulseDetected */
@@ -213,7 +229,7 @@ typedef struct {
                                                re-run on the in-kernel block loop from a snapshot of the state (asdr_host.cpp), never with a hung GPU */
 #define ASDR_STREAM_FAIL 0xFFFFFFFFu        /* stream_wait: gave up (or another wave of the launch had) */
 /* per-channel state a pipeline call advances (plain instantiation, SSB-class modes): what the snapshot in front of it holds */
-#define ASDR_SNAP_BYTES (448 + 1536 + ASDR_NB_MASK_ROW + 1024 + 1024 + 512)   /* ChanSmall, nb_hist, nb_mask, hil_q, hil_i, audio_prev */
+#define ASDR_SNAP_BYTES ((int)sizeof(ChanSmall) + 1536 + ASDR_NB_MASK_ROW + 1024 + 1024 + 512)   /* ChanSmall, nb_hist, nb_mask, hil_q, hil_i, audio_prev */
 
 /* instantiations of the update kernel (asdr_launch_update) */
 #define ASDR_KERNEL_PLAIN 0

@@ -2773,8 +2773,7 @@ const StateField kStateFields[] = {
 };
 #undef SF_CW
 #undef SF_SM
-static_assert(offsetof(ChanSmall, hil_slot) == 4 * 95 && offsetof(ChanSmall, status) == 4 * 96 && offsetof(ChanSmall, nb_gain) == 4 * 97 &&
-              offsetof(ChanSmall, pll_freq) == 4 * 93 && offsetof(ChanSmall, phase_ssb) == 4 * 80, "field table");
+// (word = index in the record's signal part, which keeps ChanSmall's members in their original order -- not their offsets in the 512-byte row: asdr_state.hip)
 
 // header + control part of a record from the host half of a channel
 void control_to_record(const Chan &c, uint32_t content, uint8_t *dst) {

@@ -3658,6 +3658,7 @@ extern "C" int asdr_stream_capacity(int device, int *compute_units, int fir_help
 template <bool RESTORE>
 __device__ __forceinline__ void stream_snapshot_body(const UpdateArgs &a, uint4 *snap) {
   if (RESTORE && *a.stream_err == 0u) return;
+  constexpr int SMALL_PIECES = (int)(sizeof(ChanSmall) / 16);
   const int t = threadIdx.x;   // 256 threads
   for (int j = 0; j < 8; ++j) {
     const int slot = (int)blockIdx.x * 8 + j;
@@ -3668,8 +3669,8 @@ __device__ __forceinline__ void stream_snapshot_body(const UpdateArgs &a, uint4 
     // piece p of the channel's snapshot row: which array, which 16-byte piece of the channel's row in it
     for (int p = t; p < ASDR_SNAP_BYTES / 16; p += 256) {
       uint4 *row; int q = p;
-      if (q < 28) row = reinterpret_cast<uint4 *>(a.small + ch);
-      else if ((q -= 28) < 96) row = reinterpret_cast<uint4 *>(a.nb_hist + (size_t)ch * 768);
+      if (q < SMALL_PIECES) row = reinterpret_cast<uint4 *>(a.small + ch);
+      else if ((q -= SMALL_PIECES) < 96) row = reinterpret_cast<uint4 *>(a.nb_hist + (size_t)ch * 768);
       else if ((q -= 96) < ASDR_NB_MASK_ROW / 16) row = reinterpret_cast<uint4 *>(a.nb_mask + (size_t)ch * ASDR_NB_MASK_ROW);
       else if ((q -= ASDR_NB_MASK_ROW / 16) < 64) row = reinterpret_cast<uint4 *>(a.hil_q + (size_t)ch * 256);
       else if ((q -= 64) < 64) row = reinterpret_cast<uint4 *>(a.hil_i + (size_t)ch * 256);

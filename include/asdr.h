@@ -479,8 +479,9 @@ void asdr_kernels_launches_reset(void);
  *    140: u32 agc_hang_count   _agc_hangCount   144: u32 agc_en     _agc_enabled
  *    148: f32 nb_threshold     _nb_threshold    152: u32 nb_en      _nb_enabled         156: u32 zero
  *   signal part, in CANONICAL order: independent of the exporting batch's block count, launch form, shard and channel index
- *    160: ChanSmall (448 B, audiosdr_amd/csrc/asdr_device.h: the biquad states, phases, AGC / PLL / blanker scalars, status bits) with
- *         hil_slot = 0, nb_gain as [oldest, middle, newest][I, Q], its unused and pad words zero
+ *    160: ChanSmall's members (448 B: the biquad states, phases, AGC / PLL / blanker scalars, status bits) as 112 words in the order of
+ *         asdr_state_record_field's table -- the order of the record, not of the 512-byte row in HBM (audiosdr_amd/csrc/asdr_device.h;
+ *         asdr_state.hip translates) -- with hil_slot = 0, nb_gain as [oldest, middle, newest][I, Q], its unused and pad words zero
  *    608: i16 nb_hist[3][2][128]  the blanker's raw-sample ring as oldest, middle, newest: the two blocks the next update works on and the
  *                              slot its input goes to (whose content is dead: the block consumed last)
  *   2144: u8  nb_mask[160]     mask codes (138 used)
