@@ -3266,7 +3266,7 @@ ASDR_KERNEL(asdr_update_kernel_als_mixed, 8 * 516 + 260, ASDR_ALS_WAVES_PER_EU, 
 // ALS with a short filter (taps <= 64, delay + taps <= 65: the reference's defaults are 55 and 3) on a channel that is not in SAM
 // mode: the filter's rows fit the plain instantiation's 388 floats per channel -> 12 waves per CU
 ASDR_KERNEL(asdr_update_kernel_als_small, 8 * ASDR_ALS_STRIDE, ASDR_WAVES_PER_EU, ASDR_ALS_STRIDE, true, false, true, 1)
-ASDR_KERNEL(asdr_update_kernel_als_small_mixed, 8 * ASDR_ALS_STRIDE, ASDR_WAVES_PER_EU, ASDR_ALS_STRIDE, true, false, false, 1)
+// (no general form: the settings groups' remainders share one sub-range, which runs on the 516-float rows -- asdr_host.cpp flush_host, left_kind)
 // ... and the loop-free twin of the uniform short-filter kernel (one-block launches: every large batch)
 extern "C" __global__ __launch_bounds__(64, ASDR_WAVES_PER_EU) void asdr_update_kernel_als_small_one(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_ALS_STRIDE];
@@ -3312,10 +3312,7 @@ extern "C" __global__ __launch_bounds__(64, 2) void asdr_als_back_loop_kernel(Up
   asdr_update_body<ASDR_STRIDE, false, false, true, 1, 10>(a, lds);
 }
 // ... and for SAM channels with a short ALS filter (ASDR_KERNEL_SAM_ALS): the filter is the post role's last stage, on the compact rows
-extern "C" __global__ __launch_bounds__(64, ASDR_WAVES_PER_EU) void asdr_sam_post_als_kernel(UpdateArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_ALS_STRIDE];
-  asdr_update_body<ASDR_ALS_STRIDE, true, false, false, 1, 5>(a, lds);
-}
+// (whole waves of one schedule key only: the remainders of such groups run in asdr_update_kernel_als_mixed)
 extern "C" __global__ __launch_bounds__(64, ASDR_WAVES_PER_EU) void asdr_sam_post_als_kernel_uniform(UpdateArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[8 * ASDR_ALS_STRIDE];
   asdr_update_body<ASDR_ALS_STRIDE, true, false, true, 1, 5>(a, lds);
@@ -3585,7 +3582,6 @@ static const char *const k_kernel_names[] = {
   "asdr_als_stage_seed_kernel",
   "asdr_reset_kernel",
   "asdr_sam_pll_kernel",
-  "asdr_sam_post_als_kernel",
   "asdr_sam_post_als_kernel_uniform",
   "asdr_sam_post_kernel",
   "asdr_sam_post_kernel_uniform",
@@ -3603,7 +3599,6 @@ static const char *const k_kernel_names[] = {
   "asdr_update_kernel_als",
   "asdr_update_kernel_als_mixed",
   "asdr_update_kernel_als_small",
-  "asdr_update_kernel_als_small_mixed",
   "asdr_update_kernel_als_small_one",
   "asdr_update_kernel_c16",
   "asdr_update_kernel_mixed",
@@ -3741,14 +3736,14 @@ extern "C" int asdr_launch_update_ordered(const UpdateArgs *a, int variant, int 
     ASDR_LAUNCH(asdr_als_pre_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
     ASDR_LAUNCH(asdr_als_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
   }
-  else if (variant == ASDR_KERNEL_ALS_SMALL) { if (uniform && a->n_blocks == 1 && a->run_if == nullptr) ASDR_LAUNCH(asdr_update_kernel_als_small_one, dim3(n_waves), dim3(64), 0, stream, *a); else if (uniform) ASDR_LAUNCH(asdr_update_kernel_als_small, dim3(n_waves), dim3(64), 0, stream, *a); else ASDR_LAUNCH(asdr_update_kernel_als_small_mixed, dim3(n_waves), dim3(64), 0, stream, *a); }
+  else if (variant == ASDR_KERNEL_ALS_SMALL) { if (uniform && a->n_blocks == 1 && a->run_if == nullptr) ASDR_LAUNCH(asdr_update_kernel_als_small_one, dim3(n_waves), dim3(64), 0, stream, *a); else if (uniform) ASDR_LAUNCH(asdr_update_kernel_als_small, dim3(n_waves), dim3(64), 0, stream, *a); else return -1;   /* (no sub-range of this kind is ever non-uniform: the remainders' sub-range is of kind _ALS) */ }
   else if ((variant == ASDR_KERNEL_SAM || variant == ASDR_KERNEL_SAM_ALS) && a->xch_sam != nullptr) {   // pre | PLL | post (one block per call: the host loops)
+    if (variant == ASDR_KERNEL_SAM_ALS && !uniform) return -1;   // (as for _ALS_SMALL: whole waves only)
     if (uniform) ASDR_LAUNCH(asdr_sam_pre_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_sam_pre_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
     ASDR_LAUNCH(asdr_sam_pll_kernel, dim3((a->n_sched + ASDR_PLL_LANES - 1) / ASDR_PLL_LANES), dim3(64), 0, stream, *a);
     if (variant == ASDR_KERNEL_SAM_ALS) {
-      if (uniform) ASDR_LAUNCH(asdr_sam_post_als_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
-      else ASDR_LAUNCH(asdr_sam_post_als_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
+      ASDR_LAUNCH(asdr_sam_post_als_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     } else {
       if (uniform) ASDR_LAUNCH(asdr_sam_post_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
       else ASDR_LAUNCH(asdr_sam_post_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
@@ -3824,14 +3819,14 @@ extern "C" int asdr_launch_sam_role(const UpdateArgs *a, int variant, int unifor
     else ASDR_LAUNCH(asdr_sam_post_loop_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
+  if (variant == ASDR_KERNEL_SAM_ALS && !uniform) return -1;   // (whole waves only: asdr_launch_update_ordered)
   if (role == 0) {
     if (uniform) ASDR_LAUNCH(asdr_sam_pre_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_sam_pre_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
   } else if (role == 1) {
     ASDR_LAUNCH(asdr_sam_pll_kernel, dim3((a->n_sched + ASDR_PLL_LANES - 1) / ASDR_PLL_LANES), dim3(64), 0, stream, *a);
   } else if (variant == ASDR_KERNEL_SAM_ALS) {
-    if (uniform) ASDR_LAUNCH(asdr_sam_post_als_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
-    else ASDR_LAUNCH(asdr_sam_post_als_kernel, dim3(n_waves), dim3(64), 0, stream, *a);
+    ASDR_LAUNCH(asdr_sam_post_als_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
   } else {
     if (uniform) ASDR_LAUNCH(asdr_sam_post_kernel_uniform, dim3(n_waves), dim3(64), 0, stream, *a);
     else ASDR_LAUNCH(asdr_sam_post_kernel, dim3(n_waves), dim3(64), 0, stream, *a);

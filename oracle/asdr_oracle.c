@@ -681,6 +681,9 @@ uint32_t ao_getAGChangCount(const asdr_oracle_t *o) { return o->agc_hang_count; 
 /* test aids (read-only): the running hang counter and the envelope as the last block left them */
 uint32_t ao_test_get_agc_hang_counter(const asdr_oracle_t *o) { return o->agc_hang_counter; }
 float ao_test_get_agc_envelope(const asdr_oracle_t *o) { return o->agc_old_abs; }
+/* ... and the ALS filter's members as the last block left them: _ALSfilterCoeffs (128 floats), _ALSfilterInputBuffer (256 floats) */
+const float *ao_als_taps(const asdr_oracle_t *o) { return o->als_w; }
+const float *ao_als_history(const asdr_oracle_t *o) { return o->als_in; }
 void ao_get_chain_constants(const asdr_oracle_t *o, float out[12]) {
   const float v[12] = {o->pll_b0, o->pll_b1, o->pll_a1, o->alpha_freq, o->beta_freq, o->f_conv, o->lock_lo, o->lock_hi,
                        o->two_pi_f, o->half_pi_f, o->two_pi_f / AO_FS, o->nb_beta};

@@ -119,6 +119,8 @@ float ao_getAMcarrierLevel(const asdr_oracle_t *o);
 uint32_t ao_getAGChangCount(const asdr_oracle_t *o); /* not in the reference API; test aid */
 uint32_t ao_test_get_agc_hang_counter(const asdr_oracle_t *o); /* test aids: the running hang counter (.cpp:420, 423) ... */
 float ao_test_get_agc_envelope(const asdr_oracle_t *o);            /* ... and the envelope (_agc_oldAbs), after the last block */
+const float *ao_als_taps(const asdr_oracle_t *o);    /* ... the ALS filter's taps (.cpp:341-343), 128 floats ... */
+const float *ao_als_history(const asdr_oracle_t *o); /* ... and its input buffer (.cpp:329-333: previous block, last block), 256 floats */
 
 void ao_enableNoiseBlanker(asdr_oracle_t *o);
 void ao_disableNoiseBlanker(asdr_oracle_t *o);

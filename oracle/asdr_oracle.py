@@ -68,6 +68,8 @@ def lib():
     L.ao_tap.argtypes = [vp, i32]
     L.ao_tap.restype = fp
     L.ao_update.argtypes = [vp, i16p, i16p, i16p]
+    L.ao_als_taps.argtypes = [vp]; L.ao_als_taps.restype = fp
+    L.ao_als_history.argtypes = [vp]; L.ao_als_history.restype = fp
 
     def sig(name, args, res=None):
         fn = getattr(L, name)
@@ -212,6 +214,14 @@ class OracleSDR:
     def tap(self, name):
         p = self._L.ao_tap(self._h, TAPS.index(name))
         return np.ctypeslib.as_array(p, shape=(BLOCK,)).copy()
+
+    def als_taps(self):
+        """The ALS filter's 128 taps as the last block left them (a copy)."""
+        return np.ctypeslib.as_array(self._L.ao_als_taps(self._h), shape=(BLOCK,)).copy()
+
+    def als_history(self):
+        """The ALS filter's input buffer, previous block then last block: 256 floats (a copy)."""
+        return np.ctypeslib.as_array(self._L.ao_als_history(self._h), shape=(2 * BLOCK,)).copy()
 
 
 def run_channels(configure, I, Q):
