@@ -270,6 +270,33 @@ def test_schedule_layout_kinds_and_remainders(A):
     b.close()
 
 
+def test_schedule_layout_three_launch_sam_groups_give_whole_waves_only(A):
+    """In the three-launch form a SAM settings group contributes whole waves to the SAM sub-range and its remainder to the ONE remainders'
+    sub-range (kind 2 = the long-row ALS kernel, which carries the PLL): no SAM sub-range holds a wave of mixed keys, which is why the
+    pre / post roles exist for waves of one schedule key only and the launcher refuses anything else."""
+    n = 4096
+    b = A.AudioSDRBatch(n, device=-1)
+    # two settings groups with remainders: 301 SAM channels (296 + 5) and 299 SAM channels without AGC (296 + 3); 3,496 plain channels, whole waves
+    for c in range(1000, 1600):
+        b.setDemodMode(A.SAMmode, ch=c)
+    for c in range(1301, 1600):
+        b.disableAGC(ch=c)
+    b.control_plane_flush()
+    lay = b.schedule_layout()
+    assert lay["sam_three_launches"] and lay["sam"] == 592 and lay["sam_als"] == 0 and lay["plain"] == 3496
+    assert lay["remainders"] == 8 and lay["remainder_kind"] == 2
+    # a small split bank: 100 SAM channels (96 + 4), split from 1 channel on; the channels back in USB join the plain groups (3,697 = 3,696 + 1
+    # with AGC, 299 = 296 + 3 without)
+    b.set_sam_launch_form(False, 1)
+    for c in range(1100, 1600):
+        b.setDemodMode(A.USBmode, ch=c)
+    b.control_plane_flush()
+    lay = b.schedule_layout()
+    assert lay["sam_three_launches"] and lay["sam"] == 96 and lay["plain"] == 3992
+    assert lay["remainders"] == 8 and lay["remainder_kind"] == 2
+    b.close()
+
+
 def test_tuner_and_front_end_creates_refuse_a_bad_device_and_leave_nothing_behind(A):
     """device = 99: every create of the tuner bank and of the front end returns NULL with the device check's text ("bad device
     index"; on a machine without a GPU the check's first half speaks, "no HIP device"), and a control-plane create right behind

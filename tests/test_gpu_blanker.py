@@ -22,10 +22,7 @@ EVERY case asserts the launch census call by call (binding.kernels_launched): th
                 channel                         asdr_update_kernel_one (the 16-row recipes have no whole wave of one mode)
 
 (U is rounded up to whole waves; channel c takes row c % U.)  positions, pairs and dense go through every form, the other recipes through
-one (with and without taps), mw_u, mw and the pipeline.  tests/test_gpu_c16.py re-runs this file through the 16-waves-per-CU form, which reads the carried mask
-codes a second time on the general path: the census then names asdr_update_kernel_c16 where that form is taken (_c16)."""
-import os
-
+one (with and without taps), mw_u, mw and the pipeline."""
 import numpy as np
 import pytest
 
@@ -40,7 +37,7 @@ ONE, LOOP, MIXED = "asdr_update_kernel_one", "asdr_update_kernel", "asdr_update_
 STREAM, STREAM_H3 = "asdr_stream_kernel", "asdr_stream_kernel_h3"
 # what a pipeline call launches around the pipeline itself: the snapshot in front, and behind it the launches that act only if a wait ran out
 STREAM_AROUND = {"asdr_stream_snapshot_kernel", "asdr_stream_restore_kernel", "asdr_stream_ack_kernel", LOOP}
-SAM_FUSED, ALS_ONE, C16 = "asdr_update_kernel_sam", "asdr_update_kernel_als_small_one", "asdr_update_kernel_c16"
+SAM_FUSED, ALS_ONE = "asdr_update_kernel_sam", "asdr_update_kernel_als_small_one"
 C2 = [S("setDemodMode", USB), S("enableAudioFilter")]
 TAP_EVERY = 5                                     # taps on channels 0, 5, 10, ...: every row of a wave over the bank
 
@@ -72,22 +69,14 @@ class Form:
             out.append(min((2, 3, 5)[k % 3], nxt - pos)); pos += out[-1]; k += 1
         return out
 
-    def census(self, k, n, direct=True):
-        """the launches of a call of k blocks on a bank of n channels (None: the pipeline's, checked by _check_pipeline); direct: the
-        bank is one settings group"""
+    def census(self, k, n):
+        """the launches of a call of k blocks on a bank of n channels (None: the pipeline's, checked by _check_pipeline)"""
         if self.kernels is not None:
             kernels = self.kernels(n) if callable(self.kernels) else self.kernels
-            return {_c16(name, self, direct): v * k for name, v in kernels.items()}
+            return {name: v * k for name, v in kernels.items()}
         if self.plan == "pipe" and k >= 8:
             return None
-        return {_c16(ONE, self, direct): 1} if k == 1 else {LOOP: 1}
-
-
-def _c16(name, form, direct):
-    """tests/test_gpu_c16.py re-runs this file with ASDR_C16=1 ASDR_C16_MIN_WAVES=1: every direct one-block launch of an SSB-class group
-    without taps then takes asdr_update_kernel_c16 in place of the kernel named here"""
-    on = os.environ.get("ASDR_C16") == "1" and name in (ONE, F.MW_U, F.MW) and not form.taps and form.mode == USB and direct and form.name != "mixed"
-    return C16 if on else name
+        return {ONE: 1} if k == 1 else {LOOP: 1}
 
 
 def _mw_behind(U):
@@ -187,7 +176,7 @@ def _run(gpu, ao, recipe, form):
             b.synchronize()
             pos += k
             got = {name: v for name, v in gpu.binding.kernels_launched(reset=True).items() if name != "asdr_reset_kernel"}
-            want = form.census(k, n, direct=not any(m == "disableNoiseBlanker" and sel is not None for m, _a, sel in sc.setup))
+            want = form.census(k, n)
             if want is None:
                 pipelined += 1
                 _check_pipeline(got, form, b, pipelined)

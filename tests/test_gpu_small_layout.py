@@ -12,16 +12,11 @@ the int16 audio of every channel and block, nb_detected after every call -- with
 Inputs are rows of tests/blanker_scenarios.py whose carried mask is not all ones -- one impulse at p >= 117, pairs across the block's end,
 dense noise at ratio 2.0, the rows that disturb one lane of a wave alone --, with six quiet blocks appended: ten quiet blocks lead in,
 events at blocks 12, 16 and 20 leave codes other than 1 in the carried mask row, and the row is all ones again between them and in the
-tail.  The last test runs this file once more with ASDR_C16=1 ASDR_C16_MIN_WAVES=1 (as tests/test_gpu_c16.py does with its files): the
-census then names asdr_update_kernel_c16.
+tail.
 
 (The file was written for a word in ChanSmall that let these kernels skip the carried mask row while it is all ones; that change did not
 pass its timing gate -- profiles/README.md, top section; profiles/experiments/mask_word.diff -- and the sequences stayed: they are the
 ones in which a stale or misplaced scalar of the row shows in the audio.)"""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -33,17 +28,11 @@ from helpers import S, Hip
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-ONE, LOOP, STREAM, C16 = G.ONE, G.LOOP, G.STREAM, G.C16
+ONE, LOOP, STREAM = G.ONE, G.LOOP, G.STREAM
 C2 = [S("setDemodMode", USB), S("enableAudioFilter")]
 TAIL = 6                                          # quiet blocks behind the recipe's own 24
 FORMS = {"mw_u": (F.N, [], F.MW_U), "mw": (F.N, [S("setOutputGain", 0.7, sel=F.MID)], F.MW), "one-8": (8, [], ONE), "one-24": (24, [], ONE)}
 EVERY = list(FORMS)
-
-
-def _kernel(form):
-    """the kernel of a one-block call; under ASDR_C16=1 every direct one-block launch of an SSB-class group takes the 16-waves-per-CU form"""
-    return C16 if os.environ.get("ASDR_C16") == "1" else FORMS[form][2]
 
 
 def _with_tail(I, Q):
@@ -127,7 +116,7 @@ class _Bank:
                 assert got.get(STREAM) == 1 and set(got) <= G.STREAM_AROUND | {STREAM}, got
                 assert b.stream_pipeline_launches() == pipelined and b.stream_pipeline_recoveries() == 0
             else:
-                want = {_kernel(self.form): 1} if k == 1 else {LOOP: 1}
+                want = {FORMS[self.form][2]: 1} if k == 1 else {LOOP: 1}
                 assert got == want, "call of %d blocks ending at %d: launched %s, expected %s" % (k, pos, got, want)
             nb = b.read_status()["nb_detected"]
             bad = np.flatnonzero(nb != self.run.nb[:, pos - 1])
@@ -209,12 +198,3 @@ def test_multi_block_calls_then_one_block_calls(gpu, ao, form):
     finally:
         bank.close()
 
-
-def test_this_file_through_the_16_waves_per_cu_kernel(gpu):
-    if os.environ.get("ASDR_C16") == "1":
-        return                                    # (the re-run itself)
-    env = dict(os.environ, ASDR_C16="1", ASDR_C16_MIN_WAVES="1")
-    out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__)],
-                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1000:]
-    assert " passed" in out.stdout

@@ -3,12 +3,14 @@
 audiosdr_amd/csrc + include at <rev> and from the working tree (the library's flags, device side only, to assembly), drops
 the lines that differ by construction (`__hip_cuid_<hash of the source text>`, `.file`, `.ident`) and compares the listings
 kernel by kernel.  A refactor of the chain kernels that means to change no generated code is checked with this, without a GPU.
+A kernel on one side only is reported as `removed` or `added`: what it does to the others' listings by construction (the
+per-function ordinal in local labels, the column of a comment behind one) is taken out before the comparison.
 
   python tools/isa_diff.py [<rev>] [--src asdr_kernels.hip] [--variants] [-- extra hipcc flags]
 
 <rev> defaults to HEAD~1.  --variants repeats the comparison for every build that tools/ablate.py and tools/timeline.py
 make (-DASDR_TIMELINE, -DASDR_WAVES_PER_EU=2, -DASDR_PIPE_CHUNK=4, -DASDR_NB_ALWAYS_SLOW, each -DASDR_ABLATE=<mask>): those go
-through conditions that the default build never compiles.  Exit status 1 if any kernel differs; nothing in the checkout changes."""
+through conditions that the default build never compiles.  Exit status 1 if any kernel present on both sides differs; nothing in the checkout changes."""
 import argparse
 import difflib
 import io
@@ -26,25 +28,45 @@ from audiosdr_amd import build as b  # noqa: E402
 
 CSRC_REL = os.path.join("audiosdr_amd", "csrc")
 DROP = ("__hip_cuid_", ".file", ".ident")
+ORDINAL = re.compile(r"(LBB|\bBB|Lfunc_begin|Lfunc_end|LJTI|Ltmp)\d+")   # numbered per function in the order of the file: BB6_2, Lfunc_end6
+HEADER = re.compile(r"\s*\.(text|section|protected|globl|weak|hidden|p2align)\b")   # what stands between a function's end and the next one's .type
 
 
 def listing(tree, src, extra):
-    """{symbol: [lines]} of `src` compiled in `tree`: one entry per function or kernel, "(other)" for what precedes the first
-    and "(metadata)" for the code-object notes at the end."""
+    """the split() assembly of `src` compiled in `tree`"""
     flags = [f for f in b.FLAGS if f not in ("-shared", "-fPIC")]
     cmd = [b.hipcc(), "--offload-arch=" + b.ARCH] + flags + list(extra) + ["--cuda-device-only", "-S", src, "-o", "-"]
     out = subprocess.run(cmd, cwd=os.path.join(tree, CSRC_REL), capture_output=True, text=True)
     if out.returncode != 0:
         sys.exit("%s in %s does not compile:\n%s" % (src, tree, out.stderr[-3000:]))
+    return split(out.stdout)
+
+
+def split(asm):
+    """{symbol: [lines]} of an assembly listing: one entry per function or kernel, "(other)" for what precedes the first, "(metadata)"
+    for the frame of the code-object notes at the end and "(metadata) <kernel>" for a kernel's entry in them."""
     parts, cur = {}, "(other)"
-    for line in out.stdout.splitlines():
+    for line in asm.splitlines():
         if any(d in line for d in DROP):
             continue
+        line = re.sub(r"\s+;", " ;", ORDINAL.sub(r"\1#", line))
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
         if m:
-            cur = m.group(1)
-        elif line.strip() == ".amdgpu_metadata":
-            cur = "(metadata)"
+            prev, cur = parts.get(cur, []), m.group(1)
+            cut = len(prev)
+            while cut and HEADER.match(prev[cut - 1]):   # this function's own header lines
+                cut -= 1
+            parts[cur] = prev[cut:]
+            del prev[cut:]
+        elif line.strip() == ".amdgpu_metadata" or (cur.startswith("(metadata)") and not line.startswith("    ")):
+            cur = "(metadata)"   # the notes' frame; a kernel's entry goes under the kernel's name
+            if line.startswith("  - ."):
+                cur = "(metadata) entry"
+                parts.pop(cur, None)
+        elif cur == "(metadata) entry" and line.startswith("    .name:"):
+            name = "(metadata) " + line.split()[1]
+            parts[name] = parts.pop(cur)
+            cur = name
         parts.setdefault(cur, []).append(line)
     return parts
 
@@ -52,10 +74,12 @@ def listing(tree, src, extra):
 def compare(old, new, label):
     bad = 0
     for name in sorted(set(old) | set(new)):
-        a, c = old.get(name, []), new.get(name, [])
-        same = a == c
-        print("%-28s %-44s %s" % (label, name, "identical (%d lines)" % len(a) if same else "DIFFERS"))
-        if not same:
+        a, c = old.get(name), new.get(name)
+        state = "removed" if c is None else "added" if a is None else "identical (%d lines)" % len(a) if a == c else "DIFFERS"
+        if name.startswith("(metadata) ") and state != "DIFFERS":
+            continue   # (a kernel's entry in the notes is worth a line only where it differs on both sides)
+        print("%-28s %-44s %s" % (label, name, state))
+        if state == "DIFFERS":
             bad += 1
             for d in list(difflib.unified_diff(a, c, "rev", "tree", n=1, lineterm=""))[:24]:
                 print("    " + d)
@@ -84,7 +108,7 @@ def main():
         with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1, 2 * len(sets))) as pool:
             jobs = [(pool.submit(listing, old, args.src, s), pool.submit(listing, ROOT, args.src, s)) for s in sets]
             bad = sum(compare(o.result(), n.result(), " ".join(s) or "(default)") for (o, n), s in zip(jobs, sets))
-    print("%s: %s" % (args.src, "every kernel identical to %s" % args.rev if not bad else "%d listing(s) differ from %s" % (bad, args.rev)))
+    print("%s: %s" % (args.src, "every kernel on both sides identical to %s" % args.rev if not bad else "%d listing(s) differ from %s" % (bad, args.rev)))
     return 1 if bad else 0
 
 
