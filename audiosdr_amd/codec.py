@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _stride, i, ip, lg, typed_library, vp
 from .binding import AsdrError
 
 CODEC_EXPORTS = ["asdr_codec_create", "asdr_codec_destroy", "asdr_codec_n_channels", "asdr_codec_kind", "asdr_codec_row_bytes",
@@ -43,10 +43,11 @@ def _fits_long(*values):
         raise AsdrError("codec: argument out of range")
 
 
-class AudioCodec(ResetStage):
+class AudioCodec(RecordStage):
     """Encoder of n_channels receivers' int16 audio rows into packet rows of one kind (include/asdr_codec.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
     _prefix = "asdr_codec_"
+    _state_dtype = CODEC_STATE_DTYPE
 
     def __init__(self, n_channels, kind="adpcm", device=0):
         self._L = _lib()
@@ -67,7 +68,7 @@ class AudioCodec(ResetStage):
         e.g. a gate's index_tensor().data_ptr() / count_tensor().data_ptr()) output row i is channel index[i] for
         i < min(count, capacity_rows), read from input row index[i], or from input row i with rows_compact (a resampler's rows
         behind the same index); otherwise row c is channel c.  Returns the row's byte count."""
-        stride = int(n_samples) if row_stride_samples is None else int(row_stride_samples)
+        stride = _stride(row_stride_samples, n_samples)
         _fits_long(stride, n_samples, out_stride_bytes)
         return int(self._chk(self._L.asdr_codec_encode_device(self._h, C.c_void_p(ptr or None), stride, int(n_samples), int(bool(rows_compact)),
                                                               C.c_void_p(out_ptr or None), int(out_stride_bytes), C.c_void_p(index_ptr or None),
@@ -80,7 +81,7 @@ class AudioCodec(ResetStage):
         entries and k packet rows cross PCIe.  capacity_rows defaults to n_channels.  rows_out: a C-contiguous uint8 array
         [capacity_rows or more, row_bytes rounded up to 4] to receive the rows (pinned memory copies fastest; the returned rows are
         then a view of it) instead of a new array per call.  want_index = False passes no host index."""
-        stride = int(n_samples) if row_stride_samples is None else int(row_stride_samples)
+        stride = _stride(row_stride_samples, n_samples)
         _fits_long(stride, n_samples)
         cap = self.n_channels if capacity_rows is None else int(capacity_rows)
         room = self.n_channels if not index_ptr else max(0, min(cap, self.n_channels))
@@ -103,18 +104,6 @@ class AudioCodec(ResetStage):
     def decode(kind, rows, n_samples):
         """asdr_codec_decode over packet rows uint8 [k, >= row_bytes] (or one row): int16 [k, n_samples].  Host code."""
         return codec_decode(kind, rows, n_samples)
-
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of CODEC_STATE_DTYPE; waits for the codec's work."""
-        st = np.zeros(self.n_channels, dtype=CODEC_STATE_DTYPE)
-        self._chk(self._L.asdr_codec_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes CODEC_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=CODEC_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_codec_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
 
 
 def codec_row_bytes(kind, n_samples):

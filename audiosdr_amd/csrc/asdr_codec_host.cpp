@@ -11,8 +11,7 @@ static_assert(sizeof(asdr_codec_state_t) == 4, "asdr_codec_state_t is a 4-byte r
 
 struct asdr_codec : StageDev {
   int kind = 0;
-  std::vector<asdr_codec_state_t> host_state;   // ASDR_NO_DEVICE only
-  asdr_codec_state_t *d_state = nullptr;
+  StageRecords<asdr_codec_state_t> state;
   void *d_rows = nullptr;
   size_t rows_cap = 0;
 };
@@ -52,7 +51,7 @@ int launch(asdr_codec_t *c, const int16_t *dRows, long row_stride_samples, long 
   a.rows = dRows; a.row_stride = row_stride_samples;
   a.out = dOut; a.out_stride = out_stride_bytes;
   a.index = dIndex; a.count = dCount;
-  a.state = c->d_state;
+  a.state = c->state.dev;
   a.n_channels = c->n; a.n_samples = (int32_t)n_samples; a.grid_rows = grid_rows; a.capacity_rows = dIndex ? capacity_rows : c->n;
   a.rows_compact = rows_compact ? 1 : 0; a.kind = c->kind;
   a.aligned = (((uintptr_t)dRows & 15u) == 0 && row_stride_samples % 8 == 0) ? 1 : 0;
@@ -82,12 +81,12 @@ asdr_codec_t *asdr_codec_create(int n_channels, int kind, int device) {
   asdr_codec *c = new asdr_codec;
   c->n = n_channels; c->kind = kind;
   if (device == ASDR_NO_DEVICE) {
-    c->host_state.assign(n_channels, asdr_codec_state_t{});
+    c->state.zero(*c);
     return c;
   }
   const size_t bytes = (size_t)n_channels * sizeof(asdr_codec_state_t);
   if (stage_open(*c, device, "codec") != 0) { asdr_codec_destroy(c); return nullptr; }
-  if (hipMalloc(&c->d_state, bytes) != hipSuccess || hipMemset(c->d_state, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+  if (hipMalloc(&c->state.dev, bytes) != hipSuccess || hipMemset(c->state.dev, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     fail("codec: device allocation failed");
     asdr_codec_destroy(c);
     return nullptr;
@@ -97,7 +96,7 @@ asdr_codec_t *asdr_codec_create(int n_channels, int kind, int device) {
 
 void asdr_codec_destroy(asdr_codec_t *c) {
   if (!c) return;
-  stage_close(*c, {c->d_state, c->d_rows});
+  stage_close(*c, {c->state.dev, c->d_rows});
   delete c;
 }
 
@@ -205,25 +204,17 @@ int asdr_codec_decode(int kind, const uint8_t *row, long n_samples, int16_t *out
 
 int asdr_codec_read_state(asdr_codec_t *c, asdr_codec_state_t *dst) {
   if (!c) return fail("null codec");
-  return stage_read_state(*c, dst, sizeof(asdr_codec_state_t), c->host_state.data(), c->d_state);
+  return c->state.read(*c, dst);
 }
 
 int asdr_codec_write_state(asdr_codec_t *c, const int *channels, int n, const asdr_codec_state_t *src) {
   if (!c) return fail("null codec");
-  return stage_write_state(*c, channels, n, src, sizeof(asdr_codec_state_t), c->host_state.data(), c->d_state,
-                           [c](int k, const void *rec) { return check_record(c, k, *(const asdr_codec_state_t *)rec); });
+  return c->state.write(*c, channels, n, src, [c](int k, const asdr_codec_state_t &s) { return check_record(c, k, s); });
 }
 
 int asdr_codec_reset(asdr_codec_t *c) {
   if (!c) return fail("null codec");
-  if (c->device == ASDR_NO_DEVICE) {
-    c->host_state.assign(c->n, asdr_codec_state_t{});
-    return 0;
-  }
-  if (stage_quiesce(*c) != 0) return -1;
-  HIPCHK(hipMemsetAsync(c->d_state, 0, (size_t)c->n * sizeof(asdr_codec_state_t), c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return c->state.zero(*c);
 }
 
 int asdr_codec_synchronize(asdr_codec_t *c) {

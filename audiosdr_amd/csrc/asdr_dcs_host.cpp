@@ -11,28 +11,24 @@ static_assert(sizeof(asdr_dcs_state_t) == 192, "asdr_dcs_state_t is a 192-byte r
 static_assert(sizeof(DcsSetting) == 8, "DcsSetting is 8 bytes");
 
 struct asdr_dcs : StageDev {
-  std::vector<DcsSetting> set;
-  bool set_dirty = true, table_dirty = true;
+  StageMirror<DcsSetting> set;
+  StageMirror<uint32_t> words;                 // ASDR_DCS_MAX_CODES code words, 0 from n_codes on
   int codes[ASDR_DCS_MAX_CODES] = {};
-  uint32_t words[ASDR_DCS_MAX_CODES] = {};     // 0 from n_codes on
   int n_codes = 0, max_errors = 0, confirm = 2, hold_bits = 46;
-  std::vector<asdr_dcs_state_t> host_state;    // ASDR_NO_DEVICE only
+  StageRecords<asdr_dcs_state_t> state;
   long long blocks = 0;
-  DcsSetting *d_set = nullptr;
-  uint32_t *d_table = nullptr;
-  asdr_dcs_state_t *d_state = nullptr;
 };
 
 namespace {
 const char *kNoDevice = "control-plane-only DCS squelch (ASDR_NO_DEVICE): the signal path needs a HIP device";
 const uint32_t kWordMask = 0x7FFFFFu, kPoly = 0xC75u;
-const size_t kChunk = 4096;   // records per transfer of reset / clear / a new table
 
 // the fields a new table restores; the whole of a creation record around them
 void restart_decode(asdr_dcs_state_t &s) {
   s.sr = 0; s.cand = -1; s.age = 255; s.run = 0; s.detected = -1; s.quiet = 0;
 }
 
+// (detected = cand = -1, age = 255: creation and reset write records, they do not memset)
 asdr_dcs_state_t creation_record() {
   asdr_dcs_state_t s{};
   restart_decode(s);
@@ -63,49 +59,7 @@ int min_distance(const uint32_t *words, int n) {
 
 int check_handle(const asdr_dcs_t *t) { return t ? 0 : fail("null DCS squelch"); }
 
-int check_channel(const asdr_dcs_t *t, int ch, bool all_allowed) {
-  if (check_handle(t) != 0) return -1;
-  if (all_allowed && ch == ASDR_ALL) return 0;
-  return ch < 0 || ch >= t->n ? fail("bad channel") : 0;
-}
-
-template <class F>
-void apply(asdr_dcs_t *t, int ch, F change) {
-  if (ch == ASDR_ALL) for (DcsSetting &s : t->set) change(s);
-  else change(t->set[ch]);
-  t->set_dirty = true;
-}
-
-// every record through `change`, in chunks, behind the handle's work
-template <class F>
-int rewrite_records(asdr_dcs_t *t, F change) {
-  if (t->device == ASDR_NO_DEVICE) {
-    for (asdr_dcs_state_t &s : t->host_state) change(s);
-    return 0;
-  }
-  if (stage_quiesce(*t) != 0) return -1;
-  std::vector<asdr_dcs_state_t> buf(std::min((size_t)t->n, kChunk));
-  for (size_t c = 0; c < (size_t)t->n; c += kChunk) {
-    const size_t m = std::min(kChunk, (size_t)t->n - c);
-    HIPCHK(hipMemcpy(buf.data(), t->d_state + c, m * sizeof(asdr_dcs_state_t), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < m; k++) change(buf[k]);
-    HIPCHK(hipMemcpy(t->d_state + c, buf.data(), m * sizeof(asdr_dcs_state_t), hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
-// the creation record into every channel (detected = cand = -1, age = 255: records are written, not memset)
-int creation_state(asdr_dcs_t *t) {
-  if (t->device == ASDR_NO_DEVICE) {
-    t->host_state.assign(t->n, creation_record());
-    return 0;
-  }
-  if (stage_quiesce(*t) != 0) return -1;
-  const std::vector<asdr_dcs_state_t> buf(std::min((size_t)t->n, kChunk), creation_record());
-  for (size_t c = 0; c < (size_t)t->n; c += kChunk)
-    HIPCHK(hipMemcpy(t->d_state + c, buf.data(), std::min(kChunk, (size_t)t->n - c) * sizeof(asdr_dcs_state_t), hipMemcpyHostToDevice));
-  return 0;
-}
+int check_channel(const asdr_dcs_t *t, int ch, bool all_allowed) { return stage_check_channel(t, ch, all_allowed, "null DCS squelch"); }
 }  // namespace
 
 extern "C" {
@@ -128,17 +82,19 @@ asdr_dcs_t *asdr_dcs_create(int n_channels, int device) {
   if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_dcs *t = new asdr_dcs;
   t->n = n_channels;
-  t->set.assign(n_channels, DcsSetting{ASDR_DCS_PASS, 0});
+  t->set.host.assign(n_channels, DcsSetting{ASDR_DCS_PASS, 0});
+  t->words.host.assign(ASDR_DCS_MAX_CODES, 0u);
   t->n_codes = ASDR_DCS_COUNT;
-  for (int i = 0; i < ASDR_DCS_COUNT; i++) { t->codes[i] = ASDR_DCS_CODES[i]; t->words[i] = word_of(ASDR_DCS_CODES[i]); }
+  for (int i = 0; i < ASDR_DCS_COUNT; i++) { t->codes[i] = ASDR_DCS_CODES[i]; t->words.host[i] = word_of(ASDR_DCS_CODES[i]); }
   if (device == ASDR_NO_DEVICE) {
-    t->host_state.assign(n_channels, creation_record());
+    t->state.fill(*t, creation_record());
     return t;
   }
   const size_t n = n_channels;
   if (stage_open(*t, device, "dcs") != 0) { asdr_dcs_destroy(t); return nullptr; }
-  if (hipMalloc(&t->d_set, n * sizeof(DcsSetting)) != hipSuccess || hipMalloc(&t->d_state, n * sizeof(asdr_dcs_state_t)) != hipSuccess ||
-      hipMalloc(&t->d_table, sizeof(t->words)) != hipSuccess || creation_state(t) != 0 || hipDeviceSynchronize() != hipSuccess) {
+  if (hipMalloc(&t->set.dev, n * sizeof(DcsSetting)) != hipSuccess || hipMalloc(&t->state.dev, n * sizeof(asdr_dcs_state_t)) != hipSuccess ||
+      hipMalloc(&t->words.dev, ASDR_DCS_MAX_CODES * sizeof(uint32_t)) != hipSuccess || t->state.fill(*t, creation_record()) != 0 ||
+      hipDeviceSynchronize() != hipSuccess) {
     fail("dcs: device allocation failed");
     asdr_dcs_destroy(t);
     return nullptr;
@@ -148,7 +104,7 @@ asdr_dcs_t *asdr_dcs_create(int n_channels, int device) {
 
 void asdr_dcs_destroy(asdr_dcs_t *t) {
   if (!t) return;
-  stage_close(*t, {t->d_set, t->d_state, t->d_table});
+  stage_close(*t, {t->set.dev, t->state.dev, t->words.dev});
   delete t;
 }
 
@@ -165,26 +121,26 @@ int asdr_dcs_set_codes(asdr_dcs_t *t, const int *codes, int n_codes) {
   }
   if (min_distance(words, n_codes) < 2 * t->max_errors + 1)
     return fail("the table's words must differ in at least 2 max_errors + 1 = " + std::to_string(2 * t->max_errors + 1) + " bits");
-  if (rewrite_records(t, restart_decode) != 0) return -1;
+  if (t->state.rewrite(*t, restart_decode) != 0) return -1;
   std::fill(t->codes, t->codes + ASDR_DCS_MAX_CODES, 0);
   std::copy(codes, codes + n_codes, t->codes);
-  std::copy(words, words + ASDR_DCS_MAX_CODES, t->words);
+  std::copy(words, words + ASDR_DCS_MAX_CODES, t->words.host.begin());
   t->n_codes = n_codes;
-  t->table_dirty = true;
+  t->words.dirty = true;
   return 0;
 }
 
 int asdr_dcs_get_codes(const asdr_dcs_t *t, int *codes, uint32_t *words) {
   if (check_handle(t) != 0) return -1;
   if (codes) std::copy(t->codes, t->codes + t->n_codes, codes);
-  if (words) std::copy(t->words, t->words + t->n_codes, words);
+  if (words) std::copy(t->words.host.begin(), t->words.host.begin() + t->n_codes, words);
   return t->n_codes;
 }
 
 int asdr_dcs_set_max_errors(asdr_dcs_t *t, int max_errors) {
   if (check_handle(t) != 0) return -1;
   if (max_errors < 0 || max_errors > ASDR_DCS_MAX_ERRORS) return fail("max_errors must be in 0..3");
-  if (min_distance(t->words, t->n_codes) < 2 * max_errors + 1) return fail("max_errors: the table's words differ in too few bits for it");
+  if (min_distance(t->words.host.data(), t->n_codes) < 2 * max_errors + 1) return fail("max_errors: the table's words differ in too few bits for it");
   t->max_errors = max_errors;
   return 0;
 }
@@ -212,7 +168,7 @@ int asdr_dcs_get_hold_bits(const asdr_dcs_t *t) { return t ? t->hold_bits : fail
 int asdr_dcs_set_want(asdr_dcs_t *t, int ch, int want) {
   if (check_channel(t, ch, true) != 0) return -1;
   if (want < ASDR_DCS_PASS || want >= t->n_codes) return fail("want must be ASDR_DCS_PASS, ASDR_DCS_ANY or an entry of the table");
-  apply(t, ch, [=](DcsSetting &s) { s.want = want; });
+  t->set.apply(ch, [=](DcsSetting &s) { s.want = want; });
   return 0;
 }
 
@@ -224,7 +180,7 @@ int asdr_dcs_get_want(const asdr_dcs_t *t, int ch, int *want) {
 
 int asdr_dcs_set_hysteresis(asdr_dcs_t *t, int ch, uint32_t hysteresis) {
   if (check_channel(t, ch, true) != 0) return -1;
-  apply(t, ch, [=](DcsSetting &s) { s.hysteresis = hysteresis; });
+  t->set.apply(ch, [=](DcsSetting &s) { s.hysteresis = hysteresis; });
   return 0;
 }
 
@@ -238,30 +194,17 @@ int asdr_dcs_update_device(asdr_dcs_t *t, const int16_t *dIn, long in_stride_blo
                            void *stream_) {
   if (check_handle(t) != 0) return -1;
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-  if (!dIn || !dOut) return fail("null device pointer");
-  if (n_blocks < 0 || n_blocks > 65535) return fail("n_blocks must be in 0..65535");
-  if (in_stride_blocks < n_blocks || out_stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
-  if (in_stride_blocks > (1L << 30) || out_stride_blocks > (1L << 30)) return fail("row stride too large");
-  if ((((uintptr_t)dIn | (uintptr_t)dOut) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
+  if (stage_check_block_rows({{dIn}, t->n, in_stride_blocks}, {{dOut}, t->n, out_stride_blocks}, n_blocks, "output span overlaps the input span") != 0)
+    return -1;
   if (n_blocks == 0) return 0;
-  const size_t in_bytes = ((size_t)(t->n - 1) * in_stride_blocks + n_blocks) * 256, out_bytes = ((size_t)(t->n - 1) * out_stride_blocks + n_blocks) * 256;
-  if (overlap((uintptr_t)dIn, in_bytes, (uintptr_t)dOut, out_bytes)) return fail("output span overlaps the input span");
   hipStream_t stream = (hipStream_t)stream_;
-  if (stage_before_launch(*t, stream) != 0) return -1;
-  if (t->set_dirty) {
-    HIPCHK(hipMemcpyAsync(t->d_set, t->set.data(), t->set.size() * sizeof(DcsSetting), hipMemcpyHostToDevice, stream));
-    t->set_dirty = false;
-  }
-  if (t->table_dirty) {
-    HIPCHK(hipMemcpyAsync(t->d_table, t->words, sizeof(t->words), hipMemcpyHostToDevice, stream));
-    t->table_dirty = false;
-  }
+  if (stage_before_launch(*t, stream) != 0 || t->set.push(stream) != 0 || t->words.push(stream) != 0) return -1;
   DcsArgs a;
   a.in = dIn; a.out = dOut;
   a.in_stride_blocks = in_stride_blocks; a.out_stride_blocks = out_stride_blocks;
   a.n_channels = t->n; a.n_blocks = n_blocks;
   a.n_codes = t->n_codes; a.max_errors = t->max_errors; a.confirm = t->confirm; a.hold_bits = t->hold_bits;
-  a.table = t->d_table; a.set = t->d_set; a.state = t->d_state;
+  a.table = t->words.dev; a.set = t->set.dev; a.state = t->state.dev;
   if (asdr_launch_dcs(&a, stream) != 0) return fail("dcs kernel launch failed");
   if (stage_after_launch(*t, stream) != 0) return -1;
   t->blocks += n_blocks;
@@ -270,14 +213,13 @@ int asdr_dcs_update_device(asdr_dcs_t *t, const int16_t *dIn, long in_stride_blo
 
 int asdr_dcs_read_state(asdr_dcs_t *t, asdr_dcs_state_t *dst) {
   if (check_handle(t) != 0) return -1;
-  return stage_read_state(*t, dst, sizeof(asdr_dcs_state_t), t->host_state.data(), t->d_state);
+  return t->state.read(*t, dst);
 }
 
 int asdr_dcs_write_state(asdr_dcs_t *t, const int *channels, int n, const asdr_dcs_state_t *src) {
   if (check_handle(t) != 0) return -1;
   const int n_codes = t->n_codes;
-  auto check_record = [=](int k, const void *rec) {
-    const asdr_dcs_state_t &s = *(const asdr_dcs_state_t *)rec;
+  auto check_record = [=](int k, const asdr_dcs_state_t &s) {
     const std::string r = "record " + std::to_string(k);
     if (s.clk >= ASDR_DCS_CLOCK) return fail(r + ": clk must be below 2625");
     if (s.sr > kWordMask) return fail(r + ": sr must be below 2^23");
@@ -288,19 +230,19 @@ int asdr_dcs_write_state(asdr_dcs_t *t, const int *channels, int n, const asdr_d
     if (s.reserved[0] != 0 || s.reserved[1] != 0) return fail(r + ": reserved fields must be 0");
     return 0;
   };
-  return stage_write_state(*t, channels, n, src, sizeof(asdr_dcs_state_t), t->host_state.data(), t->d_state, check_record);
+  return t->state.write(*t, channels, n, src, check_record);
 }
 
 int asdr_dcs_clear(asdr_dcs_t *t) {
   if (check_handle(t) != 0) return -1;
-  if (rewrite_records(t, [](asdr_dcs_state_t &s) { s.bits = s.hits = s.detections = s.openings = s.open_blocks = s.edges = 0; }) != 0) return -1;
+  if (t->state.rewrite(*t, [](asdr_dcs_state_t &s) { s.bits = s.hits = s.detections = s.openings = s.open_blocks = s.edges = 0; }) != 0) return -1;
   t->blocks = 0;
   return 0;
 }
 
 int asdr_dcs_reset(asdr_dcs_t *t) {
   if (check_handle(t) != 0) return -1;
-  if (creation_state(t) != 0) return -1;
+  if (t->state.fill(*t, creation_record()) != 0) return -1;
   t->blocks = 0;
   return 0;
 }

@@ -12,35 +12,19 @@ static_assert(sizeof(asdr_fm_state_t) == 48, "asdr_fm_state_t is a 48-byte recor
 static_assert(sizeof(FmSetting) == 32, "FmSetting is 32 bytes");
 
 struct asdr_fm : StageDev {
-  std::vector<FmSetting> set;
-  bool set_dirty = true;
-  std::vector<asdr_fm_state_t> host_state;   // ASDR_NO_DEVICE only
+  StageMirror<FmSetting> set;
+  StageRecords<asdr_fm_state_t> state;
   long long blocks = 0;
-  FmSetting *d_set = nullptr;
-  asdr_fm_state_t *d_state = nullptr;
 };
 
 namespace {
 const char *kNoDevice = "control-plane-only FM demodulator (ASDR_NO_DEVICE): the signal path needs a HIP device";
 const double kFs = 44100.0;
 
-int check_channel(const asdr_fm_t *f, int ch, bool all_allowed) {
-  if (!f) return fail("null FM demodulator");
-  if (all_allowed && ch == ASDR_ALL) return 0;
-  return ch < 0 || ch >= f->n ? fail("bad channel") : 0;
-}
-
-// one setter's change on channel ch or on all of them
-template <class F>
-void apply(asdr_fm_t *f, int ch, F change) {
-  if (ch == ASDR_ALL) for (FmSetting &s : f->set) change(s);
-  else change(f->set[ch]);
-  f->set_dirty = true;
-}
+int check_channel(const asdr_fm_t *f, int ch, bool all_allowed) { return stage_check_channel(f, ch, all_allowed, "null FM demodulator"); }
 
 // write_state's check of record k beyond its channel
-int check_record(int k, const void *rec) {
-  const asdr_fm_state_t &s = *(const asdr_fm_state_t *)rec;
+int check_record(int k, const asdr_fm_state_t &s) {
   if (s.open > 1) return fail("record " + std::to_string(k) + ": open must be 0 or 1");
   if (s.reserved != 0 || s.reserved2 != 0) return fail("record " + std::to_string(k) + ": reserved fields must be 0");
   return 0;
@@ -65,15 +49,15 @@ asdr_fm_t *asdr_fm_create(int n_channels, int device) {
   if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_fm *f = new asdr_fm;
   f->n = n_channels;
-  f->set.assign(n_channels, FmSetting{ASDR_FM_MAX_NOISE, ASDR_FM_MAX_NOISE, asdr_fm_gain_from_deviation(5000.0), ASDR_FM_MAX_DEEMPHASIS, 0, 0});
+  f->set.host.assign(n_channels, FmSetting{ASDR_FM_MAX_NOISE, ASDR_FM_MAX_NOISE, asdr_fm_gain_from_deviation(5000.0), ASDR_FM_MAX_DEEMPHASIS, 0, 0});
   if (device == ASDR_NO_DEVICE) {
-    f->host_state.assign(n_channels, asdr_fm_state_t{});
+    f->state.zero(*f);
     return f;
   }
   const size_t n = n_channels;
   if (stage_open(*f, device, "fm") != 0) { asdr_fm_destroy(f); return nullptr; }
-  if (hipMalloc(&f->d_set, n * sizeof(FmSetting)) != hipSuccess || hipMalloc(&f->d_state, n * sizeof(asdr_fm_state_t)) != hipSuccess ||
-      hipMemset(f->d_state, 0, n * sizeof(asdr_fm_state_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+  if (hipMalloc(&f->set.dev, n * sizeof(FmSetting)) != hipSuccess || hipMalloc(&f->state.dev, n * sizeof(asdr_fm_state_t)) != hipSuccess ||
+      hipMemset(f->state.dev, 0, n * sizeof(asdr_fm_state_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     fail("fm: device allocation failed");
     asdr_fm_destroy(f);
     return nullptr;
@@ -83,7 +67,7 @@ asdr_fm_t *asdr_fm_create(int n_channels, int device) {
 
 void asdr_fm_destroy(asdr_fm_t *f) {
   if (!f) return;
-  stage_close(*f, {f->d_set, f->d_state});
+  stage_close(*f, {f->set.dev, f->state.dev});
   delete f;
 }
 
@@ -92,7 +76,7 @@ int asdr_fm_n_channels(const asdr_fm_t *f) { return f ? f->n : fail("null FM dem
 int asdr_fm_set_gain(asdr_fm_t *f, int ch, uint32_t gain) {
   if (check_channel(f, ch, true) != 0) return -1;
   if (gain < 1 || gain > ASDR_FM_MAX_GAIN) return fail("gain must be in 1..2^24");
-  apply(f, ch, [=](FmSetting &s) { s.gain = gain; });
+  f->set.apply(ch, [=](FmSetting &s) { s.gain = gain; });
   return 0;
 }
 
@@ -105,7 +89,7 @@ int asdr_fm_get_gain(const asdr_fm_t *f, int ch, uint32_t *gain) {
 int asdr_fm_set_deemphasis(asdr_fm_t *f, int ch, uint32_t a) {
   if (check_channel(f, ch, true) != 0) return -1;
   if (a < 1 || a > ASDR_FM_MAX_DEEMPHASIS) return fail("de-emphasis coefficient must be in 1..32768");
-  apply(f, ch, [=](FmSetting &s) { s.deemphasis = a; });
+  f->set.apply(ch, [=](FmSetting &s) { s.deemphasis = a; });
   return 0;
 }
 
@@ -118,7 +102,7 @@ int asdr_fm_get_deemphasis(const asdr_fm_t *f, int ch, uint32_t *a) {
 int asdr_fm_set_dc_shift(asdr_fm_t *f, int ch, int hp_shift) {
   if (check_channel(f, ch, true) != 0) return -1;
   if (hp_shift < 0 || hp_shift > ASDR_FM_MAX_DC_SHIFT) return fail("hp_shift must be in 0..15");
-  apply(f, ch, [=](FmSetting &s) { s.hp_shift = (uint32_t)hp_shift; });
+  f->set.apply(ch, [=](FmSetting &s) { s.hp_shift = (uint32_t)hp_shift; });
   return 0;
 }
 
@@ -133,7 +117,7 @@ int asdr_fm_set_squelch(asdr_fm_t *f, int ch, uint64_t open_noise, uint64_t clos
   if (open_noise > close_noise) return fail("open_noise must not exceed close_noise");
   if (close_noise > ASDR_FM_MAX_NOISE) return fail("the noise thresholds must not exceed 2^41");
   if (hang_blocks < 0 || hang_blocks > ASDR_FM_MAX_HANG) return fail("hang_blocks must be in 0..65535");
-  apply(f, ch, [=](FmSetting &s) { s.open_noise = open_noise; s.close_noise = close_noise; s.hang_blocks = (uint32_t)hang_blocks; });
+  f->set.apply(ch, [=](FmSetting &s) { s.open_noise = open_noise; s.close_noise = close_noise; s.hang_blocks = (uint32_t)hang_blocks; });
   return 0;
 }
 
@@ -149,26 +133,16 @@ int asdr_fm_update_device(asdr_fm_t *f, const int16_t *dI, const int16_t *dQ, lo
                           int n_blocks, void *stream_) {
   if (!f) return fail("null FM demodulator");
   if (f->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-  if (!dI || !dQ || !dOut) return fail("null device pointer");
-  if (n_blocks < 0 || n_blocks > 65535) return fail("n_blocks must be in 0..65535");
-  if (in_stride_blocks < n_blocks || out_stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
-  if (in_stride_blocks > (1L << 30) || out_stride_blocks > (1L << 30)) return fail("row stride too large");
-  if ((((uintptr_t)dI | (uintptr_t)dQ | (uintptr_t)dOut) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
+  if (stage_check_block_rows({{dI, dQ}, f->n, in_stride_blocks}, {{dOut}, f->n, out_stride_blocks}, n_blocks, "output span overlaps an input span") != 0)
+    return -1;
   if (n_blocks == 0) return 0;
-  const size_t in_bytes = ((size_t)(f->n - 1) * in_stride_blocks + n_blocks) * 256, out_bytes = ((size_t)(f->n - 1) * out_stride_blocks + n_blocks) * 256;
-  if (overlap((uintptr_t)dI, in_bytes, (uintptr_t)dOut, out_bytes) || overlap((uintptr_t)dQ, in_bytes, (uintptr_t)dOut, out_bytes))
-    return fail("output span overlaps an input span");
   hipStream_t stream = (hipStream_t)stream_;
-  if (stage_before_launch(*f, stream) != 0) return -1;
-  if (f->set_dirty) {
-    HIPCHK(hipMemcpyAsync(f->d_set, f->set.data(), f->set.size() * sizeof(FmSetting), hipMemcpyHostToDevice, stream));
-    f->set_dirty = false;
-  }
+  if (stage_before_launch(*f, stream) != 0 || f->set.push(stream) != 0) return -1;
   FmArgs a;
   a.i = dI; a.q = dQ; a.out = dOut;
   a.in_stride_blocks = in_stride_blocks; a.out_stride_blocks = out_stride_blocks;
   a.n_channels = f->n; a.n_blocks = n_blocks;
-  a.set = f->d_set; a.state = f->d_state;
+  a.set = f->set.dev; a.state = f->state.dev;
   if (asdr_launch_fm(&a, stream) != 0) return fail("FM kernel launch failed");
   if (stage_after_launch(*f, stream) != 0) return -1;
   f->blocks += n_blocks;
@@ -177,34 +151,24 @@ int asdr_fm_update_device(asdr_fm_t *f, const int16_t *dI, const int16_t *dQ, lo
 
 int asdr_fm_read_state(asdr_fm_t *f, asdr_fm_state_t *dst) {
   if (!f) return fail("null FM demodulator");
-  return stage_read_state(*f, dst, sizeof(asdr_fm_state_t), f->host_state.data(), f->d_state);
+  return f->state.read(*f, dst);
 }
 
 int asdr_fm_write_state(asdr_fm_t *f, const int *channels, int n, const asdr_fm_state_t *src) {
   if (!f) return fail("null FM demodulator");
-  return stage_write_state(*f, channels, n, src, sizeof(asdr_fm_state_t), f->host_state.data(), f->d_state, check_record);
+  return f->state.write(*f, channels, n, src, check_record);
 }
 
 int asdr_fm_clear(asdr_fm_t *f) {
   if (!f) return fail("null FM demodulator");
-  std::vector<asdr_fm_state_t> st(f->n);
-  if (asdr_fm_read_state(f, st.data()) != 0) return -1;
-  for (asdr_fm_state_t &s : st) s.openings = s.open_blocks = 0;
-  if (f->device == ASDR_NO_DEVICE) f->host_state = st;
-  else HIPCHK(hipMemcpy(f->d_state, st.data(), f->n * sizeof(asdr_fm_state_t), hipMemcpyHostToDevice));
+  if (f->state.rewrite(*f, [](asdr_fm_state_t &s) { s.openings = s.open_blocks = 0; }) != 0) return -1;
   f->blocks = 0;
   return 0;
 }
 
 int asdr_fm_reset(asdr_fm_t *f) {
   if (!f) return fail("null FM demodulator");
-  if (f->device == ASDR_NO_DEVICE) {
-    f->host_state.assign(f->n, asdr_fm_state_t{});
-  } else {
-    if (stage_quiesce(*f) != 0) return -1;
-    HIPCHK(hipMemsetAsync(f->d_state, 0, f->n * sizeof(asdr_fm_state_t), f->stream));
-    HIPCHK(hipStreamSynchronize(f->stream));
-  }
+  if (f->state.zero(*f) != 0) return -1;
   f->blocks = 0;
   return 0;
 }

@@ -13,12 +13,9 @@ static_assert(sizeof(asdr_gate_state_t) == 32, "asdr_gate_state_t is a 32-byte r
 static_assert(sizeof(GateSetting) == 24, "GateSetting is 24 bytes");
 
 struct asdr_gate : StageDev {
-  std::vector<GateSetting> set;
-  bool set_dirty = true;
-  std::vector<asdr_gate_state_t> host_state;   // ASDR_NO_DEVICE only
+  StageMirror<GateSetting> set;
+  StageRecords<asdr_gate_state_t> state;
   long long blocks = 0;
-  GateSetting *d_set = nullptr;
-  asdr_gate_state_t *d_state = nullptr;
   uint8_t *d_flag = nullptr;
   int32_t *d_tile = nullptr, *d_count = nullptr, *d_index = nullptr;
   void *d_scr = nullptr, *d_rows = nullptr;
@@ -33,7 +30,7 @@ int n_tiles(const asdr_gate_t *g) { return (g->n + ASDR_GATE_TILE - 1) / ASDR_GA
 GateArgs make_args(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks, int n_blocks, int16_t *dRows, int capacity_rows) {
   GateArgs a;
   a.audio = dAudio; a.stride_blocks = stride_blocks; a.n_channels = g->n; a.n_blocks = n_blocks;
-  a.set = g->d_set; a.state = g->d_state;
+  a.set = g->set.dev; a.state = g->state.dev;
   a.scr = (uint64_t *)g->d_scr;
   a.flag = g->d_flag; a.tile_count = g->d_tile; a.count = g->d_count; a.index = g->d_index;
   a.rows = dRows; a.capacity_rows = capacity_rows;
@@ -42,17 +39,11 @@ GateArgs make_args(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks, in
 
 int check_audio(const asdr_gate_t *g, const int16_t *dAudio, long stride_blocks, int n_blocks) {
   if (g->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-  if (!dAudio) return fail("null device pointer");
-  if (n_blocks < 0 || n_blocks > 65535) return fail("n_blocks must be in 0..65535");
-  if (stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
-  if (stride_blocks > (1L << 30)) return fail("row stride too large");
-  if (((uintptr_t)dAudio & 15u) != 0) return fail("device pointers must be 16-byte aligned");
-  return 0;
+  return stage_check_block_rows({{dAudio}, g->n, stride_blocks}, {}, n_blocks, nullptr);
 }
 
 // write_state's check of record k beyond its channel
-int check_record(int k, const void *rec) {
-  const asdr_gate_state_t &s = *(const asdr_gate_state_t *)rec;
+int check_record(int k, const asdr_gate_state_t &s) {
   if (s.open > 1) return fail("record " + std::to_string(k) + ": open must be 0 or 1");
   if (s.reserved != 0) return fail("record " + std::to_string(k) + ": reserved byte must be 0");
   return 0;
@@ -71,17 +62,17 @@ asdr_gate_t *asdr_gate_create(int n_channels, int device) {
   if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_gate *g = new asdr_gate;
   g->n = n_channels;
-  g->set.assign(n_channels, GateSetting{0, 0, 0, 0});
+  g->set.host.assign(n_channels, GateSetting{0, 0, 0, 0});
   if (device == ASDR_NO_DEVICE) {
-    g->host_state.assign(n_channels, asdr_gate_state_t{});
+    g->state.zero(*g);
     return g;
   }
   const size_t n = n_channels, tiles = n_tiles(g);
   if (stage_open(*g, device, "gate") != 0) { asdr_gate_destroy(g); return nullptr; }
-  if (hipMalloc(&g->d_set, n * sizeof(GateSetting)) != hipSuccess || hipMalloc(&g->d_state, n * sizeof(asdr_gate_state_t)) != hipSuccess ||
+  if (hipMalloc(&g->set.dev, n * sizeof(GateSetting)) != hipSuccess || hipMalloc(&g->state.dev, n * sizeof(asdr_gate_state_t)) != hipSuccess ||
       hipMalloc(&g->d_flag, n) != hipSuccess || hipMalloc(&g->d_tile, tiles * sizeof(int32_t)) != hipSuccess ||
       hipMalloc(&g->d_count, sizeof(int32_t)) != hipSuccess || hipMalloc(&g->d_index, n * sizeof(int32_t)) != hipSuccess ||
-      hipMemset(g->d_state, 0, n * sizeof(asdr_gate_state_t)) != hipSuccess || hipMemset(g->d_flag, 0, n) != hipSuccess ||
+      hipMemset(g->state.dev, 0, n * sizeof(asdr_gate_state_t)) != hipSuccess || hipMemset(g->d_flag, 0, n) != hipSuccess ||
       hipMemset(g->d_tile, 0, tiles * sizeof(int32_t)) != hipSuccess || hipMemset(g->d_count, 0, sizeof(int32_t)) != hipSuccess ||
       hipMemset(g->d_index, 0, n * sizeof(int32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
     fail("gate: device allocation failed");
@@ -93,27 +84,23 @@ asdr_gate_t *asdr_gate_create(int n_channels, int device) {
 
 void asdr_gate_destroy(asdr_gate_t *g) {
   if (!g) return;
-  stage_close(*g, {g->d_set, g->d_state, g->d_flag, g->d_tile, g->d_count, g->d_index, g->d_scr, g->d_rows});
+  stage_close(*g, {g->set.dev, g->state.dev, g->d_flag, g->d_tile, g->d_count, g->d_index, g->d_scr, g->d_rows});
   delete g;
 }
 
 int asdr_gate_n_channels(const asdr_gate_t *g) { return g ? g->n : fail("null gate"); }
 
 int asdr_gate_set_squelch(asdr_gate_t *g, int ch, uint64_t open_energy, uint64_t close_energy, int hang_blocks) {
-  if (!g) return fail("null gate");
-  if (ch != ASDR_ALL && (ch < 0 || ch >= g->n)) return fail("bad channel");
+  if (stage_check_channel(g, ch, true, "null gate") != 0) return -1;
   if (close_energy > open_energy) return fail("close_energy must not exceed open_energy");
   if (hang_blocks < 0 || hang_blocks > ASDR_GATE_MAX_HANG) return fail("hang_blocks must be in 0..65535");
   const GateSetting s{open_energy, close_energy, (uint32_t)hang_blocks, 0};
-  if (ch == ASDR_ALL) std::fill(g->set.begin(), g->set.end(), s);
-  else g->set[ch] = s;
-  g->set_dirty = true;
+  g->set.apply(ch, [=](GateSetting &v) { v = s; });
   return 0;
 }
 
 int asdr_gate_get_squelch(const asdr_gate_t *g, int ch, uint64_t *open_energy, uint64_t *close_energy, int *hang_blocks) {
-  if (!g) return fail("null gate");
-  if (ch < 0 || ch >= g->n) return fail("bad channel");
+  if (stage_check_channel(g, ch, false, "null gate") != 0) return -1;
   if (open_energy) *open_energy = g->set[ch].open_energy;
   if (close_energy) *close_energy = g->set[ch].close_energy;
   if (hang_blocks) *hang_blocks = (int)g->set[ch].hang_blocks;
@@ -129,18 +116,12 @@ int asdr_gate_update_device(asdr_gate_t *g, const int16_t *dAudio, long stride_b
   if (capacity_rows == 0) dRows = nullptr;
   if (n_blocks == 0) return 0;
   const int grid_rows = std::min(capacity_rows, g->n);
-  if (dRows) {
-    if (((uintptr_t)dRows & 15u) != 0) return fail("device pointers must be 16-byte aligned");
-    const size_t audio_bytes = ((size_t)(g->n - 1) * stride_blocks + n_blocks) * 256, rows_bytes = (size_t)grid_rows * n_blocks * 256;
-    if (overlap((uintptr_t)dAudio, audio_bytes, (uintptr_t)dRows, rows_bytes)) return fail("packet span overlaps the audio span");
-  }
+  // the packet: grid_rows dense rows; their pointer's alignment and the overlap are what this call can still refuse
+  if (dRows && stage_check_block_rows({{dAudio}, g->n, stride_blocks}, {{dRows}, grid_rows, n_blocks}, n_blocks, "packet span overlaps the audio span") != 0)
+    return -1;
   hipStream_t stream = (hipStream_t)stream_;
   if (n_blocks > 1 && stage_reserve(*g, &g->d_scr, &g->scr_cap, (size_t)g->n * n_blocks * sizeof(uint64_t)) != 0) return -1;
-  if (stage_before_launch(*g, stream) != 0) return -1;
-  if (g->set_dirty) {
-    HIPCHK(hipMemcpyAsync(g->d_set, g->set.data(), g->set.size() * sizeof(GateSetting), hipMemcpyHostToDevice, stream));
-    g->set_dirty = false;
-  }
+  if (stage_before_launch(*g, stream) != 0 || g->set.push(stream) != 0) return -1;
   const GateArgs a = make_args(g, dAudio, stride_blocks, n_blocks, dRows, grid_rows);
   if (asdr_launch_gate_pass(&a, stream) != 0) return fail("gate kernel launch failed");
   if (dRows && asdr_launch_gate_packet(&a, grid_rows, stream) != 0) return fail("gate packet kernel launch failed");
@@ -182,7 +163,7 @@ int asdr_gate_deliver(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks,
   HIPCHK(hipMemcpyAsync(host_index, g->d_index, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
   if (rows > 0) {
     if (stage_reserve(*g, &g->d_rows, &g->rows_cap, rows_bytes) != 0) return -1;
-    if (overlap((uintptr_t)dAudio, ((size_t)(g->n - 1) * stride_blocks + n_blocks) * 256, (uintptr_t)g->d_rows, rows_bytes))
+    if (overlap((uintptr_t)dAudio, BlockRows{{dAudio}, g->n, stride_blocks}.bytes(n_blocks), (uintptr_t)g->d_rows, rows_bytes))
       return fail("internal: packet buffer overlaps the audio span");
     const GateArgs a = make_args(g, dAudio, stride_blocks, n_blocks, (int16_t *)g->d_rows, rows);
     if (asdr_launch_gate_packet(&a, rows, g->stream) != 0) return fail("gate packet kernel launch failed");
@@ -194,39 +175,30 @@ int asdr_gate_deliver(asdr_gate_t *g, const int16_t *dAudio, long stride_blocks,
 
 int asdr_gate_read_state(asdr_gate_t *g, asdr_gate_state_t *dst) {
   if (!g) return fail("null gate");
-  return stage_read_state(*g, dst, sizeof(asdr_gate_state_t), g->host_state.data(), g->d_state);
+  return g->state.read(*g, dst);
 }
 
 int asdr_gate_write_state(asdr_gate_t *g, const int *channels, int n, const asdr_gate_state_t *src) {
   if (!g) return fail("null gate");
-  return stage_write_state(*g, channels, n, src, sizeof(asdr_gate_state_t), g->host_state.data(), g->d_state, check_record);
+  return g->state.write(*g, channels, n, src, check_record);
 }
 
 int asdr_gate_clear(asdr_gate_t *g) {
   if (!g) return fail("null gate");
-  std::vector<asdr_gate_state_t> st(g->n);
-  if (asdr_gate_read_state(g, st.data()) != 0) return -1;
-  for (asdr_gate_state_t &s : st) {
+  auto keep_squelch = [](asdr_gate_state_t &s) {
     asdr_gate_state_t z{};
     z.hang_left = s.hang_left; z.open = s.open;
     s = z;
-  }
-  if (g->device == ASDR_NO_DEVICE) g->host_state = st;
-  else HIPCHK(hipMemcpy(g->d_state, st.data(), g->n * sizeof(asdr_gate_state_t), hipMemcpyHostToDevice));
+  };
+  if (g->state.rewrite(*g, keep_squelch) != 0) return -1;
   g->blocks = 0;
   return 0;
 }
 
 int asdr_gate_reset(asdr_gate_t *g) {
   if (!g) return fail("null gate");
-  if (g->device == ASDR_NO_DEVICE) {
-    g->host_state.assign(g->n, asdr_gate_state_t{});
-  } else {
-    if (stage_quiesce(*g) != 0) return -1;
-    HIPCHK(hipMemsetAsync(g->d_state, 0, g->n * sizeof(asdr_gate_state_t), g->stream));
-    HIPCHK(hipMemsetAsync(g->d_count, 0, sizeof(int32_t), g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-  }
+  if (g->state.zero(*g) != 0) return -1;
+  if (g->device != ASDR_NO_DEVICE && stage_zero(*g, g->d_count, sizeof(int32_t)) != 0) return -1;
   g->blocks = 0;
   return 0;
 }

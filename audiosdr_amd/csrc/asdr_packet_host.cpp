@@ -15,12 +15,10 @@ static_assert(sizeof(PacketRing) == 16, "PacketRing is 16 bytes");
 
 struct asdr_packet : StageDev {
   int ring = 0;
-  std::vector<uint32_t> boost;
-  bool boost_dirty = true;
-  std::vector<asdr_packet_state_t> host_state;   // ASDR_NO_DEVICE only
+  StageMirror<uint32_t> boost;
+  StageRecords<asdr_packet_state_t> state;
   long long blocks = 0;
-  uint32_t *d_boost = nullptr, *d_tile_count = nullptr, *d_index = nullptr, *d_count = nullptr;
-  asdr_packet_state_t *d_state = nullptr;
+  uint32_t *d_tile_count = nullptr, *d_index = nullptr, *d_count = nullptr;
   PacketRing *d_rings = nullptr;
   asdr_packet_frame_t *d_slots = nullptr;
   void *d_frames = nullptr;                      // deliver's, grown on demand
@@ -29,7 +27,6 @@ struct asdr_packet : StageDev {
 
 namespace {
 const char *kNoDevice = "control-plane-only packet decoder (ASDR_NO_DEVICE): the signal path and the delivery need a HIP device";
-const size_t kChunk = 4096;   // records per transfer of reset
 
 asdr_packet_state_t creation_record() {
   asdr_packet_state_t s{};
@@ -46,22 +43,12 @@ uint16_t crc_of(const uint8_t *bytes, size_t n) {
 
 int check_handle(const asdr_packet_t *t) { return t ? 0 : fail("null packet decoder"); }
 
-int check_channel(const asdr_packet_t *t, int ch, bool all_allowed) {
-  if (check_handle(t) != 0) return -1;
-  if (all_allowed && ch == ASDR_ALL) return 0;
-  return ch < 0 || ch >= t->n ? fail("bad channel") : 0;
-}
+int check_channel(const asdr_packet_t *t, int ch, bool all_allowed) { return stage_check_channel(t, ch, all_allowed, "null packet decoder"); }
 
 // the creation record into every channel (crc = 0xFFFF: records are written, not memset) and empty rings
 int creation_state(asdr_packet_t *t) {
-  if (t->device == ASDR_NO_DEVICE) {
-    t->host_state.assign(t->n, creation_record());
-    return 0;
-  }
-  if (stage_quiesce(*t) != 0) return -1;
-  const std::vector<asdr_packet_state_t> buf(std::min((size_t)t->n, kChunk), creation_record());
-  for (size_t c = 0; c < (size_t)t->n; c += kChunk)
-    HIPCHK(hipMemcpy(t->d_state + c, buf.data(), std::min(kChunk, (size_t)t->n - c) * sizeof(asdr_packet_state_t), hipMemcpyHostToDevice));
+  if (t->state.fill(*t, creation_record()) != 0) return -1;
+  if (t->device == ASDR_NO_DEVICE) return 0;
   HIPCHK(hipMemsetAsync(t->d_rings, 0, (size_t)t->n * sizeof(PacketRing), t->stream));
   HIPCHK(hipMemsetAsync(t->d_slots, 0, (size_t)t->n * t->ring * sizeof(asdr_packet_frame_t), t->stream));
   HIPCHK(hipStreamSynchronize(t->stream));   // the fills are done on return: a call on any stream may follow
@@ -123,14 +110,14 @@ asdr_packet_t *asdr_packet_create(int n_channels, int ring, int device) {
   asdr_packet *t = new asdr_packet;
   t->n = n_channels;
   t->ring = ring;
-  t->boost.assign(n_channels, 256u);
+  t->boost.host.assign(n_channels, 256u);
   if (device == ASDR_NO_DEVICE) {
-    t->host_state.assign(n_channels, creation_record());
+    creation_state(t);
     return t;
   }
   const size_t n = n_channels, n_tiles = (n + ASDR_PACKET_TILE - 1) / ASDR_PACKET_TILE;
   if (stage_open(*t, device, "packet") != 0) { asdr_packet_destroy(t); return nullptr; }
-  if (hipMalloc(&t->d_boost, n * sizeof(uint32_t)) != hipSuccess || hipMalloc(&t->d_state, n * sizeof(asdr_packet_state_t)) != hipSuccess ||
+  if (hipMalloc(&t->boost.dev, n * sizeof(uint32_t)) != hipSuccess || hipMalloc(&t->state.dev, n * sizeof(asdr_packet_state_t)) != hipSuccess ||
       hipMalloc(&t->d_rings, n * sizeof(PacketRing)) != hipSuccess || hipMalloc(&t->d_slots, n * ring * sizeof(asdr_packet_frame_t)) != hipSuccess ||
       hipMalloc(&t->d_tile_count, n_tiles * sizeof(uint32_t)) != hipSuccess || hipMalloc(&t->d_index, n * ring * sizeof(uint32_t)) != hipSuccess ||
       hipMalloc(&t->d_count, 16) != hipSuccess || creation_state(t) != 0 || hipDeviceSynchronize() != hipSuccess) {
@@ -143,7 +130,7 @@ asdr_packet_t *asdr_packet_create(int n_channels, int ring, int device) {
 
 void asdr_packet_destroy(asdr_packet_t *t) {
   if (!t) return;
-  stage_close(*t, {t->d_boost, t->d_state, t->d_rings, t->d_slots, t->d_tile_count, t->d_index, t->d_count, t->d_frames});
+  stage_close(*t, {t->boost.dev, t->state.dev, t->d_rings, t->d_slots, t->d_tile_count, t->d_index, t->d_count, t->d_frames});
   delete t;
 }
 
@@ -152,9 +139,7 @@ int asdr_packet_n_channels(const asdr_packet_t *t) { return t ? t->n : fail("nul
 int asdr_packet_set_space_boost(asdr_packet_t *t, int ch, uint32_t space_boost) {
   if (check_channel(t, ch, true) != 0) return -1;
   if (space_boost < ASDR_PACKET_MIN_BOOST || space_boost > ASDR_PACKET_MAX_BOOST) return fail("space_boost must be in 64..4096");
-  if (ch == ASDR_ALL) std::fill(t->boost.begin(), t->boost.end(), space_boost);
-  else t->boost[ch] = space_boost;
-  t->boost_dirty = true;
+  t->boost.apply(ch, [=](uint32_t &b) { b = space_boost; });
   return 0;
 }
 
@@ -167,23 +152,15 @@ int asdr_packet_get_space_boost(const asdr_packet_t *t, int ch, uint32_t *space_
 int asdr_packet_update_device(asdr_packet_t *t, const int16_t *dIn, long in_stride_blocks, int n_blocks, void *stream_) {
   if (check_handle(t) != 0) return -1;
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-  if (!dIn) return fail("null device pointer");
-  if (n_blocks < 0 || n_blocks > 65535) return fail("n_blocks must be in 0..65535");
-  if (in_stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
-  if (in_stride_blocks > (1L << 30)) return fail("row stride too large");
-  if (((uintptr_t)dIn & 15u) != 0) return fail("device pointers must be 16-byte aligned");
+  if (stage_check_block_rows({{dIn}, t->n, in_stride_blocks}, {}, n_blocks, nullptr) != 0) return -1;
   if (n_blocks == 0) return 0;
   hipStream_t stream = (hipStream_t)stream_;
-  if (stage_before_launch(*t, stream) != 0) return -1;
-  if (t->boost_dirty) {
-    HIPCHK(hipMemcpyAsync(t->d_boost, t->boost.data(), t->boost.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    t->boost_dirty = false;
-  }
+  if (stage_before_launch(*t, stream) != 0 || t->boost.push(stream) != 0) return -1;
   PacketArgs a;
   a.in = dIn; a.in_stride_blocks = in_stride_blocks;
   a.n_channels = t->n; a.n_blocks = n_blocks;
   a.ring = (uint32_t)t->ring; a.block0 = (uint32_t)t->blocks;
-  a.boost = t->d_boost; a.state = t->d_state; a.rings = t->d_rings; a.slots = t->d_slots;
+  a.boost = t->boost.dev; a.state = t->state.dev; a.rings = t->d_rings; a.slots = t->d_slots;
   if (asdr_launch_packet(&a, stream) != 0) return fail("packet kernel launch failed");
   if (stage_after_launch(*t, stream) != 0) return -1;
   t->blocks += n_blocks;
@@ -235,13 +212,12 @@ int asdr_packet_ring_state(asdr_packet_t *t, uint32_t *pending, uint32_t *lost) 
 
 int asdr_packet_read_state(asdr_packet_t *t, asdr_packet_state_t *dst) {
   if (check_handle(t) != 0) return -1;
-  return stage_read_state(*t, dst, sizeof(asdr_packet_state_t), t->host_state.data(), t->d_state);
+  return t->state.read(*t, dst);
 }
 
 int asdr_packet_write_state(asdr_packet_t *t, const int *channels, int n, const asdr_packet_state_t *src) {
   if (check_handle(t) != 0) return -1;
-  auto check_record = [](int k, const void *rec) {
-    const asdr_packet_state_t &s = *(const asdr_packet_state_t *)rec;
+  auto check_record = [](int k, const asdr_packet_state_t &s) {
     const std::string r = "record " + std::to_string(k);
     if (s.clk >= ASDR_PACKET_CLOCK) return fail(r + ": clk must be below 147");
     if (s.len > ASDR_PACKET_MAX_LEN) return fail(r + ": len must be at most 332");
@@ -253,16 +229,16 @@ int asdr_packet_write_state(asdr_packet_t *t, const int *channels, int n, const 
       if (v != 0) return fail(r + ": reserved fields must be 0");
     return 0;
   };
-  return stage_write_state(*t, channels, n, src, sizeof(asdr_packet_state_t), t->host_state.data(), t->d_state, check_record);
+  return t->state.write(*t, channels, n, src, check_record);
 }
 
 int asdr_packet_clear(asdr_packet_t *t) {
   if (check_handle(t) != 0) return -1;
   if (t->device == ASDR_NO_DEVICE) {
-    for (asdr_packet_state_t &s : t->host_state) s.bits = s.edges = s.flags = s.crc_errors = s.aborts = 0;
+    for (asdr_packet_state_t &s : t->state.host) s.bits = s.edges = s.flags = s.crc_errors = s.aborts = 0;
   } else {   // one launch zeroes the five counters and lost of every channel: all of it or, if the launch fails, none
     if (stage_quiesce(*t) != 0) return -1;
-    if (asdr_launch_packet_clear(t->d_state, t->d_rings, t->n, t->stream) != 0) return fail("packet clear launch failed");
+    if (asdr_launch_packet_clear(t->state.dev, t->d_rings, t->n, t->stream) != 0) return fail("packet clear launch failed");
     HIPCHK(hipStreamSynchronize(t->stream));
   }
   t->blocks = 0;

@@ -16,8 +16,7 @@ struct asdr_resampler : StageDev {
   int up = 1, down = 1, K = 1, shift = 15;
   std::vector<int16_t> taps;                   // h[k * up + phi]
   long long pos = 0;                           // N
-  std::vector<int16_t> host_state;             // ASDR_NO_DEVICE only
-  CarryPair carry;
+  CarryPair carry;                             // the state records
   uint32_t *d_taps = nullptr;
 };
 
@@ -121,8 +120,9 @@ asdr_resampler_t *make(int n_channels, int up, int down, int K, const int16_t *t
   asdr_resampler *r = new asdr_resampler;
   r->n = n_channels; r->up = up; r->down = down; r->K = K; r->shift = shift;
   r->taps.assign(taps, taps + (size_t)up * K);
+  r->carry.samples = kRecord;
   if (device == ASDR_NO_DEVICE) {
-    r->host_state.assign((size_t)n_channels * kRecord, 0);
+    r->carry.reset(*r);
     return r;
   }
   const size_t rec = (size_t)n_channels * kRecord * sizeof(int16_t);
@@ -289,18 +289,17 @@ long asdr_resampler_update_device(asdr_resampler_t *r, const int16_t *dAudio, lo
 
 int asdr_resampler_read_state(asdr_resampler_t *r, int16_t *dst) {
   if (!r) return fail("null resampler");
-  return stage_read_state(*r, dst, kRecord * sizeof(int16_t), r->host_state.data(), r->carry.current());
+  return r->carry.read(*r, dst);
 }
 
 int asdr_resampler_write_state(asdr_resampler_t *r, const int *channels, int n, const int16_t *src) {
   if (!r) return fail("null resampler");
-  return stage_write_state(*r, channels, n, src, kRecord * sizeof(int16_t), r->host_state.data(), r->carry.current());
+  return r->carry.write(*r, channels, n, src);
 }
 
 int asdr_resampler_reset(asdr_resampler_t *r) {
   if (!r) return fail("null resampler");
-  if (r->device == ASDR_NO_DEVICE) std::fill(r->host_state.begin(), r->host_state.end(), (int16_t)0);
-  else if (r->carry.reset(*r, (size_t)r->n * kRecord * sizeof(int16_t)) != 0) return -1;
+  if (r->carry.reset(*r) != 0) return -1;
   r->pos = 0;
   return 0;
 }

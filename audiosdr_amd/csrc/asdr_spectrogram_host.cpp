@@ -14,8 +14,7 @@ struct asdr_spectrogram : StageDev {
   int N = 0, log2n = 0, hop = 0, k0 = 0, bins = 0, window_kind = ASDR_SPECTROGRAM_RECT, kind = ASDR_SPECTROGRAM_POWER;
   std::vector<float> window;                   // [N]
   long long pos = 0;                           // T
-  std::vector<int16_t> host_state;             // ASDR_NO_DEVICE only
-  CarryPair carry;
+  CarryPair carry;                             // the state records
   float *d_window = nullptr, *d_tw = nullptr;
 };
 
@@ -69,8 +68,9 @@ asdr_spectrogram_t *asdr_spectrogram_create(int n_channels, int n_fft, int hop, 
     const double pi = 3.14159265358979323846;
     for (int i = 0; i < n_fft; i++) s->window[i] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * i / n_fft));
   }
+  s->carry.samples = n_fft;
   if (device == ASDR_NO_DEVICE) {
-    s->host_state.assign((size_t)n_channels * n_fft, 0);
+    s->carry.reset(*s);
     return s;
   }
   const size_t rec = (size_t)n_channels * n_fft * sizeof(int16_t);
@@ -191,18 +191,17 @@ long asdr_spectrogram_update_device(asdr_spectrogram_t *s, const int16_t *dAudio
 
 int asdr_spectrogram_read_state(asdr_spectrogram_t *s, int16_t *dst) {
   if (!s) return fail(kNull);
-  return stage_read_state(*s, dst, s->N * sizeof(int16_t), s->host_state.data(), s->carry.current());
+  return s->carry.read(*s, dst);
 }
 
 int asdr_spectrogram_write_state(asdr_spectrogram_t *s, const int *channels, int n, const int16_t *src) {
   if (!s) return fail(kNull);
-  return stage_write_state(*s, channels, n, src, s->N * sizeof(int16_t), s->host_state.data(), s->carry.current());
+  return s->carry.write(*s, channels, n, src);
 }
 
 int asdr_spectrogram_reset(asdr_spectrogram_t *s) {
   if (!s) return fail(kNull);
-  if (s->device == ASDR_NO_DEVICE) std::fill(s->host_state.begin(), s->host_state.end(), (int16_t)0);
-  else if (s->carry.reset(*s, (size_t)s->n * s->N * sizeof(int16_t)) != 0) return -1;
+  if (s->carry.reset(*s) != 0) return -1;
   s->pos = 0;
   return 0;
 }

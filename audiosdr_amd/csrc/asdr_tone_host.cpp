@@ -12,23 +12,19 @@ static_assert(sizeof(asdr_tone_state_t) == 704, "asdr_tone_state_t is a 704-byte
 static_assert(sizeof(ToneSetting) == 16, "ToneSetting is 16 bytes");
 
 struct asdr_tone : StageDev {
-  std::vector<ToneSetting> set;
-  bool set_dirty = true, steps_dirty = true;
+  StageMirror<ToneSetting> set;
+  StageMirror<uint32_t> steps;                 // ASDR_TONE_MAX_TONES phase steps, 0 from n_tones on
   double hz[ASDR_TONE_MAX_TONES] = {};
-  uint32_t steps[ASDR_TONE_MAX_TONES] = {};    // 0 from n_tones on
   int n_tones = 0, window = 64, dominance = 64, sections = 0;
   int32_t coef[ASDR_TONE_MAX_SECTIONS][5] = {};
-  std::vector<asdr_tone_state_t> host_state;   // ASDR_NO_DEVICE only
+  StageRecords<asdr_tone_state_t> state;
   long long blocks = 0;
-  ToneSetting *d_set = nullptr;
-  uint32_t *d_steps = nullptr, *d_table = nullptr;
-  asdr_tone_state_t *d_state = nullptr;
+  uint32_t *d_table = nullptr;
 };
 
 namespace {
 const char *kNoDevice = "control-plane-only tone squelch (ASDR_NO_DEVICE): the signal path needs a HIP device";
 const double kFs = 44100.0, kPi = 3.14159265358979323846;
-const size_t kChunk = 4096;   // records per transfer of reset / the window restart
 
 asdr_tone_state_t creation_record() {
   asdr_tone_state_t s{};
@@ -38,18 +34,7 @@ asdr_tone_state_t creation_record() {
 
 int check_handle(const asdr_tone_t *t) { return t ? 0 : fail("null tone squelch"); }
 
-int check_channel(const asdr_tone_t *t, int ch, bool all_allowed) {
-  if (check_handle(t) != 0) return -1;
-  if (all_allowed && ch == ASDR_ALL) return 0;
-  return ch < 0 || ch >= t->n ? fail("bad channel") : 0;
-}
-
-template <class F>
-void apply(asdr_tone_t *t, int ch, F change) {
-  if (ch == ASDR_ALL) for (ToneSetting &s : t->set) change(s);
-  else change(t->set[ch]);
-  t->set_dirty = true;
-}
+int check_channel(const asdr_tone_t *t, int ch, bool all_allowed) { return stage_check_channel(t, ch, all_allowed, "null tone squelch"); }
 
 // the phase steps of a table, or -1 with the reason
 int steps_of(const double *hz, int n, uint32_t *steps) {
@@ -63,40 +48,9 @@ int steps_of(const double *hz, int n, uint32_t *steps) {
   return 0;
 }
 
-// every record through `change`, in chunks, behind the handle's work
-template <class F>
-int rewrite_records(asdr_tone_t *t, F change) {
-  if (t->device == ASDR_NO_DEVICE) {
-    for (asdr_tone_state_t &s : t->host_state) change(s);
-    return 0;
-  }
-  if (stage_quiesce(*t) != 0) return -1;
-  std::vector<asdr_tone_state_t> buf(std::min((size_t)t->n, kChunk));
-  for (size_t c = 0; c < (size_t)t->n; c += kChunk) {
-    const size_t m = std::min(kChunk, (size_t)t->n - c);
-    HIPCHK(hipMemcpy(buf.data(), t->d_state + c, m * sizeof(asdr_tone_state_t), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < m; k++) change(buf[k]);
-    HIPCHK(hipMemcpy(t->d_state + c, buf.data(), m * sizeof(asdr_tone_state_t), hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
-// the creation record into every channel
-int creation_state(asdr_tone_t *t) {
-  if (t->device == ASDR_NO_DEVICE) {
-    t->host_state.assign(t->n, creation_record());
-    return 0;
-  }
-  if (stage_quiesce(*t) != 0) return -1;
-  const std::vector<asdr_tone_state_t> buf(std::min((size_t)t->n, kChunk), creation_record());
-  for (size_t c = 0; c < (size_t)t->n; c += kChunk)
-    HIPCHK(hipMemcpy(t->d_state + c, buf.data(), std::min(kChunk, (size_t)t->n - c) * sizeof(asdr_tone_state_t), hipMemcpyHostToDevice));
-  return 0;
-}
-
 // a new table or window: every channel's window starts again
 int restart_windows(asdr_tone_t *t) {
-  return rewrite_records(t, [](asdr_tone_state_t &s) { std::fill(&s.acc[0][0], &s.acc[0][0] + 2 * ASDR_TONE_MAX_TONES, 0); s.window_block = 0; });
+  return t->state.rewrite(*t, [](asdr_tone_state_t &s) { std::fill(&s.acc[0][0], &s.acc[0][0] + 2 * ASDR_TONE_MAX_TONES, 0); s.window_block = 0; });
 }
 }  // namespace
 
@@ -130,12 +84,13 @@ asdr_tone_t *asdr_tone_create(int n_channels, int device) {
   if (stage_check_create(n_channels) != 0) return nullptr;
   asdr_tone *t = new asdr_tone;
   t->n = n_channels;
-  t->set.assign(n_channels, ToneSetting{0, ASDR_TONE_PASS, 0});
+  t->set.host.assign(n_channels, ToneSetting{0, ASDR_TONE_PASS, 0});
+  t->steps.host.assign(ASDR_TONE_MAX_TONES, 0u);
   t->n_tones = ASDR_CTCSS_COUNT;
   std::copy(ASDR_CTCSS_TONES, ASDR_CTCSS_TONES + ASDR_CTCSS_COUNT, t->hz);
-  steps_of(t->hz, t->n_tones, t->steps);
+  steps_of(t->hz, t->n_tones, t->steps.host.data());
   if (device == ASDR_NO_DEVICE) {
-    t->host_state.assign(n_channels, creation_record());
+    t->state.fill(*t, creation_record());
     return t;
   }
   const size_t n = n_channels;
@@ -144,10 +99,10 @@ asdr_tone_t *asdr_tone_create(int n_channels, int device) {
   int C[ASDR_TONE_TABLE];
   for (int j = 0; j < ASDR_TONE_TABLE; j++) C[j] = (int)std::floor(16384.0 * std::cos(2.0 * kPi * j / ASDR_TONE_TABLE) + 0.5);
   for (int j = 0; j < ASDR_TONE_TABLE; j++) table[j] = ((uint32_t)C[j] & 0xFFFFu) | ((uint32_t)C[(j - 256) & (ASDR_TONE_TABLE - 1)] << 16);
-  if (hipMalloc(&t->d_set, n * sizeof(ToneSetting)) != hipSuccess || hipMalloc(&t->d_state, n * sizeof(asdr_tone_state_t)) != hipSuccess ||
-      hipMalloc(&t->d_steps, sizeof(t->steps)) != hipSuccess || hipMalloc(&t->d_table, ASDR_TONE_TABLE * sizeof(uint32_t)) != hipSuccess ||
-      hipMemcpy(t->d_table, table.data(), ASDR_TONE_TABLE * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess || creation_state(t) != 0 ||
-      hipDeviceSynchronize() != hipSuccess) {
+  if (hipMalloc(&t->set.dev, n * sizeof(ToneSetting)) != hipSuccess || hipMalloc(&t->state.dev, n * sizeof(asdr_tone_state_t)) != hipSuccess ||
+      hipMalloc(&t->steps.dev, ASDR_TONE_MAX_TONES * sizeof(uint32_t)) != hipSuccess || hipMalloc(&t->d_table, ASDR_TONE_TABLE * sizeof(uint32_t)) != hipSuccess ||
+      hipMemcpy(t->d_table, table.data(), ASDR_TONE_TABLE * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+      t->state.fill(*t, creation_record()) != 0 || hipDeviceSynchronize() != hipSuccess) {
     fail("tone: device allocation failed");
     asdr_tone_destroy(t);
     return nullptr;
@@ -157,7 +112,7 @@ asdr_tone_t *asdr_tone_create(int n_channels, int device) {
 
 void asdr_tone_destroy(asdr_tone_t *t) {
   if (!t) return;
-  stage_close(*t, {t->d_set, t->d_state, t->d_steps, t->d_table});
+  stage_close(*t, {t->set.dev, t->state.dev, t->steps.dev, t->d_table});
   delete t;
 }
 
@@ -170,16 +125,16 @@ int asdr_tone_set_tones(asdr_tone_t *t, const double *hz, int n_tones) {
   if (restart_windows(t) != 0) return -1;
   std::fill(t->hz, t->hz + ASDR_TONE_MAX_TONES, 0.0);
   std::copy(hz, hz + n_tones, t->hz);
-  std::copy(steps, steps + ASDR_TONE_MAX_TONES, t->steps);
+  std::copy(steps, steps + ASDR_TONE_MAX_TONES, t->steps.host.begin());
   t->n_tones = n_tones;
-  t->steps_dirty = true;
+  t->steps.dirty = true;
   return 0;
 }
 
 int asdr_tone_get_tones(const asdr_tone_t *t, double *hz, uint32_t *steps) {
   if (check_handle(t) != 0) return -1;
   if (hz) std::copy(t->hz, t->hz + t->n_tones, hz);
-  if (steps) std::copy(t->steps, t->steps + t->n_tones, steps);
+  if (steps) std::copy(t->steps.host.begin(), t->steps.host.begin() + t->n_tones, steps);
   return t->n_tones;
 }
 
@@ -221,7 +176,7 @@ int asdr_tone_get_highpass(const asdr_tone_t *t, int32_t *coefficients) {
 int asdr_tone_set_want(asdr_tone_t *t, int ch, int want) {
   if (check_channel(t, ch, true) != 0) return -1;
   if (want < ASDR_TONE_PASS || want >= t->n_tones) return fail("want must be ASDR_TONE_PASS, ASDR_TONE_ANY or a tone of the table");
-  apply(t, ch, [=](ToneSetting &s) { s.want = want; });
+  t->set.apply(ch, [=](ToneSetting &s) { s.want = want; });
   return 0;
 }
 
@@ -233,7 +188,7 @@ int asdr_tone_get_want(const asdr_tone_t *t, int ch, int *want) {
 
 int asdr_tone_set_min_power(asdr_tone_t *t, int ch, uint64_t min_power) {
   if (check_channel(t, ch, true) != 0) return -1;
-  apply(t, ch, [=](ToneSetting &s) { s.min_power = min_power; });
+  t->set.apply(ch, [=](ToneSetting &s) { s.min_power = min_power; });
   return 0;
 }
 
@@ -246,7 +201,7 @@ int asdr_tone_get_min_power(const asdr_tone_t *t, int ch, uint64_t *min_power) {
 int asdr_tone_set_hang(asdr_tone_t *t, int ch, int hang_windows) {
   if (check_channel(t, ch, true) != 0) return -1;
   if (hang_windows < 0 || hang_windows > ASDR_TONE_MAX_HANG) return fail("hang_windows must be in 0..255");
-  apply(t, ch, [=](ToneSetting &s) { s.hang_windows = (uint32_t)hang_windows; });
+  t->set.apply(ch, [=](ToneSetting &s) { s.hang_windows = (uint32_t)hang_windows; });
   return 0;
 }
 
@@ -260,31 +215,18 @@ int asdr_tone_update_device(asdr_tone_t *t, const int16_t *dIn, long in_stride_b
                             void *stream_) {
   if (check_handle(t) != 0) return -1;
   if (t->device == ASDR_NO_DEVICE) return fail(kNoDevice);
-  if (!dIn || !dOut) return fail("null device pointer");
-  if (n_blocks < 0 || n_blocks > 65535) return fail("n_blocks must be in 0..65535");
-  if (in_stride_blocks < n_blocks || out_stride_blocks < n_blocks) return fail("row stride shorter than n_blocks");
-  if (in_stride_blocks > (1L << 30) || out_stride_blocks > (1L << 30)) return fail("row stride too large");
-  if ((((uintptr_t)dIn | (uintptr_t)dOut) & 15u) != 0) return fail("device pointers must be 16-byte aligned");
+  if (stage_check_block_rows({{dIn}, t->n, in_stride_blocks}, {{dOut}, t->n, out_stride_blocks}, n_blocks, "output span overlaps the input span") != 0)
+    return -1;
   if (n_blocks == 0) return 0;
-  const size_t in_bytes = ((size_t)(t->n - 1) * in_stride_blocks + n_blocks) * 256, out_bytes = ((size_t)(t->n - 1) * out_stride_blocks + n_blocks) * 256;
-  if (overlap((uintptr_t)dIn, in_bytes, (uintptr_t)dOut, out_bytes)) return fail("output span overlaps the input span");
   hipStream_t stream = (hipStream_t)stream_;
-  if (stage_before_launch(*t, stream) != 0) return -1;
-  if (t->set_dirty) {
-    HIPCHK(hipMemcpyAsync(t->d_set, t->set.data(), t->set.size() * sizeof(ToneSetting), hipMemcpyHostToDevice, stream));
-    t->set_dirty = false;
-  }
-  if (t->steps_dirty) {
-    HIPCHK(hipMemcpyAsync(t->d_steps, t->steps, sizeof(t->steps), hipMemcpyHostToDevice, stream));
-    t->steps_dirty = false;
-  }
+  if (stage_before_launch(*t, stream) != 0 || t->set.push(stream) != 0 || t->steps.push(stream) != 0) return -1;
   ToneArgs a;
   a.in = dIn; a.out = dOut;
   a.in_stride_blocks = in_stride_blocks; a.out_stride_blocks = out_stride_blocks;
   a.n_channels = t->n; a.n_blocks = n_blocks;
   a.n_tones = t->n_tones; a.window = t->window; a.dominance = t->dominance; a.sections = t->sections;
   std::copy(&t->coef[0][0], &t->coef[0][0] + 5 * ASDR_TONE_MAX_SECTIONS, &a.coef[0][0]);
-  a.steps = t->d_steps; a.table = t->d_table; a.set = t->d_set; a.state = t->d_state;
+  a.steps = t->steps.dev; a.table = t->d_table; a.set = t->set.dev; a.state = t->state.dev;
   if (asdr_launch_tone(&a, stream) != 0) return fail("tone kernel launch failed");
   if (stage_after_launch(*t, stream) != 0) return -1;
   t->blocks += n_blocks;
@@ -293,14 +235,13 @@ int asdr_tone_update_device(asdr_tone_t *t, const int16_t *dIn, long in_stride_b
 
 int asdr_tone_read_state(asdr_tone_t *t, asdr_tone_state_t *dst) {
   if (check_handle(t) != 0) return -1;
-  return stage_read_state(*t, dst, sizeof(asdr_tone_state_t), t->host_state.data(), t->d_state);
+  return t->state.read(*t, dst);
 }
 
 int asdr_tone_write_state(asdr_tone_t *t, const int *channels, int n, const asdr_tone_state_t *src) {
   if (check_handle(t) != 0) return -1;
   const int window = t->window, n_tones = t->n_tones;
-  auto check_record = [=](int k, const void *rec) {
-    const asdr_tone_state_t &s = *(const asdr_tone_state_t *)rec;
+  auto check_record = [=](int k, const asdr_tone_state_t &s) {
     const std::string r = "record " + std::to_string(k);
     if (s.open > 1) return fail(r + ": open must be 0 or 1");
     if (s.window_block >= window) return fail(r + ": window_block must be below the window");
@@ -311,19 +252,19 @@ int asdr_tone_write_state(asdr_tone_t *t, const int *channels, int n, const asdr
       if (s.acc[j][0] != 0 || s.acc[j][1] != 0) return fail(r + ": acc must be 0 from n_tones on");
     return 0;
   };
-  return stage_write_state(*t, channels, n, src, sizeof(asdr_tone_state_t), t->host_state.data(), t->d_state, check_record);
+  return t->state.write(*t, channels, n, src, check_record);
 }
 
 int asdr_tone_clear(asdr_tone_t *t) {
   if (check_handle(t) != 0) return -1;
-  if (rewrite_records(t, [](asdr_tone_state_t &s) { s.windows = s.matches = s.openings = s.open_blocks = 0; }) != 0) return -1;
+  if (t->state.rewrite(*t, [](asdr_tone_state_t &s) { s.windows = s.matches = s.openings = s.open_blocks = 0; }) != 0) return -1;
   t->blocks = 0;
   return 0;
 }
 
 int asdr_tone_reset(asdr_tone_t *t) {
   if (check_handle(t) != 0) return -1;
-  if (creation_state(t) != 0) return -1;
+  if (t->state.fill(*t, creation_record()) != 0) return -1;
   t->blocks = 0;
   return 0;
 }

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _c_int, _stride, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 DCS_EXPORTS = ["asdr_dcs_create", "asdr_dcs_destroy", "asdr_dcs_n_channels", "asdr_dcs_word", "asdr_dcs_find", "asdr_dcs_set_codes",
@@ -47,13 +47,6 @@ def _lib():
     return typed_library("asdr_dcs_", _API)
 
 
-def _c_int(v, what):
-    v = int(v)
-    if not -2**31 <= v < 2**31:
-        raise AsdrError(what)
-    return v
-
-
 def dcs_word(code):
     """asdr_dcs_word: the 23-bit word of a code (three octal digits, as an int: 0o023), parity << 12 | 0x800 | code."""
     L = _lib()
@@ -64,10 +57,11 @@ def dcs_word(code):
     return w
 
 
-class DcsSquelch(ResetStage):
+class DcsSquelch(RecordStage):
     """DCS squelches of n_channels audio rows (include/asdr_dcs.h).  device = NO_DEVICE (-1) gives the control plane and the state
     records only."""
     _prefix = "asdr_dcs_"
+    _state_dtype = DCS_STATE_DTYPE
 
     def __init__(self, n_channels, device=0):
         self._L = _lib()
@@ -145,29 +139,12 @@ class DcsSquelch(ResetStage):
         """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle as int).  in_ptr: int16 rows
         [n_channels][in_stride_blocks][128]; out_ptr: int16 rows [n_channels][out_stride_blocks][128]; the strides default to
         n_blocks."""
-        si = int(n_blocks) if in_stride_blocks is None else int(in_stride_blocks)
-        so = int(n_blocks) if out_stride_blocks is None else int(out_stride_blocks)
+        si = _stride(in_stride_blocks, n_blocks)
+        so = _stride(out_stride_blocks, n_blocks)
         self._chk(self._L.asdr_dcs_update_device(self._h, C.c_void_p(in_ptr), si, C.c_void_p(out_ptr), so, int(n_blocks),
                                                  C.c_void_p(stream or None)))
 
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of DCS_STATE_DTYPE; waits for the handle's work."""
-        st = np.zeros(self.n_channels, dtype=DCS_STATE_DTYPE)
-        self._chk(self._L.asdr_dcs_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes DCS_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=DCS_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_dcs_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def clear(self):
-        self._call("clear")
-
-    def blocks(self):
-        return int(self._L.asdr_dcs_blocks(self._h))
-
+    # state (read_state, write_state, clear, blocks: RecordStage)
     def decoded_codes(self):
         """The table code of every channel's `detected`, int32 [n_channels]; -1 where no code is detected."""
         codes, _ = self.get_codes()

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _c_int, _stride, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 FM_EXPORTS = ["asdr_fm_create", "asdr_fm_destroy", "asdr_fm_n_channels", "asdr_fm_set_gain", "asdr_fm_get_gain", "asdr_fm_set_deemphasis",
@@ -56,17 +56,11 @@ def fm_deemphasis_from_tau_us(tau_us):
     return _helper("deemphasis_from_tau_us", tau_us)
 
 
-def _c_int(v, what):
-    v = int(v)
-    if not -2**31 <= v < 2**31:
-        raise AsdrError(what)
-    return v
-
-
-class FmDemodulator(ResetStage):
+class FmDemodulator(RecordStage):
     """FM demodulators of n_channels tuner channels (include/asdr_fm.h).  device = NO_DEVICE (-1) gives the control plane and the
     state records only."""
     _prefix = "asdr_fm_"
+    _state_dtype = FM_STATE_DTYPE
 
     def __init__(self, n_channels, device=0):
         self._L = _lib()
@@ -133,29 +127,12 @@ class FmDemodulator(ResetStage):
         """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle as int).  i_ptr, q_ptr: int16 rows
         [n_channels][in_stride_blocks][128]; out_ptr: int16 rows [n_channels][out_stride_blocks][128]; the strides default to
         n_blocks."""
-        si = int(n_blocks) if in_stride_blocks is None else int(in_stride_blocks)
-        so = int(n_blocks) if out_stride_blocks is None else int(out_stride_blocks)
+        si = _stride(in_stride_blocks, n_blocks)
+        so = _stride(out_stride_blocks, n_blocks)
         self._chk(self._L.asdr_fm_update_device(self._h, C.c_void_p(i_ptr), C.c_void_p(q_ptr), si, C.c_void_p(out_ptr), so, int(n_blocks),
                                                 C.c_void_p(stream or None)))
 
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of FM_STATE_DTYPE; waits for the handle's work."""
-        st = np.zeros(self.n_channels, dtype=FM_STATE_DTYPE)
-        self._chk(self._L.asdr_fm_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes FM_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=FM_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_fm_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def clear(self):
-        self._call("clear")
-
-    def blocks(self):
-        return int(self._L.asdr_fm_blocks(self._h))
-
+    # state (read_state, write_state, clear, blocks: RecordStage)
     def offset_hz(self, deviation_hz):
         """The tuning offset of every channel in Hz, float64 [n_channels], from the DC meter m (hp_shift > 0): m / 2^15 is the mean
         of v, and v = 32767 at deviation_hz, the deviation the channel's gain was set for."""

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _stride, i, ip, lg, typed_library, vp
 from .binding import ALL, BLOCK, AsdrError
 
 GATE_EXPORTS = ["asdr_gate_create", "asdr_gate_destroy", "asdr_gate_n_channels", "asdr_gate_set_squelch", "asdr_gate_get_squelch",
@@ -43,10 +43,11 @@ class _DeviceInts:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
 
 
-class AudioGate(ResetStage):
+class AudioGate(RecordStage):
     """Audio meters and squelch of n_channels receivers over the chain's int16 audio rows (include/asdr_gate.h).
     device = NO_DEVICE (-1) gives the control plane and the state records only."""
     _prefix = "asdr_gate_"
+    _state_dtype = GATE_STATE_DTYPE
 
     def __init__(self, n_channels, device=0):
         self._L = _lib()
@@ -80,7 +81,7 @@ class AudioGate(ResetStage):
         """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle as int).  ptr: int16 rows
         [n_channels][stride_blocks][128] (stride_blocks defaults to n_blocks); rows_ptr: room for capacity_rows packet rows
         [n_blocks][128], or 0 for no packet.  count_tensor() / index_tensor() hold the result in stream order."""
-        stride = int(n_blocks) if stride_blocks is None else int(stride_blocks)
+        stride = _stride(stride_blocks, n_blocks)
         self._chk(self._L.asdr_gate_update_device(self._h, C.c_void_p(ptr), stride, int(n_blocks), C.c_void_p(rows_ptr or None),
                                                   int(capacity_rows), C.c_void_p(stream or None)))
 
@@ -89,7 +90,7 @@ class AudioGate(ResetStage):
         capacity_rows defaults to n_channels.  Only the count, the index and the delivered rows cross PCIe.  rows_out: a C-contiguous
         int16 array [capacity_rows or more, n_blocks, 128] to receive the rows (pinned memory copies fastest; the returned rows are
         then a view of it) instead of a new array per call."""
-        stride = int(n_blocks) if stride_blocks is None else int(stride_blocks)
+        stride = _stride(stride_blocks, n_blocks)
         cap = self.n_channels if capacity_rows is None else int(capacity_rows)
         index = np.empty(self.n_channels, dtype=np.int32)
         n_open = C.c_int(0)
@@ -121,21 +122,3 @@ class AudioGate(ResetStage):
         if not p:
             raise AsdrError(self._L.asdr_last_error().decode())
         return torch.as_tensor(_DeviceInts(p, (self.n_channels,), self), device="cuda")
-
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of GATE_STATE_DTYPE; waits for the gate's work."""
-        st = np.zeros(self.n_channels, dtype=GATE_STATE_DTYPE)
-        self._chk(self._L.asdr_gate_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes GATE_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=GATE_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_gate_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def clear(self):
-        self._chk(self._L.asdr_gate_clear(self._h))
-
-    def blocks(self):
-        return int(self._L.asdr_gate_blocks(self._h))

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _stride, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 PACKET_EXPORTS = ["asdr_packet_create", "asdr_packet_destroy", "asdr_packet_n_channels", "asdr_packet_fcs", "asdr_packet_format_address",
@@ -59,10 +59,11 @@ def packet_format_address(frame):
     return out.value.decode()
 
 
-class PacketDecoder(ResetStage):
+class PacketDecoder(RecordStage):
     """Packet decoders of n_channels audio rows with `ring` frame slots a channel (include/asdr_packet.h).  device = NO_DEVICE (-1)
     gives the control plane and the state records only."""
     _prefix = "asdr_packet_"
+    _state_dtype = PACKET_STATE_DTYPE
 
     def __init__(self, n_channels, ring=4, device=0):
         self._L = _lib()
@@ -86,7 +87,7 @@ class PacketDecoder(ResetStage):
     def update_device(self, in_ptr, n_blocks, in_stride_blocks=None, stream=0):
         """A raw device pointer (int), asynchronous on `stream` (a hipStream_t handle as int).  in_ptr: int16 rows
         [n_channels][in_stride_blocks][128]; the stride defaults to n_blocks."""
-        si = int(n_blocks) if in_stride_blocks is None else int(in_stride_blocks)
+        si = _stride(in_stride_blocks, n_blocks)
         self._chk(self._L.asdr_packet_update_device(self._h, C.c_void_p(in_ptr), si, int(n_blocks), C.c_void_p(stream or None)))
 
     # delivery
@@ -109,21 +110,3 @@ class PacketDecoder(ResetStage):
         p, l = np.zeros(self.n_channels, dtype=np.uint32), np.zeros(self.n_channels, dtype=np.uint32)
         self._chk(self._L.asdr_packet_ring_state(self._h, p.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p)))
         return p, l
-
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of PACKET_STATE_DTYPE; waits for the handle's work."""
-        st = np.zeros(self.n_channels, dtype=PACKET_STATE_DTYPE)
-        self._chk(self._L.asdr_packet_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes PACKET_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=PACKET_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_packet_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def clear(self):
-        self._call("clear")
-
-    def blocks(self):
-        return int(self._L.asdr_packet_blocks(self._h))

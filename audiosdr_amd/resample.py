@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from ._stage import RecordStage, _stride, i, ip, lg, ll, typed_library, vp
 from .binding import AsdrError
 
 RESAMPLE_EXPORTS = ["asdr_resampler_create", "asdr_resampler_create_custom", "asdr_resampler_destroy", "asdr_resampler_n_channels",
@@ -36,11 +36,15 @@ def _taps_array(taps, up):
     return t.astype(np.int16)
 
 
-class AudioResampler(ResetStage):
+class AudioResampler(RecordStage):
     """Resampler of n_channels receivers' audio rows from 44.1 kHz to fs_out (include/asdr_resample.h).  Either fs_out (the default
     filter of that rate) or up, down, taps [up * K] as h[k * up + phi] and shift (a custom filter).  device = NO_DEVICE (-1) gives
     the control plane and the state records only."""
     _prefix = "asdr_resampler_"
+    _state_dtype = np.int16
+
+    def _record_shape(self):           # a record: the channel's last 256 input samples, oldest first
+        return (RESAMPLE_STATE_SAMPLES,)
 
     def __init__(self, n_channels, fs_out=12000, device=0, up=None, down=None, taps=None, shift=15):
         self._L = _lib()
@@ -103,19 +107,7 @@ class AudioResampler(ResetStage):
         [n_channels][stride_blocks][128] (stride_blocks defaults to n_blocks); out_ptr: int16 rows [..][out_stride].  With index_ptr /
         count_ptr (device int32 [..] and int32, e.g. a gate's index_tensor().data_ptr() / count_tensor().data_ptr()) row i is channel
         index[i] for i < min(count, capacity_rows); otherwise row c is channel c.  Returns the per-row output count."""
-        stride = int(n_blocks) if stride_blocks is None else int(stride_blocks)
+        stride = _stride(stride_blocks, n_blocks)
         return int(self._chk(self._L.asdr_resampler_update_device(self._h, C.c_void_p(ptr or None), stride, int(n_blocks), C.c_void_p(out_ptr or None),
                                                                   int(out_stride), C.c_void_p(index_ptr or None), C.c_void_p(count_ptr or None),
                                                                   int(capacity_rows), C.c_void_p(stream or None))))
-
-    # state
-    def read_state(self):
-        """int16 [n_channels, 256]: every channel's last 256 input samples, oldest first; waits for the resampler's work."""
-        st = np.zeros((self.n_channels, RESAMPLE_STATE_SAMPLES), dtype=np.int16)
-        self._chk(self._L.asdr_resampler_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes int16 [k, 256] records into `channels` (default 0 .. k - 1); every channel is checked before one is written."""
-        rec = np.ascontiguousarray(records, dtype=np.int16).reshape(-1, RESAMPLE_STATE_SAMPLES)
-        self._chk(self._L.asdr_resampler_write_state(self._h, _channel_ptr(channels, rec.shape[0]), int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))

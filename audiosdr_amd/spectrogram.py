@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, ll, typed_library, vp
+from ._stage import RecordStage, _stride, i, ip, lg, ll, typed_library, vp
 from .binding import AsdrError
 
 SPECTROGRAM_EXPORTS = ["asdr_spectrogram_create", "asdr_spectrogram_destroy", "asdr_spectrogram_n_channels", "asdr_spectrogram_n_fft",
@@ -32,13 +32,17 @@ def _lib():
     return typed_library("asdr_spectrogram_", _API)
 
 
-class AudioSpectrogram(ResetStage):
+class AudioSpectrogram(RecordStage):
     """Spectrogram of n_channels receivers' int16 audio rows (include/asdr_spectrogram.h): frames of n_fft samples (a power of two in
     128 .. 8192) every hop samples (n_fft / 16 .. n_fft, default n_fft / 2), of which the bins first_bin .. first_bin + n_bins - 1
     (default: all n_fft / 2 + 1) are written per frame, as |X|^2 (kind "power") or (re, im) (kind "complex"), float32, scaled by
     1 / n_fft and not window-corrected.  window: "rect", "hann" or a float32 array [n_fft].  device = NO_DEVICE (-1) gives the control
     plane and the state records only."""
     _prefix = "asdr_spectrogram_"
+    _state_dtype = np.int16
+
+    def _record_shape(self):           # a record: the channel's last n_fft input samples, oldest first
+        return (self.n_fft,)
 
     def __init__(self, n_channels, n_fft=8192, hop=None, first_bin=0, n_bins=None, window="hann", kind="power", device=0):
         self._L = _lib()
@@ -128,19 +132,7 @@ class AudioSpectrogram(ResetStage):
         [n_channels][stride_samples] (stride_samples defaults to n_samples); out_ptr: float32 rows [..][out_stride][frame_floats].
         With index_ptr / count_ptr (device int32 [..] and int32, e.g. a gate's index_tensor().data_ptr() / count_tensor().data_ptr())
         row i is channel index[i] for i < min(count, capacity_rows); otherwise row c is channel c.  Returns the per-row frame count."""
-        stride = int(n_samples) if stride_samples is None else int(stride_samples)
+        stride = _stride(stride_samples, n_samples)
         return int(self._chk(self._L.asdr_spectrogram_update_device(self._h, C.c_void_p(ptr or None), stride, int(n_samples), C.c_void_p(out_ptr or None),
                                                                     int(out_stride), C.c_void_p(index_ptr or None), C.c_void_p(count_ptr or None),
                                                                     int(capacity_rows), C.c_void_p(stream or None))))
-
-    # state
-    def read_state(self):
-        """int16 [n_channels, n_fft]: every channel's last n_fft input samples, oldest first; waits for the spectrogram's work."""
-        st = np.zeros((self.n_channels, self.n_fft), dtype=np.int16)
-        self._chk(self._L.asdr_spectrogram_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes int16 [k, n_fft] records into `channels` (default 0 .. k - 1); every channel is checked before one is written."""
-        rec = np.ascontiguousarray(records, dtype=np.int16).reshape(-1, self.n_fft)
-        self._chk(self._L.asdr_spectrogram_write_state(self._h, _channel_ptr(channels, rec.shape[0]), int(rec.shape[0]), rec.ctypes.data_as(C.c_void_p)))

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._stage import ResetStage, _channel_ptr, i, ip, lg, typed_library, vp
+from ._stage import RecordStage, _c_int, _stride, i, ip, lg, typed_library, vp
 from .binding import ALL, AsdrError
 
 TONE_EXPORTS = ["asdr_tone_create", "asdr_tone_destroy", "asdr_tone_n_channels", "asdr_tone_set_tones", "asdr_tone_get_tones",
@@ -46,13 +46,6 @@ def _lib():
     return typed_library("asdr_tone_", _API)
 
 
-def _c_int(v, what):
-    v = int(v)
-    if not -2**31 <= v < 2**31:
-        raise AsdrError(what)
-    return v
-
-
 def tone_highpass_design(fc_hz, sections):
     """asdr_tone_highpass_design: the Q28 coefficients (b0, b1, b2, a1, a2) of the bilinear Butterworth high-pass of order
     2 sections at 44.1 kHz, int32 [sections][5]."""
@@ -74,10 +67,11 @@ def tone_min_power(amplitude, window_blocks):
     return v
 
 
-class ToneSquelch(ResetStage):
+class ToneSquelch(RecordStage):
     """Tone squelches of n_channels audio rows (include/asdr_tone.h).  device = NO_DEVICE (-1) gives the control plane and the state
     records only."""
     _prefix = "asdr_tone_"
+    _state_dtype = TONE_STATE_DTYPE
 
     def __init__(self, n_channels, device=0):
         self._L = _lib()
@@ -161,29 +155,12 @@ class ToneSquelch(ResetStage):
         """Raw device pointers (ints), asynchronous on `stream` (a hipStream_t handle as int).  in_ptr: int16 rows
         [n_channels][in_stride_blocks][128]; out_ptr: int16 rows [n_channels][out_stride_blocks][128]; the strides default to
         n_blocks."""
-        si = int(n_blocks) if in_stride_blocks is None else int(in_stride_blocks)
-        so = int(n_blocks) if out_stride_blocks is None else int(out_stride_blocks)
+        si = _stride(in_stride_blocks, n_blocks)
+        so = _stride(out_stride_blocks, n_blocks)
         self._chk(self._L.asdr_tone_update_device(self._h, C.c_void_p(in_ptr), si, C.c_void_p(out_ptr), so, int(n_blocks),
                                                   C.c_void_p(stream or None)))
 
-    # state
-    def read_state(self):
-        """Structured array [n_channels] of TONE_STATE_DTYPE; waits for the handle's work."""
-        st = np.zeros(self.n_channels, dtype=TONE_STATE_DTYPE)
-        self._chk(self._L.asdr_tone_read_state(self._h, st.ctypes.data_as(C.c_void_p)))
-        return st
-
-    def write_state(self, records, channels=None):
-        """Writes TONE_STATE_DTYPE records into `channels` (default 0 .. len - 1); checked as a whole before one is written."""
-        rec = np.ascontiguousarray(records, dtype=TONE_STATE_DTYPE).reshape(-1)
-        self._chk(self._L.asdr_tone_write_state(self._h, _channel_ptr(channels, rec.size), int(rec.size), rec.ctypes.data_as(C.c_void_p)))
-
-    def clear(self):
-        self._call("clear")
-
-    def blocks(self):
-        return int(self._L.asdr_tone_blocks(self._h))
-
+    # state (read_state, write_state, clear, blocks: RecordStage)
     def decoded_hz(self):
         """The table frequency of every channel's `detected`, float64 [n_channels]; NaN where no tone is detected."""
         hz, _ = self.get_tones()
