@@ -30,5 +30,7 @@ from .dcs import (DCS_ANY, DCS_CODES, DCS_EXPORTS, DCS_MAX_CODES, DCS_NARROW_ROW
                   DCS_WIDE_CHANNELS, DcsSquelch, dcs_word)
 from .packet import (PACKET_EXPORTS, PACKET_FRAME_DTYPE, PACKET_MAX_PAYLOAD, PACKET_MAX_RING, PACKET_NARROW_ROWS,  # noqa: E402
                      PACKET_ROWS, PACKET_STATE_DTYPE, PACKET_WIDE_CHANNELS, PacketDecoder, packet_fcs, packet_format_address)
+from .cw import (CW_EVENT_DTYPE, CW_EXPORTS, CW_FLAG_UNKNOWN, CW_MAX_RING, CW_NARROW_ROWS, CW_ROWS, CW_STATE_DTYPE,  # noqa: E402
+                 CW_WIDE_CHANNELS, CwDecoder, cw_pitch_step)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -1,4 +1,4 @@
-"""What the ctypes mirrors of every handle but the receiver batch (gate.py, resample.py, codec.py, spectrogram.py, fm.py, tone.py, dcs.py, packet.py, tuner.py,
+"""What the ctypes mirrors of every handle but the receiver batch (gate.py, resample.py, codec.py, spectrogram.py, fm.py, tone.py, dcs.py, packet.py, cw.py, tuner.py,
 front.py) share: the typing of a handle's entry points, the life of a handle, the state records of an audio stage (RecordStage), and the small
 conversions of their arguments (_c_int, _stride)."""
 import ctypes as C

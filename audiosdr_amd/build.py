@@ -16,7 +16,7 @@ SOURCES = ["asdr_kernels.hip", "asdr_host.cpp", "asdr_front.hip", "asdr_front_ho
            "asdr_tuner_monitor.hip", "asdr_tuner_palette.hip", "asdr_tuner_condition.hip", "asdr_tuner_host.cpp", "asdr_state.hip", "asdr_tuner_state.hip", "asdr_gate.hip", "asdr_gate_host.cpp",
            "asdr_resample.hip", "asdr_resample_host.cpp", "asdr_codec.hip", "asdr_codec_host.cpp",
            "asdr_spectrogram.hip", "asdr_spectrogram_host.cpp", "asdr_fm.hip", "asdr_fm_host.cpp", "asdr_tone.hip", "asdr_tone_host.cpp",
-           "asdr_dcs.hip", "asdr_dcs_host.cpp", "asdr_packet.hip", "asdr_packet_host.cpp"]
+           "asdr_dcs.hip", "asdr_dcs_host.cpp", "asdr_packet.hip", "asdr_packet_host.cpp", "asdr_cw.hip", "asdr_cw_host.cpp"]
 DEPS = SOURCES + ["asdr_device.h", "asdr_fir.h", "asdr_tables.h", "asdr_front_device.h", "asdr_front_tables.h", "asdr_tuner_device.h", "asdr_tuner_state.h", "asdr_gate_device.h",
                   "asdr_tuner_tables.h", os.path.join("..", "..", "include", "asdr.h"), os.path.join("..", "..", "include", "asdr_front.h"),
                   os.path.join("..", "..", "include", "asdr_tuner.h"), os.path.join("..", "..", "include", "asdr_gate.h"),
@@ -26,7 +26,8 @@ DEPS = SOURCES + ["asdr_device.h", "asdr_fir.h", "asdr_tables.h", "asdr_front_de
                   "asdr_fm_device.h", os.path.join("..", "..", "include", "asdr_fm.h"),
                   "asdr_tone_device.h", os.path.join("..", "..", "include", "asdr_tone.h"),
                   "asdr_dcs_device.h", os.path.join("..", "..", "include", "asdr_dcs.h"),
-                  "asdr_packet_device.h", os.path.join("..", "..", "include", "asdr_packet.h")]
+                  "asdr_packet_device.h", os.path.join("..", "..", "include", "asdr_packet.h"),
+                  "asdr_cw_device.h", os.path.join("..", "..", "include", "asdr_cw.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-fast-math", "-fPIC", "-shared",
          "-Wall", "-Wno-unused-function", "-Wno-unused-value"]

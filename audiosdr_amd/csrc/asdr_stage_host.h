@@ -1,5 +1,5 @@
 // asdr_stage_host.h -- what the host sides of every handle but the receiver batch share (the audio stages: gate, resampler, codec,
-// spectrogram, FM demodulator, tone squelch, DCS squelch, packet decoder; the tuner bank; the front end's three batches): the device, stream and events of a
+// spectrogram, FM demodulator, tone squelch, DCS squelch, packet decoder, CW decoder; the tuner bank; the front end's three batches): the device, stream and events of a
 // handle and the rules that order its work (a launch on another stream than the last waits for the last; whatever frees or rewrites
 // what a launch may still use waits for the handle's work first), the kept grow-on-demand buffer, and the double buffer of carry rows.
 // For the audio stages it also states, once each: the handle and channel check of a setter or getter (stage_check_channel), the
